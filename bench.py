@@ -12,13 +12,16 @@ One "step" = one PPO iteration on every rank: 24 x (actor-critic act -> imx_acti
 (MLP fwd -> imx_ppo_loss -> MLP bwd -> [RCCL all-reduce of the flat gradient bucket] -> imx_adam_step).
 value = num_envs x 24 x world_size x K / wall time (max over ranks), inputs resident in HBM before the timed region.
 
-Besides the contract line it reports
+A plain run sets up, warms up, times the K steps and prints the contract line.  ``--dump-outputs DIR`` then writes what the last
+timed iteration handed its caller as DIR/<name>.npy (see dump_outputs).  ``--full`` adds, after the timed steps,
   * env_step_path: the post-physics path alone (3 env kernels per step + GAE per 24 steps, no policy) -- the
     like-for-like counterpart of cpu_baseline;
   * roofline: the dominant hand-written kernel (k_obs = observation assembly + fused height-scanner ray-cast),
     algorithmic bytes per launch / average launch duration from HIP events on the launch stream, vs the 8 TB/s peak;
   * cpu_baseline: the CPU restatement of the reference managers + GAE (oracle/, kind "port") on this box's host
-    cores, bounded sample, rank 0, N=1 only.
+    cores, bounded sample, rank 0, N=1 only;
+  * roofline_large_n / roofline_mfma / roofline_producers (--full-step): the observation kernel at 65 536 envs, imx_mlp_dw against
+    the f32 MFMA peak, the producer kernels of the full step.
 """
 
 from __future__ import annotations
@@ -489,6 +492,51 @@ def time_mlp_dw(alg, M: int, device, launches: int = 30) -> dict:
                             "frac": flops / secs_k / 1e12 / MFMA_F32_PEAK_TFLOPS, "avg_launch_us": secs_k / n * 1e6}}
 
 
+DUMP_BYTES_MAX = 64 * 1000 * 1000  # all files of one --dump-outputs together, .npy headers included
+
+
+def dump_outputs(runner, out_dir: str) -> dict:
+    """``--dump-outputs``: what the last timed iteration handed its caller, one float32 DIR/<name>.npy per array -- the rollout
+    storage (storage_*: observations, actions, rewards, dones, values, log-probs, mu, sigma, GAE returns and advantages), the
+    observations after the last env step (last_obs), the updated policy parameters (policy_params, flat bucket order) and the loss
+    scalars (loss_*, learning_rate).  Arrays with an env axis keep a fixed seeded sample of envs (the same for all of them) when the
+    whole set would exceed 64 MB.  Scalars are float64."""
+    import numpy as np
+
+    alg, st = runner.alg, runner.alg.storage
+    N = st.num_envs
+    per_env = {}  # name -> (tensor, env axis)
+    for name in ("observations", "privileged_observations", "actions", "rewards", "dones", "values", "actions_log_prob", "returns",
+                 "advantages", "mu", "sigma"):
+        t = getattr(st, name, None)
+        if t is not None:
+            per_env["storage_" + name] = (t, 1)
+    per_env["last_obs"] = (runner.last_obs, 0)
+    if runner.privileged_obs_type is not None:
+        per_env["last_critic_obs"] = (runner.last_critic_obs, 0)
+    whole = {"policy_params": alg.bucket.flat[:alg.bucket.numel]}
+    fixed = sum(4 * t.numel() for t in whole.values())
+    env_bytes = sum(4 * t.numel() for t, _ in per_env.values())
+    budget = DUMP_BYTES_MAX - 64 * 1024  # headroom for the .npy headers and the scalars
+    k = N if fixed + env_bytes <= budget else max(1, (budget - fixed) * N // env_bytes)
+    idx = None
+    if k < N:
+        idx = torch.randperm(N, generator=torch.Generator().manual_seed(0))[:k].sort().values.to(st.rewards.device)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {n: (t if idx is None else t.index_select(ax, idx)) for n, (t, ax) in per_env.items()}
+    arrays.update(whole)
+    written = 0
+    for n, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, n + ".npy"), a)
+        written += a.nbytes
+    scalars = {"loss_" + n: v for n, v in alg.loss_dict().items()}
+    scalars["learning_rate"] = alg.learning_rate
+    for n, v in scalars.items():
+        np.save(os.path.join(out_dir, n + ".npy"), np.asarray(v, dtype=np.float64))
+    return {"dir": out_dir, "arrays": len(arrays) + len(scalars), "bytes": written, "envs_sampled": k, "num_envs": N}
+
+
 def self_launch(n_gpus: int) -> int:
     """``python bench.py --gpus N`` (N > 1) outside a launcher: run the N ranks as a child ``torch.distributed.run`` and relay rank 0's
     line.  This parent has not initialised HIP (importing torch does not) and never does: the children are fresh processes."""
@@ -532,10 +580,13 @@ def main():
                     "(command term, contact sensor, reset / interval events, terrain curriculum, ArticulationData refresh, ActuatorNetLSTM x "
                     "decimation): all of it inside the captured rollout; reported as env_step_path_full + roofline_producers")
     ap.add_argument("--no-graph", action="store_true", help="eager rollout instead of one hipGraph replay per rollout")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-large-n", action="store_true", help="skip the 65 536-env launches of the observation kernel (they share "
-                    "its name and would skew a rocprofv3 --stats average taken over this command)")
-    ap.add_argument("--cpu-budget", type=float, default=12.0)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full only: skip cpu_baseline")
+    ap.add_argument("--no-large-n", action="store_true", help="--full only: skip the 65 536-env launches of the observation kernel (they "
+                    "share its name and would skew a rocprofv3 --stats average taken over this command)")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="--full only: seconds cpu_baseline spends on its timed sample")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure env_step_path, the roofline blocks and "
+                    "cpu_baseline (a plain run only sets up, warms up, times --steps iterations and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed iteration computed as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:  # before anything touches the GPU
         raise SystemExit(self_launch(args.gpus))
@@ -659,8 +710,8 @@ def main():
     stats = runner.alg.loss_dict()
     collect_ms = sum(ev[3 * k].elapsed_time(ev[3 * k + 1]) for k in range(args.steps)) / args.steps
     update_ms = sum(ev[3 * k + 1].elapsed_time(ev[3 * k + 2]) for k in range(args.steps)) / args.steps
+    dumped = dump_outputs(runner, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
-    # --- secondary measurements on rank 0 (outside the timed region)
     out = {
         "metric": ("env-steps/sec (whole node), Anymal-C rough 4096 envs/GPU, RSL-RL PPO iteration (collect+GAE+update)"
                    if args.task == TASK and args.num_envs == 4096 else
@@ -685,7 +736,10 @@ def main():
                         "grad_allreduce_per_iteration": int(runner.alg.num_learning_epochs) * int(runner.alg.num_mini_batches),
                         "bucket_bytes": 4 * (runner.alg.bucket.numel + 8)} if (world > 1 or force_dist) else None),
     }
-    if rank == 0:
+    if dumped is not None:
+        out["dump_outputs"] = dumped
+    # --- secondary measurements on rank 0 (--full, outside the timed region)
+    if rank == 0 and args.full:
         env_rate, env_step_s = time_env_path(env, T, iters=20)
         out["env_step_path_full" if args.full_step else "env_step_path"] = {
             "value": env_rate, "unit": "env-steps/s", "us_per_env_step_batch": env_step_s * 1e6,
@@ -733,12 +787,13 @@ def main():
                 out["roofline_mfma"]["traffic"] = json.load(open(tf1)).get("k_mlp_dw_bytes_per_launch")
         except Exception as exc:  # secondary measurement only
             out["roofline_mfma"] = {"error": str(exc)}
-        out["ppo"] = {k: round(v, 6) for k, v in stats.items()}
-        out["ppo"]["learning_rate"] = runner.alg.learning_rate
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.task, args.num_envs, T, args.cpu_budget)
             if "env_step_path" in out:
                 out["env_step_path"]["vs_cpu_baseline"] = env_rate / out["cpu_baseline"]["value"]
+    if rank == 0:
+        out["ppo"] = {k: round(v, 6) for k, v in stats.items()}
+        out["ppo"]["learning_rate"] = runner.alg.learning_rate
         sys.stdout.flush()
         os.dup2(real_stdout, 1)
         print(json.dumps(out), flush=True)

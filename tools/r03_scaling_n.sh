@@ -2,7 +2,7 @@
 # one GPU, the headline task at other env counts per GPU (the driver's line is 4096): PPO iteration and post-physics path
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r03s; mkdir -p $O; cd $R
 for n in 1024 4096 16384 65536; do
-  python3 bench.py --num-envs $n --steps 5 --warmup 2 --no-cpu-baseline --no-large-n > $O/n_$n.json 2> $O/n_$n.err
+  python3 bench.py --full --num-envs $n --steps 5 --warmup 2 --no-cpu-baseline --no-large-n > $O/n_$n.json 2> $O/n_$n.err
   python3 - <<PY
 import json
 d=json.loads(open("$O/n_$n.json").read().strip().splitlines()[-1])

@@ -138,7 +138,23 @@ enum imx_rew_op {
     IMX_W_TRACK_ANG_VEL_Z_WORLD_EXP,  /* ...:99-106 */
     IMX_W_JOINT_POS_TARGET_L2,        /* isaaclab_tasks .../classic/cartpole/mdp/rewards.py:19-26 p0=target */
     IMX_W_EXTERNAL,                   /* aux0 = column in ext_reward */
-    IMX_W_BODY_LIN_ACC_L2             /* :125-128 ids = asset bodies; state.body_lin_acc_w */
+    IMX_W_BODY_LIN_ACC_L2,            /* :125-128 ids = asset bodies; state.body_lin_acc_w */
+    /* isaaclab_tasks .../velocity/config/spot/mdp/rewards.py.  "stand still" = ||cmd|| == 0 (all 3 components) and ||v_b,xy|| <= threshold */
+    IMX_W_AIR_TIME_REWARD,            /* :31-58   ids = 4 sensor bodies; p0 = mode_time, p1 = velocity_threshold */
+    IMX_W_BASE_ANGULAR_VELOCITY_REWARD, /* :61-68 p0 = std: exp(-|cmd_z - w_b,z| / std) */
+    IMX_W_BASE_LINEAR_VELOCITY_REWARD,  /* :71-83 p0 = std, p1 = ramp_rate, p2 = ramp_at_vel */
+    IMX_W_GAIT_REWARD,                /* :86-177  ids = sensor bodies pair0[0], pair0[1], pair1[0], pair1[1]; p0 = std, p1 = max_err^2,
+                                                  p2 = velocity_threshold */
+    IMX_W_FOOT_CLEARANCE_REWARD,      /* :180-188 ids = asset bodies; p0 = target_height, p1 = std, p2 = tanh_mult; state.body_pos_w */
+    IMX_W_ACTION_SMOOTHNESS_PENALTY,  /* :196-198 ||a - a_prev|| */
+    IMX_W_AIR_TIME_VARIANCE_PENALTY,  /* :201-212 ids = sensor bodies; unbiased var of last air / contact time clipped at 0.5 */
+    IMX_W_BASE_MOTION_PENALTY,        /* :216-222 */
+    IMX_W_BASE_ORIENTATION_PENALTY,   /* :225-232 */
+    IMX_W_FOOT_SLIP_PENALTY,          /* :235-249 ids = sensor bodies, ids2 = asset bodies; p0 = threshold */
+    IMX_W_JOINT_ACCELERATION_PENALTY, /* :252-256 ids = ALL joints (the function ignores asset_cfg.joint_ids) */
+    IMX_W_JOINT_POSITION_PENALTY,     /* :259-268 ids = all joints; p0 = stand_still_scale, p1 = velocity_threshold */
+    IMX_W_JOINT_TORQUES_PENALTY,      /* :271-275 ids = all joints */
+    IMX_W_JOINT_VELOCITY_PENALTY      /* :278-282 ids = all joints */
 };
 
 /* observation ops -- envs/mdp/observations.py */
@@ -193,6 +209,8 @@ typedef struct imx_state {
     const float* body_lin_acc_w;        /* (N,NB,3) ArticulationData.body_lin_acc_w */
     const float* command_time_left;     /* (N)   CommandTerm.time_left (managers/command_manager.py:60-61) */
     const int64_t* command_counter;     /* (N)   CommandTerm.command_counter */
+    const float* body_pos_w;            /* (N,NB,3) ArticulationData.body_pos_w, or NULL unless a term reads it */
+    const float* last_contact_time;     /* (N,B) ContactSensorData.last_contact_time, or NULL unless a term reads it */
 } imx_state_t;
 
 /* ---- manager state + outputs (caller-owned, persistent across steps) ------------------------------------------ */
@@ -265,7 +283,9 @@ enum imx_event_op {
     IMX_E_RESET_JOINTS_BY_SCALE,        /* :987-1015;  ranges: position lo, hi, velocity lo, hi */
     IMX_E_RESET_JOINTS_BY_OFFSET,       /* :1020-1049 */
     IMX_E_PUSH_BY_SETTING_VELOCITY,     /* :795-820;   ranges: lo/hi x 6 */
-    IMX_E_APPLY_EXTERNAL_FORCE_TORQUE   /* :764-791;   ranges: force lo, hi, torque lo, hi; body ids */
+    IMX_E_APPLY_EXTERNAL_FORCE_TORQUE,  /* :764-791;   ranges: force lo, hi, torque lo, hi; body ids */
+    IMX_E_RESET_JOINTS_AROUND_DEFAULT   /* isaaclab_tasks .../velocity/config/spot/mdp/events.py:26-60; ranges as the joint resets: the
+                                           default +- range is clamped to the soft limits BEFORE sampling */
 };
 typedef struct imx_event_term {
     int32_t op;                            /* enum imx_event_op */
@@ -753,7 +773,8 @@ int imx_mlp_head_fwd_bwd(int64_t M, int K, int A, const float* z_d, int64_t ldz,
 
 /* reset_root_state_uniform (envs/mdp/events.py:823-868) and reset_joints_by_scale / _by_offset (:987-1049).
  * ranges28 (HOST) = pose {x,y,z,roll,pitch,yaw} (lo,hi) x6, velocity (lo,hi) x6, joint position lo,hi, joint velocity lo,hi.
- * joint_mode 0 = by scale, 1 = by offset, < 0 = joints untouched.  default_root_state (N,13: pos, quat wxyz, lin, ang),
+ * joint_mode 0 = by scale, 1 = by offset, 2 = around default (reset_joints_around_default: default + range clamped to the
+ * soft limits, then sampled), < 0 = joints untouched.  default_root_state (N,13: pos, quat wxyz, lin, ang),
  * soft_joint_pos_limits (N,J,2), soft_joint_vel_limits (N,J).  uniforms_d: optional (N, 12 + 2J) = [pose 6 | velocity 6 |
  * joint pos J | joint vel J].  Outputs = what write_root_pose_to_sim (N,7), write_root_velocity_to_sim (N,6) and
  * write_joint_state_to_sim (N,J)x2 receive. */

@@ -109,23 +109,27 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
     for (int k = 0; k < p->nrew; ++k) {
         const int32_t* r = &w[p->rew_off + k * IMX_REC_WORDS];
         const int op = r[IMX_R_OP];
-        IMX_REQUIRE(op >= IMX_W_IS_ALIVE && op <= IMX_W_BODY_LIN_ACC_L2, "plan: unknown reward op %d", op);
+        IMX_REQUIRE(op >= IMX_W_IS_ALIVE && op <= IMX_W_JOINT_VELOCITY_PENALTY, "plan: unknown reward op %d", op);
         IMX_REQUIRE(r[IMX_R_OUT] == k, "plan: reward record %d has index %d", k, r[IMX_R_OUT]);
         int limit = p->J;
         const char* what = "joint";
         if (op == IMX_W_UNDESIRED_CONTACTS || op == IMX_W_CONTACT_FORCES || op == IMX_W_FEET_AIR_TIME ||
-            op == IMX_W_FEET_AIR_TIME_POSITIVE_BIPED || op == IMX_W_FEET_SLIDE) {
+            op == IMX_W_FEET_AIR_TIME_POSITIVE_BIPED || op == IMX_W_FEET_SLIDE || op == IMX_W_AIR_TIME_REWARD || op == IMX_W_GAIT_REWARD ||
+            op == IMX_W_AIR_TIME_VARIANCE_PENALTY || op == IMX_W_FOOT_SLIP_PENALTY) {
             limit = p->B;
             what = "body";
         } else if (op == IMX_W_IS_TERMINATED_TERM) {
             limit = p->nterm;
             what = "termination-term";
-        } else if (op == IMX_W_BODY_LIN_ACC_L2) {
+        } else if (op == IMX_W_BODY_LIN_ACC_L2 || op == IMX_W_FOOT_CLEARANCE_REWARD) {
             limit = p->NB;
             what = "asset body";
         }
         if (check_ids(w, r[IMX_R_IDS_OFF], r[IMX_R_NIDS], limit, what, k)) return 1;
-        if (op == IMX_W_FEET_SLIDE) {
+        if (op == IMX_W_AIR_TIME_REWARD || op == IMX_W_GAIT_REWARD)
+            IMX_REQUIRE(r[IMX_R_NIDS] == 4, "plan: reward record %d (op %d) needs exactly 4 feet", k, op);
+        if (op == IMX_W_AIR_TIME_VARIANCE_PENALTY) IMX_REQUIRE(r[IMX_R_NIDS] > 0, "plan: air_time_variance_penalty without feet");
+        if (op == IMX_W_FEET_SLIDE || op == IMX_W_FOOT_SLIP_PENALTY) {
             IMX_REQUIRE(r[IMX_R_NIDS2] == r[IMX_R_NIDS], "plan: feet_slide needs equally many sensor and asset bodies");
             if (check_ids(w, r[IMX_R_IDS2_OFF], r[IMX_R_NIDS2], p->NB, "asset body", k)) return 1;
         }

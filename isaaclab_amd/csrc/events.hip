@@ -1,7 +1,8 @@
 // Reset / interval events and the terrain curriculum as masked kernels.
 //
 // Reference (isaaclab/isaaclab/envs/mdp/events.py): reset_root_state_uniform :823-868, reset_joints_by_scale :987-1015,
-// reset_joints_by_offset :1020-1049, push_by_setting_velocity :795-820; terrain_levels_vel
+// reset_joints_by_offset :1020-1049, push_by_setting_velocity :795-820; reset_joints_around_default
+// (isaaclab_tasks/.../velocity/config/spot/mdp/events.py:26-60); terrain_levels_vel
 // (isaaclab_tasks/.../locomotion/velocity/mdp/curriculums.py:26-55) + TerrainImporter.update_env_origins
 // (isaaclab/isaaclab/terrains/terrain_importer.py:307-326).  The reference runs them on a compacted env_ids list with a
 // host sync per term (len(env_ids), nonzero); here they take the reset mask of imx_terminations_rewards and rewrite only
@@ -18,7 +19,7 @@ namespace {
 struct ResetCfg {
     float pose_lo[6], pose_hi[6], vel_lo[6], vel_hi[6];
     float jpos_lo, jpos_hi, jvel_lo, jvel_hi;
-    int joint_mode;  // 0 scale, 1 offset, < 0: joints untouched
+    int joint_mode;  // 0 scale, 1 offset, 2 around default, < 0: joints untouched
 };
 
 __device__ __forceinline__ float draw(const float* __restrict__ U, int64_t stride, int64_t e, int col, uint64_t seed, uint32_t step) {
@@ -68,8 +69,14 @@ k_reset_events(int64_t N, int J, ResetCfg c, const uint8_t* __restrict__ mask, c
             const int64_t e = q / J;
             const int j = (int)(q - e * J);
             if (mask && !mask[e]) continue;
-            const float sp = draw(U, ustride, e, 12 + j, seed, step) * (c.jpos_hi - c.jpos_lo) + c.jpos_lo;
-            const float sv = draw(U, ustride, e, 12 + J + j, seed, step) * (c.jvel_hi - c.jvel_lo) + c.jvel_lo;
+            const float up = draw(U, ustride, e, 12 + j, seed, step), uv = draw(U, ustride, e, 12 + J + j, seed, step);
+            if (c.joint_mode == 2) {  // reset_joints_around_default: the range is clamped to the soft limits first, then sampled
+                jpos[q] = around_default(djp[q], c.jpos_lo, c.jpos_hi, plim[2 * q], plim[2 * q + 1], up);
+                jvel[q] = around_default(djv[q], c.jvel_lo, c.jvel_hi, -vlim[q], vlim[q], uv);
+                continue;
+            }
+            const float sp = up * (c.jpos_hi - c.jpos_lo) + c.jpos_lo;
+            const float sv = uv * (c.jvel_hi - c.jvel_lo) + c.jvel_lo;
             float p = c.joint_mode == 1 ? djp[q] + sp : djp[q] * sp;
             float v = c.joint_mode == 1 ? djv[q] + sv : djv[q] * sv;
             p = fminf(fmaxf(p, plim[2 * q]), plim[2 * q + 1]);  // clamp_(lo, hi): min(max(x, lo), hi)
@@ -170,7 +177,7 @@ extern "C" int imx_reset_events(int64_t N, int64_t J, const uint8_t* reset_mask_
     IMX_REQUIRE(joint_mode < 0 || (J > 0 && default_joint_pos_d && default_joint_vel_d && soft_joint_pos_limits_d &&
                                    soft_joint_vel_limits_d && joint_pos_d && joint_vel_d),
                 "imx_reset_events: joint reset (mode %d) needs the joint defaults, limits and outputs", joint_mode);
-    IMX_REQUIRE(joint_mode <= 1, "imx_reset_events: joint_mode %d (0 = by scale, 1 = by offset, < 0 = skip)", joint_mode);
+    IMX_REQUIRE(joint_mode <= 2, "imx_reset_events: joint_mode %d (0 = by scale, 1 = by offset, 2 = around default, < 0 = skip)", joint_mode);
     ResetCfg c;
     for (int k = 0; k < 6; ++k) {
         c.pose_lo[k] = ranges28[2 * k]; c.pose_hi[k] = ranges28[2 * k + 1];

@@ -170,6 +170,13 @@ IMX_DEV void quat_apply(float w, float x, float y, float z, float vx, float vy, 
 }
 
 // wrap_to_pi (isaaclab/utils/math.py:95-117), torch.remainder semantics
+// reset_joints_around_default (isaaclab_tasks/.../velocity/config/spot/mdp/events.py:48-58): lo/hi = clamp(default + range, limits),
+// then sample_uniform (utils/math.py:1313-1331) = u * (hi - lo) + lo
+IMX_DEV float around_default(float d, float r_lo, float r_hi, float lim_lo, float lim_hi, float u) {
+    const float lo = fminf(fmaxf(d + r_lo, lim_lo), lim_hi), hi = fminf(fmaxf(d + r_hi, lim_lo), lim_hi);
+    return u * (hi - lo) + lo;
+}
+
 IMX_DEV float wrap_to_pi(float a) {
     const float PI = 3.14159265358979323846f, TWO_PI = 6.28318530717958647692f;
     float m = fmodf(a + PI, TWO_PI);

@@ -117,7 +117,8 @@ __global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate(imx_orch_t o) 
             }
         }
         const float* __restrict__ U = T.uniforms_d;
-        if (T.op == IMX_E_RESET_JOINTS_BY_SCALE || T.op == IMX_E_RESET_JOINTS_BY_OFFSET) {  // events.py:987-1049
+        if (T.op == IMX_E_RESET_JOINTS_BY_SCALE || T.op == IMX_E_RESET_JOINTS_BY_OFFSET ||
+            T.op == IMX_E_RESET_JOINTS_AROUND_DEFAULT) {  // events.py:987-1049, spot/mdp/events.py:26-60
             // lane = joint of one valid env at a time (the same draws, keyed by (env, column)): 2 J samples + clamps per env spread over
             // the wave instead of a J-trip loop on the env's own lane
             const bool by_offset = T.op == IMX_E_RESET_JOINTS_BY_OFFSET;
@@ -125,6 +126,14 @@ __global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate(imx_orch_t o) 
                 const int64_t er = (int64_t)blockIdx.x * ORCH_BLOCK + (__ffsll((long long)m) - 1);  // wave-uniform
                 for (int j = lane; j < J; j += ORCH_BLOCK) {
                     const size_t q = (size_t)er * J + j;
+                    if (T.op == IMX_E_RESET_JOINTS_AROUND_DEFAULT) {  // range clamped to the soft limits first, then sampled
+                        const float vl = o.soft_joint_vel_limits_d[q];
+                        o.joint_pos_out_d[q] = around_default(o.default_joint_pos_d[q], T.ranges[0], T.ranges[1], o.soft_joint_pos_limits_d[2 * q],
+                                                              o.soft_joint_pos_limits_d[2 * q + 1], draw(U, 2 * (int64_t)J, er, j, o.seed, t, step));
+                        o.joint_vel_out_d[q] = around_default(o.default_joint_vel_d[q], T.ranges[2], T.ranges[3], -vl, vl,
+                                                              draw(U, 2 * (int64_t)J, er, J + j, o.seed, t, step));
+                        continue;
+                    }
                     const float sp = draw(U, 2 * (int64_t)J, er, j, o.seed, t, step) * (T.ranges[1] - T.ranges[0]) + T.ranges[0];
                     const float sv = draw(U, 2 * (int64_t)J, er, J + j, o.seed, t, step) * (T.ranges[3] - T.ranges[2]) + T.ranges[2];
                     float p = by_offset ? o.default_joint_pos_d[q] + sp : o.default_joint_pos_d[q] * sp;
@@ -167,7 +176,8 @@ __global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate(imx_orch_t o) 
                         d[7 + k] + (draw(U, 12, e, 6 + k, o.seed, t, step) * (T.ranges[12 + 2 * k + 1] - T.ranges[12 + 2 * k]) + T.ranges[12 + 2 * k]);
             } break;
             case IMX_E_RESET_JOINTS_BY_SCALE:
-            case IMX_E_RESET_JOINTS_BY_OFFSET: break;  // (worked off by the whole wave, below)
+            case IMX_E_RESET_JOINTS_BY_OFFSET:
+            case IMX_E_RESET_JOINTS_AROUND_DEFAULT: break;  // (worked off by the whole wave, below)
             case IMX_E_APPLY_EXTERNAL_FORCE_TORQUE: {  // events.py:764-791: two sample_uniform calls (forces, then torques) of (k, nb, 3)
                 const int nb = T.body_ids_d ? T.num_body_ids : NB;
                 for (int b = 0; b < nb; ++b) {
@@ -290,7 +300,7 @@ extern "C" int imx_reset_orchestrate(const imx_orch_t* o, imx_stream_t stream) {
                 IMX_REQUIRE(o->default_root_state_d && o->root_pose_out_d && o->root_vel_out_d, "imx_reset_orchestrate: reset_root_state_uniform needs "
                             "default_root_state, root_pose_out and root_vel_out");
                 break;
-            case IMX_E_RESET_JOINTS_BY_SCALE: case IMX_E_RESET_JOINTS_BY_OFFSET:
+            case IMX_E_RESET_JOINTS_BY_SCALE: case IMX_E_RESET_JOINTS_BY_OFFSET: case IMX_E_RESET_JOINTS_AROUND_DEFAULT:
                 IMX_REQUIRE(o->num_joints > 0 && o->default_joint_pos_d && o->default_joint_vel_d && o->soft_joint_pos_limits_d &&
                             o->soft_joint_vel_limits_d && o->joint_pos_out_d && o->joint_vel_out_d,
                             "imx_reset_orchestrate: a joint reset needs the joint defaults, limits and outputs");

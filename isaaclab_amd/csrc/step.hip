@@ -110,6 +110,12 @@ IMX_DEV float max_hist_force(const float* __restrict__ F, int64_t e, int H, int 
     return sqrtf(m);
 }
 
+// the gate of Spot's gait / air-time / joint-position terms (isaaclab_tasks .../velocity/config/spot/mdp/rewards.py:52-53):
+// torch.norm(cmd, dim=1) > 0 over all three command components, or torch.linalg.norm(v_b[:, :2]) > velocity_threshold
+IMX_DEV bool spot_active(float cx, float cy, float cz, float vx, float vy, float vth) {
+    return sqrtf((cx * cx + cy * cy) + cz * cz) > 0.0f || sqrtf(vx * vx + vy * vy) > vth;
+}
+
 // scratch layout for k_term_rew (4-byte words, nw = number of env groups; sized for the smallest group: ceil(N/16) groups)
 //   [0, nw*KA)               float  per-group partial sums of episode_sums over reset envs
 //   [.., + nw*NT)            int    per-group counts of term_dones over reset envs
@@ -568,6 +574,89 @@ k_term_rew(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, StepScratch s
                         const float* a = S.body_lin_acc_w + ((size_t)ec * P.NB + b) * 3;
                         return norm3(a[0], a[1], a[2]);
                     });
+                    break;
+                // ---- Spot (isaaclab_tasks .../velocity/config/spot/mdp/rewards.py).  "active" = torch.logical_or(||cmd|| > 0,
+                //      ||v_b,xy|| > velocity_threshold) with the norm of the WHOLE command, yaw rate included (:52-53, :150-151, :264-268)
+                case IMX_W_AIR_TIME_REWARD: {  // :31-58, ids = the 4 feet of the sensor
+                    const bool act = spot_active(cmdx, cmdy, cmdz, lbx, lby, f_of(r[IMX_R_P1]));
+                    f = sum_ids(ids, n, [&](int b) {
+                        const float at = S.current_air_time[ec * Bn + b], ct = S.current_contact_time[ec * Bn + b];
+                        const float t_max = fmaxf(at, ct);
+                        const float stance = fminf(fmaxf(ct - at, -p0), p0);  // clip(contact - air, -mode_time, mode_time)
+                        return act ? (t_max < p0 ? fminf(t_max, p0) : 0.0f) : stance;
+                    });
+                } break;
+                case IMX_W_BASE_ANGULAR_VELOCITY_REWARD: f = expf(-fabsf(cmdz - abz) / p0); break;  // :61-68
+                case IMX_W_BASE_LINEAR_VELOCITY_REWARD: {  // :71-83
+                    const float ex = cmdx - lbx, ey = cmdy - lby;
+                    const float err = sqrtf(ex * ex + ey * ey), mag = sqrtf(cmdx * cmdx + cmdy * cmdy);
+                    const float mult = fmaxf(1.0f + f_of(r[IMX_R_P1]) * (mag - f_of(r[IMX_R_P2])), 1.0f);
+                    f = expf(-err / p0) * mult;
+                } break;
+                case IMX_W_GAIT_REWARD: {  // :86-177, ids = pair0[0], pair0[1], pair1[0], pair1[1]; p1 = max_err**2
+                    const float p1 = f_of(r[IMX_R_P1]);
+                    float at[4], ct[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        at[u] = S.current_air_time[ec * Bn + ids[u]];
+                        ct[u] = S.current_contact_time[ec * Bn + ids[u]];
+                    }
+                    auto pair_reward = [&](float a0, float a1, float c0, float c1) {  // exp(-(clip(d1^2) + clip(d2^2)) / std)
+                        const float d1 = a0 - a1, d2 = c0 - c1;
+                        return expf(-(fminf(d1 * d1, p1) + fminf(d2 * d2, p1)) / p0);
+                    };
+                    const float sync = pair_reward(at[0], at[1], ct[0], ct[1]) * pair_reward(at[2], at[3], ct[2], ct[3]);
+                    // _async_reward_func(f0, f1): air(f0) against contact(f1), contact(f0) against air(f1)
+                    const float async = pair_reward(at[0], ct[2], ct[0], at[2]) * pair_reward(at[1], ct[3], ct[1], at[3]) *
+                                        pair_reward(at[0], ct[3], ct[0], at[3]) * pair_reward(at[2], ct[1], ct[2], at[1]);
+                    f = spot_active(cmdx, cmdy, cmdz, lbx, lby, f_of(r[IMX_R_P2])) ? sync * async : 0.0f;
+                } break;
+                case IMX_W_FOOT_CLEARANCE_REWARD: {  // :180-188, ids = asset bodies; the only reader of body_pos_w
+                    const float p1 = f_of(r[IMX_R_P1]), p2 = f_of(r[IMX_R_P2]);
+                    const float s = sum_ids(ids, n, [&](int b) {
+                        const size_t o = ((size_t)ec * P.NB + b) * 3;
+                        const float dz = S.body_pos_w[o + 2] - p0;
+                        const float vx = S.body_lin_vel_w[o], vy = S.body_lin_vel_w[o + 1];
+                        return (dz * dz) * tanhf(p2 * sqrtf(vx * vx + vy * vy));
+                    });
+                    f = expf(-s / p1);
+                } break;
+                case IMX_W_ACTION_SMOOTHNESS_PENALTY:  // :196-198, the norm, not its square
+                    f = sqrtf(sum_range(A, [&](int i) { const float d = Bf.action[ec * A + i] - Bf.prev_action[ec * A + i]; return d * d; }));
+                    break;
+                case IMX_W_AIR_TIME_VARIANCE_PENALTY: {  // :201-212, torch.var: unbiased (divisor n - 1) of the times clipped at 0.5
+                    auto var_clipped = [&](const float* __restrict__ t) {
+                        const float mean = sum_ids(ids, n, [&](int b) { return fminf(t[ec * Bn + b], 0.5f); }) / (float)n;
+                        const float ss = sum_ids(ids, n, [&](int b) { const float d = fminf(t[ec * Bn + b], 0.5f) - mean; return d * d; });
+                        return ss / (float)(n - 1);
+                    };
+                    f = var_clipped(S.last_air_time) + var_clipped(S.last_contact_time);
+                } break;
+                case IMX_W_BASE_MOTION_PENALTY: f = 0.8f * (lbz * lbz) + 0.2f * (fabsf(abx) + fabsf(aby)); break;  // :216-222
+                case IMX_W_BASE_ORIENTATION_PENALTY: f = sqrtf(pgx * pgx + pgy * pgy); break;                     // :225-232
+                case IMX_W_FOOT_SLIP_PENALTY: {  // :235-249, ids = sensor bodies, ids2 = asset bodies, p0 = threshold
+                    const int32_t* ids2 = W + r[IMX_R_IDS2_OFF];
+                    for (int i = 0; i < n; ++i) {
+                        const float c = (max_hist_force(S.net_forces_w_history, ec, H, Bn, ids[i]) > p0) ? 1.0f : 0.0f;
+                        const float* v = S.body_lin_vel_w + ((size_t)ec * P.NB + ids2[i]) * 3;
+                        f += c * sqrtf(v[0] * v[0] + v[1] * v[1]);
+                    }
+                } break;
+                case IMX_W_JOINT_ACCELERATION_PENALTY:  // :252-256 (ids = every joint)
+                    f = sqrtf(sum_ids(ids, n, [&](int j) { const float x = S.joint_acc[ec * J + j]; return x * x; }));
+                    break;
+                case IMX_W_JOINT_POSITION_PENALTY: {  // :259-268, p0 = stand_still_scale, p1 = velocity_threshold
+                    const float d = sqrtf(sum_ids(ids, n, [&](int j) {
+                        const float x = S.joint_pos[ec * J + j] - S.default_joint_pos[ec * J + j];
+                        return x * x;
+                    }));
+                    f = spot_active(cmdx, cmdy, cmdz, lbx, lby, f_of(r[IMX_R_P1])) ? d : p0 * d;
+                } break;
+                case IMX_W_JOINT_TORQUES_PENALTY:  // :271-275
+                    f = sqrtf(sum_ids(ids, n, [&](int j) { const float x = S.applied_torque[ec * J + j]; return x * x; }));
+                    break;
+                case IMX_W_JOINT_VELOCITY_PENALTY:  // :278-282
+                    f = sqrtf(sum_ids(ids, n, [&](int j) { const float x = S.joint_vel[ec * J + j]; return x * x; }));
                     break;
                 default: break;
             }
@@ -1268,6 +1357,20 @@ extern "C" int imx_terminations_rewards_rollout(const imx_plan_t* plan, int64_t 
             case IMX_W_JOINT_POS_TARGET_L2: if (need(st->joint_pos, "joint_pos")) return 1; break;
             case IMX_W_EXTERNAL: if (need(st->ext_reward, "ext_reward")) return 1; break;
             case IMX_W_BODY_LIN_ACC_L2: if (need(st->body_lin_acc_w, "body_lin_acc_w")) return 1; break;
+            case IMX_W_AIR_TIME_REWARD: case IMX_W_GAIT_REWARD:
+                if (need(st->command, "command") || need(st->current_air_time, "current_air_time") ||
+                    need(st->current_contact_time, "current_contact_time")) return 1;
+                break;
+            case IMX_W_BASE_ANGULAR_VELOCITY_REWARD: case IMX_W_BASE_LINEAR_VELOCITY_REWARD: if (need(st->command, "command")) return 1; break;
+            case IMX_W_FOOT_CLEARANCE_REWARD: if (need(st->body_pos_w, "body_pos_w") || need(st->body_lin_vel_w, "body_lin_vel_w")) return 1; break;
+            case IMX_W_AIR_TIME_VARIANCE_PENALTY: if (need(st->last_air_time, "last_air_time") || need(st->last_contact_time, "last_contact_time")) return 1; break;
+            case IMX_W_FOOT_SLIP_PENALTY: if (need(st->net_forces_w_history, "net_forces_w_history") || need(st->body_lin_vel_w, "body_lin_vel_w")) return 1; break;
+            case IMX_W_JOINT_ACCELERATION_PENALTY: if (need(st->joint_acc, "joint_acc")) return 1; break;
+            case IMX_W_JOINT_POSITION_PENALTY:
+                if (need(st->command, "command") || need(st->joint_pos, "joint_pos") || need(st->default_joint_pos, "default_joint_pos")) return 1;
+                break;
+            case IMX_W_JOINT_TORQUES_PENALTY: if (need(st->applied_torque, "applied_torque")) return 1; break;
+            case IMX_W_JOINT_VELOCITY_PENALTY: if (need(st->joint_vel, "joint_vel")) return 1; break;
             default: break;
         }
     }

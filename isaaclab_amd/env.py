@@ -926,7 +926,8 @@ class ManagerBasedRLEnv:
             if self.contact_sensor is not None:
                 d = self.contact_sensor.data
                 kw.update(net_forces_w_history=d.net_forces_w_history.data_ptr(), last_air_time=d.last_air_time.data_ptr(),
-                          current_air_time=d.current_air_time.data_ptr(), current_contact_time=d.current_contact_time.data_ptr())
+                          current_air_time=d.current_air_time.data_ptr(), current_contact_time=d.current_contact_time.data_ptr(),
+                          last_contact_time=d.last_contact_time.data_ptr())
             kw["ext_reward"] = _lib.ptr(self._ext_reward)
             kw["ext_term"] = _lib.ptr(self._ext_term)
             kw["ext_obs"] = _lib.ptr(self._ext_obs)

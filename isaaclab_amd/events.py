@@ -2,7 +2,8 @@
 
 Host-side mirror of the reference's ``EventManager.apply(mode="reset" | "interval")`` for the locomotion tasks' terms
 (reference ``isaaclab/envs/mdp/events.py``: ``reset_root_state_uniform`` :823, ``reset_joints_by_scale`` :987,
-``reset_joints_by_offset`` :1020, ``push_by_setting_velocity`` :795) and of ``terrain_levels_vel``
+``reset_joints_by_offset`` :1020, ``push_by_setting_velocity`` :795; Spot's ``reset_joints_around_default``,
+``isaaclab_tasks/.../velocity/config/spot/mdp/events.py:26-60``) and of ``terrain_levels_vel``
 (``isaaclab_tasks/.../locomotion/velocity/mdp/curriculums.py:26-55``).  The reference calls each term with a compacted
 ``env_ids`` tensor; here every call takes the boolean reset mask the step kernel already produced and rewrites only the
 flagged rows of the caller's "to simulator" buffers -- no ``nonzero``, no ``len(env_ids)`` host sync.  No CPU fallback.
@@ -36,7 +37,7 @@ def _func_name(term: dict) -> str:
 
 
 class ResetEvents:
-    """``reset_root_state_uniform`` + ``reset_joints_by_scale|offset`` (one launch) and ``push_by_setting_velocity``."""
+    """``reset_root_state_uniform`` + ``reset_joints_by_scale|offset|around_default`` (one launch) and ``push_by_setting_velocity``."""
 
     def __init__(self, num_envs: int, num_joints: int, device, pose_range=None, velocity_range=None,
                  joint_position_range=(1.0, 1.0), joint_velocity_range=(0.0, 0.0), joint_mode: str | None = "scale",
@@ -44,7 +45,7 @@ class ResetEvents:
         self.N, self.J, self.device = int(num_envs), int(num_joints), torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("ResetEvents needs a GPU: libimx has no CPU path")
-        self.joint_mode = {"scale": 0, "offset": 1, None: -1}[joint_mode]
+        self.joint_mode = {"scale": 0, "offset": 1, "around_default": 2, None: -1}[joint_mode]
         r = _axis_ranges(pose_range) + _axis_ranges(velocity_range) + [float(x) for x in (*joint_position_range, *joint_velocity_range)]
         self._ranges28 = (ctypes.c_float * 28)(*r)
         self._push12 = (ctypes.c_float * 12)(*_axis_ranges(push_velocity_range)) if push_velocity_range is not None else None
@@ -61,9 +62,9 @@ class ResetEvents:
             fn, params = _func_name(term), term.get("params", {}) or {}
             if fn == "reset_root_state_uniform":
                 kw.update(pose_range=params.get("pose_range"), velocity_range=params.get("velocity_range"))
-            elif fn in ("reset_joints_by_scale", "reset_joints_by_offset"):
+            elif fn in ("reset_joints_by_scale", "reset_joints_by_offset", "reset_joints_around_default"):
                 kw.update(joint_position_range=tuple(params["position_range"]), joint_velocity_range=tuple(params["velocity_range"]),
-                          joint_mode="scale" if fn.endswith("scale") else "offset")
+                          joint_mode=fn[len("reset_joints_by_"):] if fn.startswith("reset_joints_by_") else "around_default")
             elif fn == "push_by_setting_velocity":
                 kw.update(push_velocity_range=params.get("velocity_range"))
         return cls(num_envs, num_joints, device, seed=seed, **kw)
@@ -140,7 +141,7 @@ class TerrainCurriculum:
 
 # ---------------------------------------------------------------------------------------------------- orchestration (imx_reset_orchestrate)
 _EVENT_OPS = {"reset_root_state_uniform": 1, "reset_joints_by_scale": 2, "reset_joints_by_offset": 3, "push_by_setting_velocity": 4,
-              "apply_external_force_torque": 5}
+              "apply_external_force_torque": 5, "reset_joints_around_default": 6}
 _INTERVAL_OK = ("push_by_setting_velocity", "apply_external_force_torque")
 
 

@@ -50,7 +50,10 @@ W_OPS = dict(IS_ALIVE=1, IS_TERMINATED=2, IS_TERMINATED_TERM=3, LIN_VEL_Z_L2=4, 
              ACTION_RATE_L2=16, ACTION_L2=17, UNDESIRED_CONTACTS=18, CONTACT_FORCES=19, TRACK_LIN_VEL_XY_EXP=20,
              TRACK_ANG_VEL_Z_EXP=21, FEET_AIR_TIME=22, FEET_AIR_TIME_POSITIVE_BIPED=23, FEET_SLIDE=24,
              TRACK_LIN_VEL_XY_YAW_FRAME_EXP=25, TRACK_ANG_VEL_Z_WORLD_EXP=26, JOINT_POS_TARGET_L2=27, EXTERNAL=28,
-             BODY_LIN_ACC_L2=29)
+             BODY_LIN_ACC_L2=29, AIR_TIME_REWARD=30, BASE_ANGULAR_VELOCITY_REWARD=31, BASE_LINEAR_VELOCITY_REWARD=32, GAIT_REWARD=33,
+             FOOT_CLEARANCE_REWARD=34, ACTION_SMOOTHNESS_PENALTY=35, AIR_TIME_VARIANCE_PENALTY=36, BASE_MOTION_PENALTY=37,
+             BASE_ORIENTATION_PENALTY=38, FOOT_SLIP_PENALTY=39, JOINT_ACCELERATION_PENALTY=40, JOINT_POSITION_PENALTY=41,
+             JOINT_TORQUES_PENALTY=42, JOINT_VELOCITY_PENALTY=43)
 O_OPS = dict(BASE_POS_Z=1, BASE_LIN_VEL=2, BASE_ANG_VEL=3, PROJECTED_GRAVITY=4, ROOT_POS_W=5, ROOT_QUAT_W=6,
              ROOT_LIN_VEL_W=7, ROOT_ANG_VEL_W=8, JOINT_POS=9, JOINT_POS_REL=10, JOINT_POS_LIMIT_NORMALIZED=11,
              JOINT_VEL=12, JOINT_VEL_REL=13, HEIGHT_SCAN=14, LAST_ACTION=15, GENERATED_COMMANDS=16, EXTERNAL=17)
@@ -59,6 +62,7 @@ A_JOINT_AFFINE = 1
 _MDP = "isaaclab.envs.mdp"
 _VEL = "isaaclab_tasks.manager_based.locomotion.velocity.mdp"
 _CART = "isaaclab_tasks.manager_based.classic.cartpole.mdp"
+_SPOT = "isaaclab_tasks.manager_based.locomotion.velocity.config.spot.mdp.rewards"
 
 
 def f32(x: float) -> float:
@@ -301,6 +305,71 @@ class PlanCompiler:
             return [ids] if isinstance(ids, int) else [int(i) for i in ids]
         return list(range(len(names)))
 
+    # -- Spot's own reward terms (isaaclab_tasks .../velocity/config/spot/mdp/rewards.py) -------------------------------------
+    def _spot_reward(self, name: str, fn: str, p: dict, rec: dict, blob: _Blob) -> None:
+        """Fills ``rec`` for one of the 14 Spot reward functions; ``NotImplementedError`` for any other name in that module (there is
+        no Python fallback for them).  The four joint penalties take the norm over ALL joints whatever ``asset_cfg`` names: the functions
+        never index with ``asset_cfg.joint_ids`` (rewards.py:252-282)."""
+        all_joints = list(range(len(self.joint_names)))
+
+        def ids_of(key, kind, default_entity="robot"):
+            return self.resolve_ids(p.get(key), kind, default_entity)
+
+        if fn == "air_time_reward":  # :31-58 -- `.expand(-1, 4)` fixes the foot count
+            ids = ids_of("sensor_cfg", "body", "contact_forces")
+            if len(ids) != 4:
+                raise ValueError(f"reward term '{name}': air_time_reward expands its command mask to 4 feet; the sensor cfg selects {len(ids)} bodies")
+            rec.update(op=W_OPS["AIR_TIME_REWARD"], ids_off=blob.ints(ids), nids=4, p0=f32(p["mode_time"]), p1=f32(p["velocity_threshold"]))
+        elif fn == "base_angular_velocity_reward":  # :61-68
+            rec.update(op=W_OPS["BASE_ANGULAR_VELOCITY_REWARD"], p0=f32(p["std"]))
+        elif fn == "base_linear_velocity_reward":  # :71-83
+            rec.update(op=W_OPS["BASE_LINEAR_VELOCITY_REWARD"], p0=f32(p["std"]), p1=f32(p.get("ramp_rate", 0.5)),
+                       p2=f32(p.get("ramp_at_vel", 1.0)))
+        elif fn == "GaitReward":  # :86-177: ManagerTermBase; the pairs are resolved once against the contact sensor's bodies
+            pairs = p["synced_feet_pair_names"]
+            if len(pairs) != 2 or len(pairs[0]) != 2 or len(pairs[1]) != 2:
+                raise ValueError("This reward only supports gaits with two pairs of synchronized feet, like trotting.")
+            names = self._entity_names("contact_forces", "body")
+            ids = []
+            for pair in pairs:  # ContactSensor.find_bodies(pair)[0]: target order (preserve_order=False)
+                r_ids, _ = resolve_matching_names(list(pair), names)
+                if len(r_ids) < 2:
+                    raise ValueError(f"reward term '{name}': synced feet pair {list(pair)} resolves to {len(r_ids)} body")
+                ids += [int(r_ids[0]), int(r_ids[1])]
+            rec.update(op=W_OPS["GAIT_REWARD"], ids_off=blob.ints(ids), nids=4, p0=f32(p["std"]), p1=f32(float(p["max_err"]) ** 2),
+                       p2=f32(p["velocity_threshold"]))
+        elif fn == "foot_clearance_reward":  # :180-188
+            ids = ids_of("asset_cfg", "body")
+            rec.update(op=W_OPS["FOOT_CLEARANCE_REWARD"], ids_off=blob.ints(ids), nids=len(ids), p0=f32(p["target_height"]), p1=f32(p["std"]),
+                       p2=f32(p["tanh_mult"]))
+        elif fn == "action_smoothness_penalty":  # :196-198
+            rec.update(op=W_OPS["ACTION_SMOOTHNESS_PENALTY"])
+        elif fn == "air_time_variance_penalty":  # :201-212
+            ids = ids_of("sensor_cfg", "body", "contact_forces")
+            rec.update(op=W_OPS["AIR_TIME_VARIANCE_PENALTY"], ids_off=blob.ints(ids), nids=len(ids))
+        elif fn == "base_motion_penalty":  # :216-222
+            rec.update(op=W_OPS["BASE_MOTION_PENALTY"])
+        elif fn == "base_orientation_penalty":  # :225-232
+            rec.update(op=W_OPS["BASE_ORIENTATION_PENALTY"])
+        elif fn == "foot_slip_penalty":  # :235-249: sensor ids and asset ids are separate lists
+            ids = ids_of("sensor_cfg", "body", "contact_forces")
+            ids2 = ids_of("asset_cfg", "body")
+            if len(ids) != len(ids2):
+                raise ValueError(f"reward term '{name}': foot_slip_penalty pairs {len(ids)} sensor bodies with {len(ids2)} asset bodies")
+            rec.update(op=W_OPS["FOOT_SLIP_PENALTY"], ids_off=blob.ints(ids), nids=len(ids), ids2_off=blob.ints(ids2), nids2=len(ids2),
+                       p0=f32(p["threshold"]))
+        elif fn in ("joint_acceleration_penalty", "joint_torques_penalty", "joint_velocity_penalty"):  # :252-256, :271-282
+            self.resolve_ids(p.get("asset_cfg"), "joint")  # the cfg must still resolve (SceneEntityCfg.resolve) though it selects nothing
+            opn = {"joint_acceleration_penalty": "JOINT_ACCELERATION_PENALTY", "joint_torques_penalty": "JOINT_TORQUES_PENALTY",
+                   "joint_velocity_penalty": "JOINT_VELOCITY_PENALTY"}[fn]
+            rec.update(op=W_OPS[opn], ids_off=blob.ints(all_joints), nids=len(all_joints))
+        elif fn == "joint_position_penalty":  # :259-268
+            self.resolve_ids(p.get("asset_cfg"), "joint")
+            rec.update(op=W_OPS["JOINT_POSITION_PENALTY"], ids_off=blob.ints(all_joints), nids=len(all_joints),
+                       p0=f32(p["stand_still_scale"]), p1=f32(p["velocity_threshold"]))
+        else:
+            raise NotImplementedError(f"reward term '{name}': {_SPOT}:{fn} has no fused op")
+
     # -- compile ------------------------------------------------------------------------------------------------
     def compile(self) -> Plan:
         cfg, robot = self.cfg, self.robot
@@ -520,6 +589,8 @@ class PlanCompiler:
             elif fn == f"{_MDP}.rewards:body_lin_acc_l2":
                 ids = self.resolve_ids(p.get("asset_cfg"), "body")
                 rec.update(op=W_OPS["BODY_LIN_ACC_L2"], ids_off=blob.ints(ids), nids=len(ids))
+            elif _short(fn)[0] == _SPOT:
+                self._spot_reward(name, _short(fn)[1], p, rec, blob)
             else:
                 known = False
                 rec.update(op=W_OPS["EXTERNAL"], aux0=n_ext_rew)

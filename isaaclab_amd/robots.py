@@ -3,9 +3,9 @@
 The reference obtains joint/body names and default joint positions from PhysX after loading the robot USD
 (``Articulation._initialize_impl``); neither PhysX nor the USD files exist here, so the *names* ship as data.
 Defaults follow the asset cfgs (reference ``source/isaaclab_assets/isaaclab_assets/robots/anymal.py:112-121``,
-``unitree.py:290-307`` (G1), ``cartpole.py``).  The G1 joint order is a synthetic breadth-first order of the 37
-joint names the G1 cfg's regexes refer to (the true PhysX order is not recoverable offline); term semantics do
-not depend on it because every index list is resolved by name through :func:`resolve_matching_names`.
+``unitree.py:290-307`` (G1), ``spot.py:151-160``, ``cartpole.py``).  The G1 and Spot joint / body orders are synthetic
+breadth-first orders of the names the task cfgs' regexes refer to (the true PhysX order is not recoverable offline); term
+semantics do not depend on them because every index list is resolved by name through :func:`resolve_matching_names`.
 """
 
 from __future__ import annotations
@@ -148,4 +148,15 @@ CARTPOLE = RobotSpec(
     joint_pos_limits=(-4.0, 4.0),
 )
 
-ROBOTS = {r.name: r for r in (ANYMAL_C, G1, CARTPOLE)}
+_SPOT_LEGS = ("fl", "fr", "hl", "hr")
+
+SPOT = RobotSpec(
+    name="spot",
+    # synthetic breadth-first order: hip_x, hip_y, knee of the four legs; the body below the base, one link level at a time
+    joint_names=[f"{leg}_{j}" for j in ("hx", "hy", "kn") for leg in _SPOT_LEGS],
+    body_names=["body"] + [f"{leg}_{b}" for b in ("hip", "uleg", "lleg", "foot") for leg in _SPOT_LEGS],
+    default_joint_pos={"[fh]l_hx": 0.1, "[fh]r_hx": -0.1, "f[rl]_hy": 0.9, "h[rl]_hy": 1.1, ".*_kn": -1.5},
+    default_root_height=0.5,
+)
+
+ROBOTS = {r.name: r for r in (ANYMAL_C, G1, CARTPOLE, SPOT)}

@@ -22,9 +22,9 @@ DYNAMIC = (
     "body_lin_vel_w", "command", "net_forces_w_history",
     "last_air_time", "current_air_time", "current_contact_time", "last_contact_time",
 )
-# further per-step tensors only a few optional terms read (body_lin_acc_l2, command_resample): drawn from their own generator so that
-# the tensors above are unchanged by their presence; recorded fixtures carry them only when their cfg needs them
-EXTRA = ("body_lin_acc_w", "command_time_left", "command_counter")
+# further per-step tensors only a few optional terms read (body_lin_acc_l2, command_resample, foot_clearance_reward): drawn from their
+# own generators so that the tensors above are unchanged by their presence; recorded fixtures carry them only when their cfg needs them
+EXTRA = ("body_lin_acc_w", "command_time_left", "command_counter", "body_pos_w")
 # tensors fixed for the lifetime of the scene
 STATIC = ("default_joint_pos", "default_joint_vel", "soft_joint_pos_limits", "soft_joint_vel_limits", "env_origins")
 
@@ -42,9 +42,9 @@ def _quat_from_euler(roll, pitch, yaw):
 def contact_body_groups(robot: RobotSpec) -> dict[str, list[int]]:
     """Which bodies play the 'feet' / 'thigh' / 'base' roles for the synthetic contact distribution."""
     names = robot.body_names
-    feet = [i for i, n in enumerate(names) if n.endswith("FOOT") or n.endswith("_ankle_roll_link")]
-    thigh = [i for i, n in enumerate(names) if n.endswith("THIGH") or n.endswith("_knee_link")]
-    base = [i for i, n in enumerate(names) if n in ("base", "torso_link")]
+    feet = [i for i, n in enumerate(names) if n.endswith("FOOT") or n.endswith("_ankle_roll_link") or n.endswith("_foot")]
+    thigh = [i for i, n in enumerate(names) if n.endswith("THIGH") or n.endswith("_knee_link") or n.endswith("leg")]
+    base = [i for i, n in enumerate(names) if n in ("base", "torso_link", "body")]
     return {"feet": feet, "thigh": thigh, "base": base}
 
 
@@ -143,6 +143,15 @@ def generate_extras(robot: RobotSpec, num_envs: int, gen: torch.Generator) -> di
             "command_counter": torch.randint(0, 3, (N,), generator=gen, dtype=torch.int64)}
 
 
+def generate_body_pos(robot: RobotSpec, num_envs: int, gen: torch.Generator) -> torch.Tensor:
+    """``ArticulationData.body_pos_w`` (N, B, 3): x, y ~ N(0, 0.5) around the world origin, heights ~ U(0, 0.3) m (feet swinging
+    around a 0.1 m clearance target and links above them; only the heights enter a term)."""
+    N, B = num_envs, robot.num_bodies
+    xy = torch.randn(N, B, 2, generator=gen) * 0.5
+    z = torch.rand(N, B, 1, generator=gen) * 0.3
+    return torch.cat([xy, z], dim=-1).contiguous()
+
+
 class StateFeed:
     """``S`` snapshots of the post-physics state held on ``device``; ``advance()`` moves to the next one.
 
@@ -162,8 +171,10 @@ class StateFeed:
         snaps = [generate_snapshot(robot, num_envs, gen, history, extent_xy=extent_xy) for _ in range(num_snapshots)]
         self._stack: dict[str, torch.Tensor] = {}
         gen_x = torch.Generator().manual_seed(seed + 0x5EED)
+        gen_p = torch.Generator().manual_seed(seed + 0xB0D7)
         for sn in snaps:
             sn.update(generate_extras(robot, num_envs, gen_x))
+            sn["body_pos_w"] = generate_body_pos(robot, num_envs, gen_p)
         for name in DYNAMIC + EXTRA:
             self._stack[name] = torch.stack([s[name] for s in snaps], dim=0).to(self.device).contiguous()
         # every snapshot keeps the same origins/defaults; root xy of later snapshots re-uses snapshot-0 origins

@@ -135,6 +135,7 @@ class FusedInference:
         import ctypes
 
         self.ok = 1 <= len(nets) <= 2
+        self._padded, self._wpk = [], None  # (a stack that does not fit returns below: refresh() must still be callable)
         dims, ws, bs, alphas, nl = [], [], [], [], []
         for layers in nets:
             acts = [a for _, a in layers[:-1]]
@@ -153,7 +154,6 @@ class FusedInference:
         # Layers whose in-features are not a multiple of 32 (235 observations) get a zero-padded copy of their weights with a
         # row pitch that is (the kernel issues unconditional 16-byte loads over whole 32-wide reduction groups);
         # ``refresh()`` re-copies them after the parameters changed (once per rollout).
-        self._padded = []
         pitch, wp = [], []
         for w in ws:
             k = w.shape[1]
@@ -188,7 +188,10 @@ class FusedInference:
 
     @torch.no_grad()
     def refresh(self):
-        """Re-copy the padded weight buffers from the live parameters (capturable: plain device copies)."""
+        """Re-copy the padded weight buffers from the live parameters (capturable: plain device copies); nothing to do when the
+        stacks did not fit (``ok`` False: the caller runs the library path)."""
+        if not self.ok:
+            return
         for buf, w in self._padded:
             buf[:, :w.shape[1]].copy_(w)
         if self._wpk is not None:  # all layers in one launch
@@ -405,10 +408,29 @@ def _mlp_backward_layers(L, layers, saved, dout, M, scratch, deferred, stream, h
             elif prev_act is None:
                 d = dx
             else:
-                z, _h = saved[i]
-                with torch.enable_grad():
-                    zz = z.detach().requires_grad_(True)
-                    (d,) = torch.autograd.grad(prev_act(zz), zz, dx)
+                z, h = saved[i]
+                d = _act_backward(prev_act, dx, z, h)
+
+
+def _act_backward(act, dh, z, h):
+    """Gradient through a hidden activation other than ELU: the aten backward op autograd itself would call (bit-identical), written
+    out because the update also runs under inference mode (hipGraph capture), where autograd records nothing."""
+    if isinstance(act, nn.Identity):
+        return dh
+    if isinstance(act, nn.Tanh):
+        return torch.ops.aten.tanh_backward(dh, h)
+    if isinstance(act, nn.Sigmoid):
+        return torch.ops.aten.sigmoid_backward(dh, h)
+    if isinstance(act, nn.ReLU):
+        return torch.ops.aten.threshold_backward(dh, h, 0)
+    if isinstance(act, nn.LeakyReLU):
+        return torch.ops.aten.leaky_relu_backward(dh, z, act.negative_slope, False)
+    if isinstance(act, nn.SELU):  # selu(x) = elu(x, alpha, scale)
+        return torch.ops.aten.elu_backward(dh, 1.6732632423543772848170429916717, 1.0507009873554804934193349852946, 1.0, False, z)
+    with torch.inference_mode(False), torch.enable_grad():  # any other module: autograd on copies (not capturable)
+        zz = z.clone().requires_grad_(True)
+        (d,) = torch.autograd.grad(act(zz), zz, dh.clone())
+    return d
 
 
 class PPO:

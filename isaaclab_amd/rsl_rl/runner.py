@@ -276,8 +276,9 @@ class OnPolicyRunner:
                                      self._ep_stats.data_ptr(), env._log_out.data_ptr(), self._log_accum.data_ptr(),
                                      self._log_accum.numel(), stream))
             obs = obs_dict["policy"]
-            if priv is not None:
-                cobs = obs_dict[priv]
+            # the critic reads this step's observations (its own group, or the policy's: the first step's input may be a copy -- the
+            # captured graph's -- and is not the buffer env.step writes)
+            cobs = obs_dict[priv] if priv is not None else obs
         self._privileged_obs = cobs if priv is not None else obs
         st.step = self.num_steps_per_env
         if self._graph_capturing:

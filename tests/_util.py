@@ -130,3 +130,200 @@ class OrchGolden:
         out["command"] = self.t("draws/command")[slot]
         out["rand_levels"] = self.t("draws/rand_levels")[slot]
         return out
+
+
+# ---------------------------------------------------------------------------------------------------- PPO update / inference parity
+# Tolerance rule of the gradient checks (tests/test_policy_shapes_gpu.py, tools/fuzz_kernels.py): per parameter tensor, the kernel's error
+# against a float64 autograd reference is at most max(1e-5 * max|g_ref|, 2 * e_torch), where e_torch is the error of the same computation in
+# fp32 torch autograd against the same reference.  fp32 summation over 24 576 rows is not 1e-5 of every element; this lets the kernels be as
+# inexact as torch's own fp32 path and no more -- a dropped ragged tile, a wrong pitch or an unzeroed pad column lands orders above it.
+# One addition: an element may also be off by 1e-6 of the sum of the absolute values of its terms (S = |dZ|^T |X| for a weight,
+# sum |dZ| for a bias; 16 fp32 roundings).  Needed where the sum cancels: the value head's bias gradient is a mean of 2 (v - R) / M
+# over 24 576 rows, ~1e-4 from terms that add up to ~0.5 in magnitude, and there torch's pairwise reduction happens to be 5x closer
+# than any blocked order (seen: 2.3e-9 against 5e-10, where fp32's own scale is 3e-8).
+GRAD_REL_FLOOR, GRAD_TORCH_FACTOR, GRAD_SUM_FLOOR = 1e-5, 2.0, 1e-6
+
+
+def fill_storage(alg, seed: int):
+    """Seeded transitions in ``alg.storage`` (the pattern of test_whole_update_matches_torch_reference): observations N(0, 1), the stored
+    means / values from the policy itself (the first minibatch of an update sees ratio 1), actions drawn around them, returns and
+    advantages random."""
+    st, pol = alg.storage, alg.policy
+    T, N, A = st.actions.shape
+    g = torch.Generator().manual_seed(seed)
+    st.observations.copy_(torch.randn(st.observations.shape, generator=g))
+    if st.privileged_observations is not None:
+        st.privileged_observations.copy_(torch.randn(st.privileged_observations.shape, generator=g))
+    cobs = st.privileged_observations if st.privileged_observations is not None else st.observations
+    with torch.no_grad():
+        mu = pol.actor(st.observations.flatten(0, 1)).view(T, N, A)
+        val = pol.critic(cobs.flatten(0, 1)).view(T, N, 1)
+        sigma = pol._std(mu).contiguous()
+        act = mu + sigma * torch.randn(T, N, A, generator=g).to(mu.device)
+        st.mu.copy_(mu); st.sigma.copy_(sigma); st.actions.copy_(act); st.values.copy_(val)
+        st.actions_log_prob.copy_(torch.distributions.Normal(mu, sigma).log_prob(act).sum(-1, keepdim=True))
+        st.returns.copy_(val + 0.3 * torch.randn(T, N, 1, generator=g).to(mu.device))
+        st.advantages.copy_(torch.randn(T, N, 1, generator=g))
+    st.step = T
+
+
+def _autograd_minibatch(alg, batch, dtype):
+    """Gradients of every policy parameter, the five loss scalars of one minibatch and, per Linear parameter, the sum of the absolute
+    values of the terms of each gradient element (name -> tensor): torch autograd through a ``dtype`` copy."""
+    import copy
+
+    import torch.nn as nn
+
+    from oracle.rsl_rl_oracle import ppo_losses
+
+    m = copy.deepcopy(alg.policy).to(dtype)
+    obs, cobs, act, v_old, adv, ret, logp_old, mu_old, sg_old = (x.to(dtype) for x in batch)
+    seen = []
+    hooks = [mod.register_forward_hook(lambda mod, inp, out, name=name: seen.append((name, inp[0], out)))
+             for name, mod in m.named_modules() if isinstance(mod, nn.Linear)]
+    with torch.enable_grad():
+        mu = m.actor(obs)
+        s, v, e, kl = ppo_losses(mu, m._std(mu), act, logp_old, mu_old, sg_old, adv, ret, m.critic(cobs), v_old, alg.clip_param,
+                                 alg.use_clipped_value_loss)
+        loss = s + alg.value_loss_coef * v - alg.entropy_coef * e
+        params = [p for p in m.parameters() if p.requires_grad]
+        grads = torch.autograd.grad(loss, params + [out for _, _, out in seen])
+    for h in hooks:
+        h.remove()
+    sums = {}
+    for (name, x, _), dz in zip(seen, grads[len(params):]):
+        sums[name + ".weight"] = dz.abs().t() @ x.detach().abs()
+        sums[name + ".bias"] = dz.abs().sum(0)
+    return grads[:len(params)], torch.stack([s, v, e, kl, loss]).detach(), sums
+
+
+def check_minibatch_gradients(alg, batch, what=""):
+    """``PPO.minibatch_step`` on ``batch`` against float64 autograd under the tolerance rule above; the gradient bucket is poisoned
+    with NaN first, so a gradient element the kernels never write fails too."""
+    ref64, loss64, sums = _autograd_minibatch(alg, batch, torch.float64)
+    ref32 = _autograd_minibatch(alg, batch, torch.float32)[0]
+    alg.bucket.grad.fill_(float("nan"))
+    with torch.no_grad():
+        out8 = alg.minibatch_step(*batch).clone()
+    torch.cuda.synchronize()
+    assert_close(out8[:5], loss64, FLOAT_TOL, f"{what}: loss scalars (surrogate, value, entropy, KL, total)")
+    params = [(n, p) for n, p in alg.policy.named_parameters() if p.requires_grad]
+    for (name, p), r64, r32 in zip(params, ref64, ref32):
+        got = p.grad.double()
+        assert bool(torch.isfinite(got).all()), f"{what}: {name}: gradient not written (NaN / inf)"
+        err = (got - r64).abs()
+        e_t = float((r32.double() - r64).abs().max())
+        bound = max(GRAD_REL_FLOOR * float(r64.abs().max()), GRAD_TORCH_FACTOR * e_t)
+        if name in sums:
+            bound = torch.clamp(GRAD_SUM_FLOOR * sums[name], min=bound)
+        over = err > bound
+        assert not bool(over.any()), (f"{what}: {name} {tuple(p.shape)}: {int(over.sum())} elements over the bound, max err {float(err.max()):.3e} "
+                                      f"vs fp64 (max |g| {float(r64.abs().max()):.3e}, fp32 torch err {e_t:.3e})")
+
+
+def reference_update(ref_pol, data, perm, nmb: int, nep: int, kw: dict, std=None):
+    """One PPO update in torch: autograd + ``clip_grad_norm_`` + ``torch.optim.Adam`` + the rsl_rl adaptive-LR rule (restated in
+    oracle/rsl_rl_oracle.py), on ``data`` = the flattened storage (obs, actions, values, advantages, returns, log-probs, mu, sigma,
+    critic obs) walked in the order of ``perm``.  Returns the final learning rate."""
+    from oracle.rsl_rl_oracle import adaptive_lr, ppo_losses
+
+    std = std or (lambda: ref_pol.std)
+    Mb = perm.numel() // nmb
+    opt = torch.optim.Adam(ref_pol.parameters(), lr=kw["learning_rate"])
+    lr = kw["learning_rate"]
+    for _ in range(nep):
+        for i in range(nmb):
+            idx = perm[i * Mb:(i + 1) * Mb]
+            obs, a_, v_old, adv, ret, logp_old, mu_old, sg_old, cobs = (x[idx] for x in data)
+            if kw.get("normalize_advantage_per_mini_batch"):
+                adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+            mu_b = ref_pol.actor(obs)
+            s_, v_, e_, kl = ppo_losses(mu_b, std().expand_as(mu_b), a_, logp_old, mu_old, sg_old, adv, ret, ref_pol.critic(cobs), v_old,
+                                        kw["clip_param"], kw["use_clipped_value_loss"])
+            if kw["schedule"] == "adaptive":
+                lr = adaptive_lr(lr, float(kl.detach()), kw["desired_kl"])
+            for gr in opt.param_groups:
+                gr["lr"] = lr
+            loss = s_ + kw["value_loss_coef"] * v_ - kw["entropy_coef"] * e_
+            opt.zero_grad()
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(ref_pol.parameters(), kw["max_grad_norm"])
+            opt.step()
+    return lr
+
+
+def update_params_agree(pol, ref_pol, steps: int):
+    """The outlier-tolerant criterion of tools/fuzz_kernels.py::case_update for the parameters after ``steps`` Adam steps: every element
+    within 1e-4 * max(1, steps / 4) except a handful (<= 2 + 1e-4 of the tensor) that may be off by up to the learning-rate steps taken
+    (Adam moves a parameter by ~lr whatever |g| is on its first steps, so the rounding of a ~1e-8 gradient element flips a visible part of
+    lr).  Returns (ok, worst in-tolerance error, message)."""
+    tol = 1e-4 * max(1.0, steps / 4)
+    err, bad = 0.0, []
+    for (name, p), q in zip(pol.named_parameters(), ref_pol.parameters()):
+        d = (p.detach() - q.detach()).abs()
+        over = d > tol
+        n_over = int(over.sum())
+        if n_over > 2 + int(1e-4 * d.numel()) or float(d.max()) > 2.5e-3 * steps:
+            bad.append(f"{name}: {n_over} of {d.numel()} over {tol:.0e}, max {float(d.max()):.2e}")
+        err = max(err, float(d[~over].max()) if n_over < d.numel() else float(d.max()))
+    return not bad and err <= tol, err, "; ".join(bad)
+
+
+def check_fused_inference(pol, M: int, seed: int, what=""):
+    """``FusedInference`` (both networks, one launch) against the float64 modules on a row-pitched input whose pad columns hold NaN;
+    the packed weight images and the row layout must agree bit for bit."""
+    from isaaclab_amd.rsl_rl.ppo import FusedInference, _mlp_layers
+
+    D, A = pol.actor[0].in_features, pol.actor[-1].out_features
+    g = torch.Generator().manual_seed(seed)
+    pitch = (D + 3) // 4 * 4 + 4
+    xb = torch.full((M, pitch), float("nan"))
+    xb[:, :D] = torch.randn(M, D, generator=g)
+    x = xb.cuda()[:, :D]
+    inf = FusedInference(_mlp_layers(pol.actor), _mlp_layers(pol.critic))
+    assert inf.ok, what
+    mu, val = torch.full((M, A), float("nan"), device="cuda"), torch.full((M, 1), float("nan"), device="cuda")
+    inf(x, mu, val)
+    packed, inf._wpk = inf._wpk, None
+    mu_r, val_r = torch.full_like(mu, float("nan")), torch.full_like(val, float("nan"))
+    inf(x, mu_r, val_r)
+    inf._wpk = packed
+    torch.cuda.synchronize()
+    assert packed is not None and torch.equal(mu, mu_r) and torch.equal(val, val_r), f"{what}: packed and row-layout weights differ"
+    import copy
+
+    p64 = copy.deepcopy(pol).double()
+    with torch.no_grad():
+        assert_close(mu, p64.actor(x.double()), FLOAT_TOL, f"{what}: mu")
+        assert_close(val, p64.critic(x.double()), FLOAT_TOL, f"{what}: value")
+
+
+def check_infer_act(pol, M: int, seed: int, step: int, what=""):
+    """``imx_mlp_infer_act`` (PPO.act in the actor head's epilogue) against ``imx_mlp_infer`` + ``imx_policy_act``: bit-identical actions,
+    log-probs, means, sigmas, stored observations and values (tools/fuzz_kernels.py::case_infer_act)."""
+    from isaaclab_amd import _lib
+    from isaaclab_amd.rsl_rl.ppo import FusedInference, _mlp_layers
+
+    L = _lib.lib()
+    s = torch.cuda.current_stream().cuda_stream
+    D, A = pol.actor[0].in_features, pol.actor[-1].out_features
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(M, D, generator=g).cuda()
+    inf = FusedInference(_mlp_layers(pol.actor), _mlp_layers(pol.critic))
+    assert inf.ok, what
+    stp = torch.tensor([step], dtype=torch.int32, device="cuda")
+    mu, val = torch.empty(M, A, device="cuda"), torch.empty(M, 1, device="cuda")
+    inf(x, mu, val)
+    nan = lambda *sh: torch.full(sh, float("nan"), device="cuda")  # noqa: E731
+    a0, m0, s0, lp0, v0, o0 = nan(M, A), nan(M, A), nan(M, A), nan(M), nan(M, 1), nan(M, D)
+    _lib.check(L.imx_policy_act(M, A, D, mu.data_ptr(), pol.std.data_ptr(), val.data_ptr(), x.data_ptr(), seed, stp.data_ptr(), a0.data_ptr(),
+                                lp0.data_ptr(), m0.data_ptr(), s0.data_ptr(), v0.data_ptr(), o0.data_ptr(), None, s))
+    a1, m1, s1, lp1, v1, o1 = nan(M, A), nan(M, A), nan(M, A), nan(M), nan(M, 1), nan(M, D)
+    act = _lib.ImxPolicyAct(std_d=pol.std.data_ptr(), seed=seed, step_counter_d=stp.data_ptr(), actions_out_d=a1.data_ptr(), logp_out_d=lp1.data_ptr(),
+                            mu_out_d=m1.data_ptr(), sigma_out_d=s1.data_ptr(), obs_out_d=o1.data_ptr(), plan=None, state=None, buf=None,
+                            pre_clip=float("inf"))
+    inf(x, None, v1, act=act)
+    torch.cuda.synchronize()
+    for k, (p, q) in dict(actions=(a0, a1), mu=(m0, m1), sigma=(s0, s1), log_prob=(lp0, lp1), value=(v0, v1), obs=(o0, o1)).items():
+        assert torch.equal(p, q), f"{what}: {k} of imx_mlp_infer_act differs from imx_mlp_infer + imx_policy_act"
+    assert bool(torch.isfinite(a1).all()), what

@@ -202,3 +202,45 @@ def test_only_observation_minibatch_buffers_carry_a_row_pitch():
                     assert buf.stride(0) % 4 == 0 and buf.stride(0) - buf.shape[1] < 4, (D, Dc, A, k, buf.stride())
                 else:
                     assert buf.is_contiguous(), (D, Dc, A, k, tuple(buf.shape), buf.stride())
+
+
+@pytest.mark.parametrize("activation,hidden", [("tanh", [128, 128]), ("relu", [400, 200, 100]), ("elu", [512, 512, 256, 128]),
+                                               ("elu", [1024, 512, 256, 128])])
+def test_fused_inference_of_a_stack_that_does_not_fit_is_off_and_refresh_is_a_no_op(activation, hidden):
+    """FusedInference takes ELU stacks of at most 4 Linear layers and 512 features.  Anything else reports ok = False, and the
+    runner still calls refresh() at the start of every rollout after the first: that must do nothing (it raised AttributeError)."""
+    import torch
+
+    from isaaclab_amd.rsl_rl.actor_critic import ActorCritic
+    from isaaclab_amd.rsl_rl.ppo import FusedInference, _mlp_layers
+
+    pol = ActorCritic(87, 87, 21, actor_hidden_dims=hidden, critic_hidden_dims=hidden, activation=activation)
+    before = [p.detach().clone() for p in pol.parameters()]
+    for nets in ((pol.actor, pol.critic), (pol.critic,)):
+        inf = FusedInference(*[_mlp_layers(n) for n in nets])
+        assert not inf.ok
+        inf.refresh()
+        inf.refresh()
+    assert all(torch.equal(p, q) for p, q in zip(pol.parameters(), before))
+
+
+@pytest.mark.parametrize("activation", ["elu", "selu", "relu", "lrelu", "tanh", "sigmoid", "crelu", "identity"])
+def test_activation_backward_of_the_update_equals_autograd_under_inference_mode(activation):
+    """The explicit backward of PPO.update takes every hidden activation but ELU through ppo._act_backward; the update is captured
+    into a hipGraph under inference mode, where autograd records nothing.  Its result must equal autograd's, bit for bit."""
+    import torch
+
+    from isaaclab_amd.rsl_rl.actor_critic import _ACT
+    from isaaclab_amd.rsl_rl.ppo import _act_backward
+
+    act = _ACT[activation]()
+    g = torch.Generator().manual_seed(1)
+    z = 3.0 * torch.randn(257, 33, generator=g)
+    z[0, :4] = torch.tensor([0.0, -0.0, 1e-30, -1e-30])
+    dh = torch.randn(257, 33, generator=g)
+    zz = z.clone().requires_grad_(True)
+    (ref,) = torch.autograd.grad(act(zz), zz, dh)
+    with torch.inference_mode():
+        zi, di = z.clone(), dh.clone()
+        got = _act_backward(act, di, zi, act(zi))
+    assert torch.equal(got, ref)

@@ -1,6 +1,6 @@
 """Random-shape sweep of the stand-alone kernels against torch (fp64) / the rsl_rl restatement: GAE, imx_mlp_fwd_elu, imx_mlp_infer (packed
 and row layouts), imx_mlp_dw[_elu], the LSTM actuator, a whole PPO.update with random network shapes.  Test infrastructure, run on the GPU box:
-    python tools/fuzz_kernels.py [cases per kernel] [seed]"""
+    python tools/fuzz_kernels.py [cases per kernel] [seed] [kind ...]"""
 import ctypes
 import os
 import sys
@@ -366,12 +366,102 @@ def case_update_graph(rng):
     return same and bool(torch.isfinite(p1).all()), f"T={T} N={N} D={D} A={A} hidden={hidden} mb={nmb} ep={nep} identical={same}"
 
 
+ODD_WIDTHS = [32, 33, 64, 100, 128, 200, 256, 400, 500]  # non-multiples of 32 take every ragged path (padded / packed images, K % 32 != 0 heads)
+
+
+def case_update_shapes(rng):
+    """PPO.minibatch_step on minibatch 0 of a seeded storage (the storage's own permutation / gather) against float64 autograd under the
+    tolerance rule of tests/_util.py, then an update of ONE minibatch and epoch (gather of every row, loss, backward, clip, Adam) against
+    torch autograd + Adam: hidden widths that are not multiples of 32, any ActorCritic activation, different actor / critic stacks, T*N
+    up to 24 576 x 4.  One Adam step because later steps amplify rounding: Adam moves an element by ~lr whatever |g| is, and once the
+    parameters differ by rounding a ReLU kink or a clip boundary crossed by one path and not the other flips such steps (seen at 4 steps
+    with relu / identity nets: whole rows off by 1e-3 while every minibatch gradient passes the fp64 check).  The multi-step update is
+    case_update's and tests/test_policy_shapes_gpu.py's."""
+    import copy
+
+    import isaaclab_amd.rsl_rl.ppo as ppo_mod
+    from _util import check_minibatch_gradients, fill_storage, reference_update, update_params_agree
+    from isaaclab_amd.rsl_rl.actor_critic import _ACT, ActorCritic
+    from isaaclab_amd.rsl_rl.ppo import PPO
+
+    T, N = int(rng.choice([1, 4, 16, 24])), int(rng.choice([1, 33, 1000, 4096]))
+    D, A = int(rng.integers(1, 320)), int(rng.integers(1, 41))
+    Dc = int(rng.choice([0, 0, int(rng.integers(1, 320))]))
+    act_name = str(rng.choice(sorted(_ACT)))
+    ah = [int(rng.choice(ODD_WIDTHS)) for _ in range(int(rng.integers(1, 4)))]
+    ch = ah if rng.integers(0, 2) else [int(rng.choice(ODD_WIDTHS)) for _ in range(int(rng.integers(1, 4)))]
+    nmb = int(rng.choice([1, 2, 4]))
+    while (T * N) % nmb:
+        nmb -= 1
+    ppo_mod.FUSED_HEAD = str(rng.choice(["0", "1"]))
+    two_streams = bool(rng.choice([True, True, False]))
+    torch.manual_seed(int(rng.integers(0, 1 << 30)))
+    pol = ActorCritic(D, Dc or D, A, actor_hidden_dims=ah, critic_hidden_dims=ch, activation=act_name, init_noise_std=float(rng.choice([0.5, 1.0])))
+    ref_pol = copy.deepcopy(pol).cuda()
+    kw = dict(num_learning_epochs=1, num_mini_batches=nmb, schedule="adaptive", desired_kl=0.01, learning_rate=1e-3, entropy_coef=0.005,
+              max_grad_norm=1.0, clip_param=0.2, value_loss_coef=1.0, use_clipped_value_loss=True, two_streams=two_streams)
+    alg = PPO(pol, device="cuda:0", **kw)
+    alg.init_storage("rl", N, T, (D,), (Dc,), (A,))
+    fill_storage(alg, int(rng.integers(0, 1 << 30)))
+    desc = f"T={T} N={N} D={D} Dc={Dc} A={A} actor={ah} critic={ch} act={act_name} mb={nmb} fused_head={ppo_mod.FUSED_HEAD} two_streams={two_streams}"
+    seed = int(rng.integers(0, 1 << 30))
+    stg = alg.storage
+    cobs_all = stg.privileged_observations if Dc else stg.observations
+    data = [x.flatten(0, 1).clone() for x in (stg.observations, stg.actions, stg.values, stg.advantages, stg.returns, stg.actions_log_prob,
+                                              stg.mu, stg.sigma, cobs_all)]
+    try:
+        torch.manual_seed(seed)
+        stg.draw_permutation(nmb)
+        check_minibatch_gradients(alg, stg.gather_minibatch(0, nmb), desc)
+    except AssertionError as e:
+        return False, str(e)
+    alg.num_mini_batches = 1
+    torch.manual_seed(seed)
+    alg.update()
+    torch.cuda.synchronize()
+    torch.manual_seed(seed)
+    lr = reference_update(ref_pol, data, torch.randperm(T * N, device="cuda:0"), 1, 1, kw)
+    ok, err, msg = update_params_agree(pol, ref_pol, 1)
+    lr_ok = abs(alg.learning_rate - lr) <= 1e-9 * max(1.0, lr)
+    del alg, stg
+    import gc
+
+    gc.collect()
+    return ok and lr_ok, f"{desc} lr_ok={lr_ok} err={err:.1e} {msg}"
+
+
+def case_infer_act_shapes(rng):
+    """imx_mlp_infer against float64 on a NaN-padded row pitch, packed == row-layout weights, imx_mlp_infer_act == imx_mlp_infer +
+    imx_policy_act, with hidden widths that are not multiples of 32 (tests/_util.py helpers)."""
+    from _util import check_fused_inference, check_infer_act
+    from isaaclab_amd.rsl_rl.actor_critic import ActorCritic
+
+    M, D, A = int(rng.choice([1, 33, 100, 2048, 4096, 4113])), int(rng.integers(1, 400)), int(rng.integers(1, 41))
+    ah = [int(rng.choice(ODD_WIDTHS)) for _ in range(int(rng.integers(1, 4)))]
+    ch = ah if rng.integers(0, 2) else [int(rng.choice(ODD_WIDTHS)) for _ in range(int(rng.integers(1, 4)))]
+    torch.manual_seed(int(rng.integers(0, 1 << 30)))
+    pol = ActorCritic(D, D, A, actor_hidden_dims=ah, critic_hidden_dims=ch, init_noise_std=float(rng.choice([0.3, 1.0]))).cuda()
+    desc = f"M={M} D={D} A={A} actor={ah} critic={ch}"
+    seed, step = int(rng.integers(0, 1 << 40)), int(rng.integers(0, 100000))
+    try:
+        check_fused_inference(pol, M, seed % (1 << 30), desc)
+        check_infer_act(pol, M, seed, step, desc)
+    except AssertionError as e:
+        return False, str(e)
+    return True, desc
+
+
 if __name__ == "__main__":
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 50
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     bad = 0
-    for name, fn in (("gae", case_gae), ("fwd_elu", case_fwd_elu), ("infer", case_infer), ("dw", case_dw), ("lstm", case_lstm), ("infer_act", case_infer_act), ("ppo_loss", case_ppo_loss),
-                     ("update", case_update), ("update_graph", case_update_graph)):
+    kinds = (("gae", case_gae), ("fwd_elu", case_fwd_elu), ("infer", case_infer), ("dw", case_dw), ("lstm", case_lstm), ("infer_act", case_infer_act),
+             ("ppo_loss", case_ppo_loss), ("update", case_update), ("update_graph", case_update_graph), ("update_shapes", case_update_shapes),
+             ("infer_act_shapes", case_infer_act_shapes))
+    only = sys.argv[3:]  # optional: the kinds to run (default: all)
+    for name, fn in kinds:
+        if only and name not in only:
+            continue
         rng = np.random.default_rng(seed)
         nbad, worst = 0, ""
         for c in range(cases):

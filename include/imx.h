@@ -622,10 +622,11 @@ int imx_actuator_net_mlp(int64_t N, int64_t J, int num_dense, const int32_t* den
                          float* computed_effort_d, float* applied_effort_d, imx_stream_t stream);
 
 /* rsl_rl EmpiricalNormalization.forward (3rd party v2.3.1, absent): if update != 0 fold the batch (N,D) into the running
- * mean / variance (count, mean, var, std are device buffers; Chan's update with the biased batch variance), then
- * out = (x - mean) / (std + eps).  PARITY UNPINNED.  SURVEY 8f row 3. */
+ * mean / variance (count (int64, like upstream's long buffer), mean, var, std are device buffers; Chan's update with the biased
+ * batch variance, rate = N / (count + N) from the exact count), then out = (x - mean) / (std + eps).  PARITY UNPINNED.
+ * SURVEY 8f row 3. */
 int imx_empirical_normalization(int64_t N, int64_t D, const float* x_d, int update, float eps, float* mean_d, float* var_d,
-                                float* std_d, float* count_d, float* out_d, imx_stream_t stream);
+                                float* std_d, int64_t* count_d, float* out_d, imx_stream_t stream);
 
 /* ---- actor / critic MLP inside PPO.update (rsl_rl v2.3.1 ppo.py::update `loss.backward()` through the nn.Linear / nn.ELU
  * stacks of actor_critic.py; 3rd party, absent: PARITY UNPINNED, checked against torch autograd).  fp32 on the f32 MFMA.

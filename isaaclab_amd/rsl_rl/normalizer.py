@@ -19,7 +19,9 @@ class EmpiricalNormalization(nn.Module):
         self.register_buffer("_mean", torch.zeros(shape).unsqueeze(0))
         self.register_buffer("_var", torch.ones(shape).unsqueeze(0))
         self.register_buffer("_std", torch.ones(shape).unsqueeze(0))
-        self.register_buffer("_count_f", torch.zeros(1))  # float on the device: no host sync in forward
+        # upstream's buffer: ``self.register_buffer("count", torch.tensor(0, dtype=torch.long))``.  Exact past 2^24 (the fp32 count it
+        # replaces was not), advanced on the device: no host sync in forward.  ``_host_count`` mirrors it for the ``until`` test.
+        self.register_buffer("count", torch.tensor(0, dtype=torch.long))
         self._host_count = 0
 
     @property
@@ -30,19 +32,27 @@ class EmpiricalNormalization(nn.Module):
     def std(self):
         return self._std.squeeze(0).clone()
 
-    @property
-    def count(self):
-        return int(self._count_f.item())
+    def updating(self) -> bool:
+        """Whether ``forward`` folds its batch into the statistics (upstream ``update``: ``if until is not None and count >= until``)."""
+        return self.training and (self.until is None or self._host_count < self.until)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        # checkpoints of the earlier layout hold a float (1,) "_count_f" in place of the long "count"
+        old = state_dict.pop(prefix + "_count_f", None)
+        if old is not None and prefix + "count" not in state_dict:
+            state_dict[prefix + "count"] = old.reshape(()).round().long()
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        self._host_count = int(self.count)  # the one sync: a resumed run stops updating at ``until`` like the one it continues
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         x = x.contiguous()
         N, D = x.shape
-        update = self.training and (self.until is None or self._host_count < self.until)
+        update = self.updating()
         if update:
             self._host_count += N
         out = torch.empty_like(x)
         check(lib().imx_empirical_normalization(N, D, x.data_ptr(), int(update), float(self.eps), self._mean.data_ptr(),
-                                                self._var.data_ptr(), self._std.data_ptr(), self._count_f.data_ptr(),
+                                                self._var.data_ptr(), self._std.data_ptr(), self.count.data_ptr(),
                                                 out.data_ptr(), _lib.current_stream(x.device)))
         return out
 

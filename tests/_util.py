@@ -327,3 +327,50 @@ def check_infer_act(pol, M: int, seed: int, step: int, what=""):
     for k, (p, q) in dict(actions=(a0, a1), mu=(m0, m1), sigma=(s0, s1), log_prob=(lp0, lp1), value=(v0, v1), obs=(o0, o1)).items():
         assert torch.equal(p, q), f"{what}: {k} of imx_mlp_infer_act differs from imx_mlp_infer + imx_policy_act"
     assert bool(torch.isfinite(a1).all()), what
+
+
+# ---------------------------------------------------------------------------------------------------- EmpiricalNormalization
+# Tolerance rule of the normaliser checks (tests/test_producer_shapes_gpu.py, tools/fuzz_producers.py): after every batch, the kernel's
+# running mean and variance may differ from the float64 restatement by at most max(FLOAT_TOL * max(|ref|, 1), 2 * e_torch) per element,
+# e_torch = the largest error of the same statistic computed by the fp32 restatement (rsl-rl's own arithmetic) over the whole tensor.
+# The normalised output gets the same bound plus one derived term: an fp32 mean or std is at best within half an ulp of the exact value,
+# and on a column with |mean| = 1e3 and std = 1e-2 half an ulp of the mean alone is 1.5e-3 of output -- whether torch's pairwise sum lands
+# closer on a given column is luck.  So an output element may also be off by two ulps (2 * 2^-23 relative) of the mean and of the std,
+# propagated: 2^-22 * (|mean| + |out| * std) / (std + eps).  The apply step itself is then checked alone, against the float64
+# normalisation with the kernel's own statistics, within FLOAT_TOL.
+NORM_TORCH_FACTOR, NORM_ULPS = 2.0, 2.0 ** -22
+
+
+def check_normalizer_step(norm, out, o64, o32, x, what=""):
+    """One ``EmpiricalNormalization.forward`` (training) of ``x`` (fp32, CPU) that gave ``out``, against the restatement in float64
+    (``o64``) and in fp32 (``o32``); both are advanced by this call."""
+    r64 = o64.forward(x.double(), training=True)
+    r32 = o32.forward(x, training=True)
+    fl = lambda ref: FLOAT_TOL * ref.abs().clamp(min=1.0)  # noqa: E731
+    prop = NORM_ULPS * (o64.mean.abs() + r64.abs() * o64.std) / (o64.std + norm.eps)
+    for name, got, ref, t32, extra in (("mean", norm._mean, o64.mean, o32.mean, 0.0), ("var", norm._var, o64.var, o32.var, 0.0),
+                                       ("output", out, r64, r32, prop)):
+        got = got.double().cpu()
+        assert got.shape == ref.shape, f"{what}: {name} shape {tuple(got.shape)} vs {tuple(ref.shape)}"
+        assert bool(torch.isfinite(got).all()), f"{what}: {name} not finite"
+        err = (got - ref).abs()
+        e_t = float((t32.double() - ref).abs().max())
+        bound = torch.clamp(fl(ref) + extra, min=NORM_TORCH_FACTOR * e_t)
+        over = err > bound
+        assert not bool(over.any()), (f"{what}: {name}: {int(over.sum())} elements over the bound, max err {float(err.max()):.3e} "
+                                      f"(fp32 torch err {e_t:.3e})")
+    own = (x.double() - norm._mean.double().cpu()) / (norm._std.double().cpu() + norm.eps)
+    assert_close(out, own, FLOAT_TOL, f"{what}: output against the float64 apply of the kernel's own statistics")
+
+
+# The actuator networks (ActuatorNetMLP here; tests/_producer_cases.py) follow the same floor as the gradient rule: an output element may
+# also be off by GRAD_SUM_FLOOR of the network evaluated on absolute values (|W|, |b|, |inputs|, times |torque scale|) -- the sum of the
+# absolute values of its terms, which bounds the rounding of a dot product that cancels (every activation used has |act(x)| <= |x|).
+# Seen: a tanh MLP output of 0.3 from terms of ~40 in size, torque scale 12: 3.8e-5 off, 1.2e-6 of its term sum.
+def assert_close_terms(got, ref, terms, what=""):
+    got, ref, terms = (torch.as_tensor(t).double().cpu() for t in (got, ref, terms))
+    assert got.shape == ref.shape, f"{what}: shape {tuple(got.shape)} vs {tuple(ref.shape)}"
+    err = (got - ref).abs()
+    bound = torch.maximum(FLOAT_TOL * ref.abs().clamp(min=1.0), GRAD_SUM_FLOOR * terms)
+    over = ~(err <= bound)
+    assert not bool(over.any()), f"{what}: {int(over.sum())} elements over the bound, max err {float(err.max()):.3e}"

@@ -244,3 +244,33 @@ def test_activation_backward_of_the_update_equals_autograd_under_inference_mode(
         zi, di = z.clone(), dh.clone()
         got = _act_backward(act, di, zi, act(zi))
     assert torch.equal(got, ref)
+
+
+def test_normalizer_state_dict_round_trip_keeps_count_and_until():
+    """The running count is upstream's long ``count`` buffer; loading a state dict restores the host-side count that decides ``until``,
+    so a resumed run stops updating where the saved one would have.  Checkpoints of the earlier layout (a float ``_count_f``) still load."""
+    import torch
+
+    from isaaclab_amd.rsl_rl.normalizer import EmpiricalNormalization
+
+    a = EmpiricalNormalization([5], until=1000)
+    a.count.fill_(100003 * 170)  # past 2^24: an fp32 count could not hold it
+    a._host_count = int(a.count)
+    a._mean.normal_()
+    sd = a.state_dict()
+    assert set(sd) == {"_mean", "_var", "_std", "count"} and sd["count"].dtype == torch.int64 and sd["count"].dim() == 0
+    b = EmpiricalNormalization([5], until=1000)
+    assert b.updating()
+    b.load_state_dict(sd)
+    assert int(b.count) == 100003 * 170 and b._host_count == 100003 * 170
+    assert torch.equal(b._mean, a._mean)
+    assert not b.updating()  # past ``until``: forward no longer folds batches in
+    c = EmpiricalNormalization([5], until=10 ** 8)
+    c.load_state_dict(sd)
+    assert c.updating()
+    c.eval()
+    assert not c.updating()
+    old = {"_mean": sd["_mean"], "_var": sd["_var"], "_std": sd["_std"], "_count_f": torch.tensor([4096.0 * 3])}
+    d = EmpiricalNormalization([5], until=4096 * 3)
+    d.load_state_dict(old)
+    assert int(d.count) == 4096 * 3 and d.count.dtype == torch.int64 and not d.updating()

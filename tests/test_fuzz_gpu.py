@@ -44,7 +44,8 @@ def test_rollout_sweep(seed):
     fuzz_rollout.one_case(seed)
 
 
-@pytest.mark.parametrize("kind", ["contact", "command", "pd_actuator", "articulation"])
+@pytest.mark.parametrize("kind", ["contact", "command", "pd_actuator", "articulation", "delayed", "remotized", "lstm_net", "mlp_net",
+                                  "normalizer", "events"])
 def test_producer_sweep(kind):
     import fuzz_producers as fp
 

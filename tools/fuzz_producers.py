@@ -1,8 +1,14 @@
-"""Random sweeps of two stateful producers against their oracles (which the reference's fixtures pin): ContactSensor update (random
-body / history counts, update period gating, thresholds, forces, partial resets) and UniformVelocityCommand (random ranges, heading /
-standing fractions, resampling windows shorter and longer than a step, resets, fed uniforms).  Test infrastructure, run on the GPU box:
-    python tools/fuzz_producers.py [cases] [seed]"""
+"""Random sweeps of the stateful producers against their oracles (which the reference's fixtures pin): ContactSensor update (random
+body / history counts, update period gating, thresholds, forces, partial resets), UniformVelocityCommand (random ranges, heading /
+standing fractions, resampling windows shorter and longer than a step, resets, fed uniforms), and -- against the oracles run in float64,
+cases in tests/_producer_cases.py -- the delayed / remotized PD actuator, the LSTM and MLP actuator nets, the empirical normaliser and the
+reset / interval events with the terrain curriculum.  lstm_net picks one of the three ANYdrive-shape kernels per case; the two that
+IMX_LSTM_KERNEL selects run in a persistent child process each.  Test infrastructure, run on the GPU box:
+    python tools/fuzz_producers.py [cases] [seed] [kind ...]"""
+import atexit
+import json
 import os
+import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -127,12 +133,116 @@ def case_articulation(rng):
     return f"N={N} J={J} dt={dt}"
 
 
+def case_delayed(rng):
+    from _producer_cases import delayed_case
+
+    mx = int(rng.choice([0, 1, 2, 4, 7, 37]))
+    mn = int(rng.integers(0, mx + 1))
+    N, J = int(rng.choice([1, 2, 63, 65, 1000, 4097])), int(rng.choice([1, 3, 12, 23]))
+    return delayed_case(N, J, mn, mx, None, int(rng.integers(0, 1 << 30)))
+
+
+def case_remotized(rng):
+    from _producer_cases import delayed_case
+
+    mx = int(rng.choice([0, 1, 4, 37]))
+    mn = int(rng.integers(0, mx + 1))
+    N, J = int(rng.choice([1, 7, 63, 65, 1000, 4097])), int(rng.choice([1, 3, 12]))
+    return delayed_case(N, J, mn, mx, int(rng.choice([1, 2, 3, 9, 16])), int(rng.integers(0, 1 << 30)), dup=bool(rng.integers(0, 2)))
+
+
+_CHILDREN = {}
+
+
+def _close(p):
+    if p.poll() is None:
+        p.stdin.close()
+        p.wait(timeout=60)
+
+
+def _child(kern):
+    p = _CHILDREN.get(kern)
+    if p is None or p.poll() is not None:
+        cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [os.path.join(ROOT, "tests", "_producer_cases.py"), "--serve"]
+        p = subprocess.Popen(cmd, env=dict(os.environ, IMX_LSTM_KERNEL=kern), cwd=ROOT, stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+        _CHILDREN[kern] = p
+        atexit.register(_close, p)
+    return p
+
+
+def case_lstm_net(rng):
+    """Random network and shape.  ANYdrive shapes (hidden 8, <= 4 layers, head none / 16 / 32) go to the matrix-core kernel in this
+    process or to the lanes / register kernel in its child; the others to the generic kernel here."""
+    from _producer_cases import ACTS, lstm_case
+
+    fast = bool(rng.integers(0, 2))
+    if fast:
+        H, L, head = 8, int(rng.integers(1, 5)), [[], [16], [32]][int(rng.integers(0, 3))]
+    else:
+        H, L = int(rng.choice([1, 3, 5, 8, 16, 32])), int(rng.integers(1, 6))
+        L = min(L, 3) if H == 32 else L
+        head = [[], [8], [24], [16, 8], [64]][int(rng.integers(0, 5))]
+        if H == 8 and L <= 4 and head in ([], [16], [32]):
+            head = [24]
+    N, J = int(rng.choice([1, 7, 31, 64, 129, 1000, 4097])), int(rng.choice([1, 3, 12]))
+    kw = dict(N=N, J=J, H=H, L=L, head=head, act=str(rng.choice(ACTS)), seed=int(rng.integers(0, 1 << 30)), steps=int(rng.integers(2, 9)),
+              unaligned=bool(not fast and H == 8 and rng.integers(0, 2)))
+    kern = str(rng.choice(["m", "l", "r"])) if fast else "generic"
+    if kern in ("m", "generic"):
+        return f"[{kern}] " + lstm_case(**kw)
+    p = _child(kern)
+    p.stdin.write(json.dumps(kw) + "\n")
+    p.stdin.flush()
+    for line in p.stdout:
+        if line.startswith("@@ ok "):
+            return f"[{kern}] " + line[6:].strip()
+        if line.startswith("@@ FAIL "):
+            raise AssertionError(f"IMX_LSTM_KERNEL={kern}: " + line[8:].strip())
+    raise RuntimeError(f"IMX_LSTM_KERNEL={kern} child exited with {p.wait(timeout=60)} on {kw}")
+
+
+def case_mlp_net(rng):
+    from _producer_cases import ACTS, mlp_case
+
+    idx = [int(v) for v in rng.integers(0, 6, size=int(rng.integers(1, 4)))]
+    widths = [int(rng.choice([1, 8, 16, 24, 32, 64])) for _ in range(int(rng.integers(0, 4)))]
+    N, J = int(rng.choice([1, 7, 63, 65, 1000, 4097])), int(rng.choice([1, 3, 12]))
+    scales = tuple(float(v) for v in rng.choice([0.1, 0.5, 1.0, 2.0, 7.5], size=3))
+    return mlp_case(N, J, idx, str(rng.choice(["pos_vel", "vel_pos"])), str(rng.choice(ACTS)), widths, int(rng.integers(0, 1 << 30)), scales)
+
+
+def case_normalizer(rng):
+    from _producer_cases import normalizer_case
+
+    D = int(rng.choice([1, 2, 63, 64, 65, 235, 310, 513]))
+    rows = [1, 2, 63, 64, 4096, 4097] + ([100003] if D <= 65 else [])  # (a 100 003 x 513 batch is 0.2 GB of oracle work per call)
+    batches = [int(rng.choice(rows)) for _ in range(int(rng.integers(1, 5)))]
+    return normalizer_case(D, batches, int(rng.integers(0, 1 << 30)))
+
+
+def case_events(rng):
+    from _producer_cases import events_case
+
+    N, J, NB = int(rng.choice([1, 2, 63, 64, 65, 255, 257, 4097, 100003])), int(rng.choice([1, 12, 37])), int(rng.choice([1, 4, 17]))
+    ids = None
+    if rng.integers(0, 2):
+        ids = sorted(int(b) for b in rng.choice(NB, size=int(rng.integers(1, NB + 1)), replace=False))
+    R, C = int(rng.choice([1, 2, 10])), int(rng.choice([1, 3, 20]))
+    return events_case(N, J, NB, R, C, int(rng.integers(0, 1 << 30)), body_ids=ids, degenerate=bool(rng.integers(0, 2)))
+
+
+KINDS = (("contact_sensor", case_contact), ("velocity_command", case_command), ("pd_actuator", case_pd_actuator), ("articulation", case_articulation),
+         ("delayed", case_delayed), ("remotized", case_remotized), ("lstm_net", case_lstm_net), ("mlp_net", case_mlp_net),
+         ("normalizer", case_normalizer), ("events", case_events))
+
 if __name__ == "__main__":
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 50
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    only = set(sys.argv[3:])
     bad = 0
-    for name, fn in (("contact_sensor", case_contact), ("velocity_command", case_command), ("pd_actuator", case_pd_actuator),
-                     ("articulation", case_articulation)):
+    for name, fn in KINDS:
+        if only and name not in only:
+            continue
         rng = np.random.default_rng(seed)
         nbad, last = 0, ""
         for c in range(cases):

@@ -89,6 +89,10 @@ IMX_DEV bool any_ids(const int32_t* __restrict__ ids, int n, F f) {
 
 // max over history of the force norm on body b (rewards.py:266, terminations.py:157): max_h sqrt(s_h) with s_h = (x^2 + y^2) + z^2.
 // sqrtf is correctly rounded and monotone, so max_h sqrt(s_h) == sqrt(max_h s_h) bit for bit: ONE square root per body.
+// torch.clamp / Tensor.clip of an observation: NaN stays NaN (fminf / fmaxf alone return the bound).  A height-scan ray that misses
+// (+inf hit) through a DigitalFilter gives -inf - -inf = NaN, and the reference's observation is NaN, not the clip bound.
+IMX_DEV float clip_keep_nan(float v, float lo, float hi) { return v != v ? v : fminf(fmaxf(v, lo), hi); }
+
 IMX_DEV float max_hist_force(const float* __restrict__ F, int64_t e, int H, int B, int b) {
     const float* f = F + ((size_t)e * H * B + b) * 3;
     float m = 0.0f;  // squared norms are >= 0
@@ -850,7 +854,7 @@ IMX_DEV float obs_post(const XCol& x, float v, int corrupt, const float* __restr
         const float nz = noise_sample<GAUSS>(flags, lo, hi, noise_u, seed, step, e, D, c);
         v = (flags & IMX_F_NOISE_ADD) ? v + nz : ((flags & IMX_F_NOISE_SCALE) ? v * nz : nz);
     }
-    if (flags & IMX_F_CLIP) v = fminf(fmaxf(v, f_of(x.b.w)), f_of(x.c.x));
+    if (flags & IMX_F_CLIP) v = clip_keep_nan(v, f_of(x.b.w), f_of(x.c.x));
     if (flags & IMX_F_SCALE) v = v * f_of(x.c.y);
     return v;
 }
@@ -870,7 +874,7 @@ IMX_DEV float apply_modifiers(const int32_t* __restrict__ W, int xmod, float v, 
         switch (op) {
             case IMX_M_SCALE: v = v * a; break;
             case IMX_M_BIAS: v = v + a; break;
-            case IMX_M_CLIP: v = fminf(fmaxf(v, a), b); break;
+            case IMX_M_CLIP: v = clip_keep_nan(v, a, b); break;
             case IMX_M_INTEGRATOR: {  // integral += (data + y_prev) / 2 * dt; y_prev = data (modifier.py:247-259)
                 float* s = st + soff * d;
                 const float yp = zero ? 0.0f : s[d];
@@ -1123,7 +1127,7 @@ k_obs_lean(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, MeshView M, c
             const float nz = noise_sample<false>(flags, nlo, nhi, noise_u, seed, step, e, P.D, c);
             v = (flags & IMX_F_NOISE_ADD) ? v + nz : ((flags & IMX_F_NOISE_SCALE) ? v * nz : nz);
         }
-        if (flags & IMX_F_CLIP) v = fminf(fmaxf(v, clo), chi);
+        if (flags & IMX_F_CLIP) v = clip_keep_nan(v, clo, chi);
         if (flags & IMX_F_SCALE) v = v * scale;
         obs_row[(unsigned)c] = v;
     } else {

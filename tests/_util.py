@@ -374,3 +374,50 @@ def assert_close_terms(got, ref, terms, what=""):
     bound = torch.maximum(FLOAT_TOL * ref.abs().clamp(min=1.0), GRAD_SUM_FLOOR * terms)
     over = ~(err <= bound)
     assert not bool(over.any()), f"{what}: {int(over.sum())} elements over the bound, max err {float(err.max()):.3e}"
+
+
+# The env step (k_action, k_term_rew + step_tail, the k_obs* kernels; tests/_step_cases.py) against the oracle run in float64 on the same
+# fp32 state and fp32-rounded cfg scalars.  An element may be off by FLOAT_TOL of its |ref64|, or by STEP_TORCH_FACTOR times the largest
+# error the fp32 oracle (the reference's own arithmetic) makes on that term's tensor, whichever is larger.  Below 1 in magnitude this is
+# tighter than assert_close's FLOAT_TOL * max(|ref|, 1).  The fp32 error is taken over the envs held to fp64 (see the masks below).
+# An Episode_Reward/* log entry (a mean of episode sums over the reset envs) may also be off by STEP_SUM_FLOOR of the mean of the
+# |episode sums| it averages: the kernel sums fp32 group partials in a fixed tree, torch in its own order, and where the sums cancel
+# (feet_air_time: last_air_time - threshold of either sign) neither lands near the fp64 value in relative terms.
+# Masks (terminated, time_outs, term_dones, reset ids) are bit-exact against fp64, except on the envs where the fp32 oracle decides
+# differently from fp64: those sit within rounding of a threshold, and they are held bit-exact to the fp32 oracle -- the reference's own
+# fp32 decision -- instead.  So are the envs whose tilt lies within STEP_ACOS_BAND rad of a bad_orientation limit_angle (acos is
+# ill-conditioned there: an fp32 rounding of the projected gravity moves the angle by ~3e-7).  At most STEP_NEAR_FRACTION of the envs may
+# take that path.
+STEP_TORCH_FACTOR, STEP_SUM_FLOOR, STEP_ACOS_BAND, STEP_NEAR_FRACTION = 2.0, 2.0 ** -18, 2e-6, 0.01
+
+
+def step_bound(ref64, ref32, rows=None):
+    """Per-element bound of the env-step rule above; ``rows``: the envs (first dim) the fp32 error is taken over (default all)."""
+    ref64, ref32 = torch.as_tensor(ref64).double().cpu(), torch.as_tensor(ref32).double().cpu()
+    e32 = (ref32 - ref64).abs()
+    if rows is not None:
+        e32 = e32[rows]
+    e_t = float(e32.max()) if e32.numel() else 0.0
+    return torch.clamp(FLOAT_TOL * ref64.abs(), min=STEP_TORCH_FACTOR * e_t), e_t
+
+
+def assert_close_step(got, ref64, ref32, what="", rows=None):
+    """``got`` (the kernel) against ``ref64`` under the env-step rule; ``rows`` (bool, first dim): the envs held to fp64 -- the others
+    are held to ``ref32`` under FLOAT_TOL relative (they sit on a decision the fp32 oracle takes differently, see above)."""
+    got = torch.as_tensor(got).double().cpu()
+    ref64, ref32 = torch.as_tensor(ref64).double().cpu(), torch.as_tensor(ref32).double().cpu()
+    assert got.shape == ref64.shape, f"{what}: shape {tuple(got.shape)} vs {tuple(ref64.shape)}"
+    fin = torch.isfinite(ref64)  # (a ray that misses: +-inf, or NaN through a filter -- the same non-finite value, element for element)
+    assert torch.equal(torch.isfinite(got), fin), f"{what}: finite masks differ"
+    assert torch.equal(torch.isnan(got), torch.isnan(ref64)) and bool((got[torch.isinf(ref64)] == ref64[torch.isinf(ref64)]).all()), what
+    if rows is None:
+        rows = torch.ones(got.shape[0], dtype=torch.bool)
+    got, ref64, ref32 = (torch.where(fin, t, torch.zeros_like(t)) for t in (got, ref64, ref32))
+    bound, e_t = step_bound(ref64, ref32, rows)
+    err = (got - ref64).abs()
+    over = (err > bound) & rows.view(-1, *([1] * (got.dim() - 1)))
+    assert not bool(over.any()), (f"{what}: {int(over.sum())} elements over the bound, max err {float(err[over].max()):.3e} at |ref| "
+                                  f"{float(ref64[over].abs().max()):.3e} (fp32 oracle err {e_t:.3e})")
+    if not bool(rows.all()):
+        far = ~rows
+        assert_close(got[far], ref32[far], FLOAT_TOL, f"{what}: envs on a threshold, against the fp32 oracle")

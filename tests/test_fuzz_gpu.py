@@ -37,6 +37,13 @@ def test_random_cfg_sweep(seed):
     fuzz_cfg.one_case(seed)
 
 
+@pytest.mark.parametrize("seed", [7100, 7101, 7102, 7103])
+def test_random_cfg_fp64_sweep(seed):
+    import fuzz_cfg
+
+    fuzz_cfg.one_case_fp64(seed)
+
+
 @pytest.mark.parametrize("seed", [9000, 9001, 9002, 9003])
 def test_rollout_sweep(seed):
     import fuzz_rollout

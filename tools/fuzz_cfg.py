@@ -3,7 +3,10 @@ Anymal-C scene with random subsets (order kept) of the reward / termination / ob
 term the path knows, two observation groups), random weights (incl. 0), scale / clip / uniform, gaussian and constant noise (add, scale, abs), modifier chains (scale, bias, clip,
 DigitalFilter, Integrator), per-term and
 per-group history, episode length, the six joint action classes in random combinations (processed actions compared).  Masks / ids bit-exact, floats 1e-5.  Test infrastructure, run on
-the GPU box:  python tools/fuzz_cfg.py [cases] [first_seed]"""
+the GPU box:  python tools/fuzz_cfg.py [cases] [first_seed]
+
+``--fp64``: the same random cfgs per term against the oracle in float64 on an edge-shaped feed (tests/_step_cases.py, the env-step rule of
+tests/_util.py), at env counts across the group-size and wave-order boundaries and both step-tail modes."""
 import copy
 import json
 import os
@@ -204,13 +207,33 @@ def one_case(case_seed: int) -> str:
     return f"N={N} steps={steps} resets={nreset}: {what}"
 
 
+def one_case_fp64(case_seed: int) -> str:
+    from _step_cases import run_case
+    from isaaclab_amd.plan import compile_plan
+
+    rng = np.random.default_rng(case_seed)
+    fx, what = mutate(rng)
+    N = int(rng.choice([1, 2, 17, 63, 64, 65, 257, 1000, 2049, 8192, 8193, 16385]))
+    steps = int(rng.integers(3, 5))
+    tail = str(rng.choice(["deferred", "in_kernel"]))
+    try:
+        compile_plan(fx["env"], ROBOTS[fx["robot"]])
+    except NotImplementedError as exc:  # combinations the product refuses by name at construction
+        return f"REFUSED ({str(exc)[:90]})"
+    seen = run_case(fx, N, seed=case_seed, steps=steps, tail=tail)
+    return f"N={N} steps={steps} tail={tail} resets={seen['resets']} near={seen['near']}: {what}"
+
+
 if __name__ == "__main__":
-    cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
-    first = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    fp64 = "--fp64" in sys.argv
+    args = [a for a in sys.argv[1:] if a != "--fp64"]
+    cases = int(args[0]) if len(args) > 0 else 40
+    first = int(args[1]) if len(args) > 1 else 0
+    run = one_case_fp64 if fp64 else one_case
     bad = 0
     for c in range(first, first + cases):
         try:
-            print(f"case {c}: ok   {one_case(c)}", flush=True)
+            print(f"case {c}: ok   {run(c)}", flush=True)
         except (AssertionError, NotImplementedError, ValueError, KeyError, RuntimeError) as e:
             bad += 1
             print(f"case {c}: FAIL {type(e).__name__}: {str(e)[:1500]}", flush=True)

@@ -46,7 +46,8 @@ enum imx_header_word {
     /* height scanner as a SensorBase (sensors/sensor_base.py:182-205,287-297; ray_caster.py:107-114,236-237) */
     IMX_H_SCAN_PERIOD /* f32 cfg.update_period */, IMX_H_SCAN_DT /* f32 physics dt: SensorBase.update(dt) per physics step */,
     IMX_H_SCAN_SUBSTEPS /* decimation: update() calls per env step */, IMX_H_SCAN_DRIFT_LO /* f32 cfg.drift_range */,
-    IMX_H_SCAN_DRIFT_HI, IMX_H_SCAN_STATEFUL /* 1: per-env timestamps / drift are kept (imx_buffers.scan_state) */
+    IMX_H_SCAN_DRIFT_HI, IMX_H_SCAN_STATEFUL /* 1: per-env timestamps / drift are kept (imx_buffers.scan_state) */,
+    IMX_H_TERM_SLOTS /* per-env reward-term state slots (imx_buffers.term_state rows): one per IMX_W_PROGRESS_REWARD record */
 };
 
 /* record layout (IMX_REC_WORDS int32/f32 words) */
@@ -154,7 +155,15 @@ enum imx_rew_op {
     IMX_W_JOINT_ACCELERATION_PENALTY, /* :252-256 ids = ALL joints (the function ignores asset_cfg.joint_ids) */
     IMX_W_JOINT_POSITION_PENALTY,     /* :259-268 ids = all joints; p0 = stand_still_scale, p1 = velocity_threshold */
     IMX_W_JOINT_TORQUES_PENALTY,      /* :271-275 ids = all joints */
-    IMX_W_JOINT_VELOCITY_PENALTY      /* :278-282 ids = all joints */
+    IMX_W_JOINT_VELOCITY_PENALTY,     /* :278-282 ids = all joints */
+    /* isaaclab_tasks .../classic/humanoid/mdp/rewards.py (Isaac-Ant-v0, Isaac-Humanoid-v0) */
+    IMX_W_UPRIGHT_POSTURE_BONUS,      /* :21-27   p0 = threshold: -projected_gravity_b.z > threshold */
+    IMX_W_MOVE_TO_TARGET_BONUS,       /* :30-40   p0 = threshold, p1, p2 = target x, y (base_heading_proj) */
+    IMX_W_PROGRESS_REWARD,            /* :43-78   p0..p2 = target; aux0 = term_state slot (the potentials; prev_potentials is the value
+                                                  read before the update) */
+    IMX_W_JOINT_POS_LIMITS_PENALTY_RATIO, /* :81-111 ids = all joints; ids2 = (J) f32 gear_ratio_scaled; p0 = threshold,
+                                                  p1 = f32(1 - threshold) (the Python double) */
+    IMX_W_POWER_CONSUMPTION           /* :114-140 ids = all joints; ids2 = (J) f32 gear_ratio_scaled; reads buf.action (raw, A == J) */
 };
 
 /* observation ops -- envs/mdp/observations.py */
@@ -175,7 +184,14 @@ enum imx_obs_op {
     IMX_O_HEIGHT_SCAN,      /* :165-173 p0=offset */
     IMX_O_LAST_ACTION,      /* :512-521 */
     IMX_O_GENERATED_COMMANDS, /* :529-531 */
-    IMX_O_EXTERNAL          /* aux0 = column offset in ext_obs */
+    IMX_O_EXTERNAL,         /* aux0 = column offset in ext_obs */
+    /* isaaclab_tasks .../classic/humanoid/mdp/observations.py; angles are atan2(sin, cos) of the euler_xyz_from_quat angle mod 2 pi */
+    IMX_O_BASE_YAW_ROLL,    /* :19-30  2 columns: yaw, roll */
+    IMX_O_BASE_UP_PROJ,     /* :33-40  -projected_gravity_b.z */
+    IMX_O_BASE_HEADING_PROJ,/* :43-58  p0..p2 = target_pos: quat_rotate(q, FORWARD_VEC_B) . normalize((target - pos) * (1, 1, 0)) */
+    IMX_O_BASE_ANGLE_TO_TARGET, /* :61-77 p0..p2 = target_pos */
+    IMX_O_BODY_INCOMING_WRENCH  /* envs/mdp/observations.py:176-185 ids = asset bodies; 6 columns per body in id order;
+                                   state.link_incoming_joint_force */
 };
 
 /* action ops -- envs/mdp/actions/joint_actions.py:130-139 (raw*scale+offset[,clamp]) */
@@ -211,6 +227,8 @@ typedef struct imx_state {
     const int64_t* command_counter;     /* (N)   CommandTerm.command_counter */
     const float* body_pos_w;            /* (N,NB,3) ArticulationData.body_pos_w, or NULL unless a term reads it */
     const float* last_contact_time;     /* (N,B) ContactSensorData.last_contact_time, or NULL unless a term reads it */
+    const float* link_incoming_joint_force; /* (N,NB,6) root_physx_view.get_link_incoming_joint_force() (force, torque), or NULL
+                                               unless a term reads it */
 } imx_state_t;
 
 /* ---- manager state + outputs (caller-owned, persistent across steps) ------------------------------------------ */
@@ -256,6 +274,9 @@ typedef struct imx_buffers {
                                     Curriculum/terrain_levels (curriculum_manager.py:95-118: mean level over all envs); needs the deferred
                                     tail (flags bit 0 / enable_corruption bit 4) */
     int64_t ev_flags;            /* bit 0: the metrics entries exist, bit 1: the curriculum entry exists */
+    float* term_state;           /* (IMX_H_TERM_SLOTS, N) per-env state of stateful reward terms (progress_reward.potentials), carried
+                                    across steps; written by imx_terminations_rewards (the reset branch once the env's reset flag is
+                                    known) and imx_term_state_reset.  NULL unless the plan has stateful terms */
 } imx_buffers_t;
 
 /* ---- slot t of an rsl_rl RolloutStorage, filled by the step kernel itself (imx_terminations_rewards_rollout) ------------------ */
@@ -437,6 +458,12 @@ int imx_observations(const imx_plan_t* plan, int64_t num_envs, const imx_state_t
 /* Name of the kernel imx_observations launches for this plan ("k_obs_lean<false>", "k_obs<false,true>", ...): benchmarks and
  * profiles attribute their timings to the kernel that actually ran.  Static string. */
 const char* imx_observations_kernel_name(const imx_plan_t* plan);
+/* The reset(env_ids) of the plan's stateful reward terms (RewardManager.reset -> ManagerTermBase.reset, reward_manager.py:100-126):
+ * progress_reward.potentials = -||target - root_pos_w|| / step_dt over all three components (classic/humanoid/mdp/rewards.py:54-63),
+ * the same device function as the reset branch of imx_terminations_rewards.  mask_d: optional (N) uint8, NULL = every env.  Reads
+ * state->root_pos_w; a no-op for a plan without stateful terms. */
+int imx_term_state_reset(const imx_plan_t* plan, int64_t num_envs, const imx_state_t* state, const imx_buffers_t* buf,
+                         const uint8_t* mask_d, imx_stream_t stream);
 
 /* ArticulationData.root_lin_vel_b / root_ang_vel_b / projected_gravity_b
  * (assets/articulation/articulation_data.py:512-515,603-619) = quat_rotate_inverse (utils/math.py:605-625). */

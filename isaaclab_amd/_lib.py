@@ -16,13 +16,14 @@ STATE_FIELDS = (
     "applied_torque", "computed_torque", "default_joint_pos", "default_joint_vel", "soft_joint_pos_limits",
     "soft_joint_vel_limits", "body_lin_vel_w", "command", "net_forces_w_history", "last_air_time",
     "current_air_time", "current_contact_time", "env_origins", "ext_reward", "ext_term", "ext_obs",
-    "body_lin_acc_w", "command_time_left", "command_counter", "body_pos_w", "last_contact_time",
+    "body_lin_acc_w", "command_time_left", "command_counter", "body_pos_w", "last_contact_time", "link_incoming_joint_force",
 )
 BUFFER_FIELDS = (
     "episode_length_buf", "action", "prev_action", "processed_action", "reward_buf", "episode_sums", "step_reward",
     "term_dones", "terminated", "truncated", "reset_buf", "reset_env_ids", "counters", "log_out", "obs", "scratch", "mod_state",
     "obs_extra1", "obs_extra2", "obs_extra3", "scan_state", "scan_hit_z", "scan_drift_feed", "log_accum",
     "ev_part", "ev_flags",  # (ev_flags is an int64 carried in a pointer-sized field)
+    "term_state",
 )
 
 
@@ -102,6 +103,7 @@ _SIGNATURES = {
     "imx_terminations_rewards_rollout": (c_int, [c_void_p, c_int64, POINTER(ImxState), POINTER(ImxBuffers), c_int, POINTER(ImxRolloutSlot),
                                                  c_void_p]),
     "imx_observations_kernel_name": (c_char_p, [c_void_p]),
+    "imx_term_state_reset": (c_int, [c_void_p, c_int64, POINTER(ImxState), POINTER(ImxBuffers), c_void_p, c_void_p]),
     "imx_orch_part_floats": (c_size_t, [c_int64]),
     "imx_reset_orchestrate": (c_int, [POINTER(ImxOrch), c_void_p]),
     "imx_observations": (c_int, [c_void_p, c_int64, POINTER(ImxState), POINTER(ImxBuffers), c_void_p, c_void_p, c_uint64,

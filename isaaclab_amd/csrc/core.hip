@@ -83,6 +83,8 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
     IMX_REQUIRE(w[IMX_H_GROUP_OFF] >= IMX_HEADER_WORDS && (size_t)w[IMX_H_GROUP_OFF] + 4 * (size_t)p->ngroups <= nwords, "plan: group table out of range");
     IMX_REQUIRE(p->nobs >= 0 && p->nobs <= 4096 && p->nact >= 0 && p->nact <= 64, "plan: bad obs/action term counts");
     IMX_REQUIRE(p->CMD >= 0 && p->CMD <= 16, "plan: bad command dim");
+    p->term_slots = w[IMX_H_TERM_SLOTS];
+    IMX_REQUIRE(p->term_slots >= 0 && p->term_slots <= 256, "plan: %d reward-term state slots", p->term_slots);
     auto table_ok = [&](int off, int n) {
         return n == 0 || (off >= IMX_HEADER_WORDS && (size_t)off + (size_t)n * IMX_REC_WORDS <= nwords);
     };
@@ -109,7 +111,7 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
     for (int k = 0; k < p->nrew; ++k) {
         const int32_t* r = &w[p->rew_off + k * IMX_REC_WORDS];
         const int op = r[IMX_R_OP];
-        IMX_REQUIRE(op >= IMX_W_IS_ALIVE && op <= IMX_W_JOINT_VELOCITY_PENALTY, "plan: unknown reward op %d", op);
+        IMX_REQUIRE(op >= IMX_W_IS_ALIVE && op <= IMX_W_POWER_CONSUMPTION, "plan: unknown reward op %d", op);
         IMX_REQUIRE(r[IMX_R_OUT] == k, "plan: reward record %d has index %d", k, r[IMX_R_OUT]);
         int limit = p->J;
         const char* what = "joint";
@@ -129,6 +131,15 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
         if (op == IMX_W_AIR_TIME_REWARD || op == IMX_W_GAIT_REWARD)
             IMX_REQUIRE(r[IMX_R_NIDS] == 4, "plan: reward record %d (op %d) needs exactly 4 feet", k, op);
         if (op == IMX_W_AIR_TIME_VARIANCE_PENALTY) IMX_REQUIRE(r[IMX_R_NIDS] > 0, "plan: air_time_variance_penalty without feet");
+        if (op == IMX_W_PROGRESS_REWARD)
+            IMX_REQUIRE(r[IMX_R_AUX0] >= 0 && r[IMX_R_AUX0] < p->term_slots, "plan: reward record %d: state slot %d outside [0, %d)", k,
+                        r[IMX_R_AUX0], p->term_slots);
+        if (op == IMX_W_JOINT_POS_LIMITS_PENALTY_RATIO || op == IMX_W_POWER_CONSUMPTION) {  // per-joint gear table, every joint in order
+            IMX_REQUIRE(r[IMX_R_NIDS] == p->J && r[IMX_R_NIDS2] == p->J && r[IMX_R_IDS2_OFF] >= IMX_HEADER_WORDS &&
+                            (size_t)r[IMX_R_IDS2_OFF] + (size_t)p->J <= nwords,
+                        "plan: reward record %d (op %d): gear table needs every joint", k, op);
+            if (op == IMX_W_POWER_CONSUMPTION) IMX_REQUIRE(p->A == p->J, "plan: power_consumption multiplies (N,A) actions with (N,J) velocities: A=%d J=%d", p->A, p->J);
+        }
         if (op == IMX_W_FEET_SLIDE || op == IMX_W_FOOT_SLIP_PENALTY) {
             IMX_REQUIRE(r[IMX_R_NIDS2] == r[IMX_R_NIDS], "plan: feet_slide needs equally many sensor and asset bodies");
             if (check_ids(w, r[IMX_R_IDS2_OFF], r[IMX_R_NIDS2], p->NB, "asset body", k)) return 1;
@@ -153,7 +164,7 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
     for (int k = 0; k < p->nobs; ++k) {
         const int32_t* r = &w[p->obs_off + k * IMX_REC_WORDS];
         const int op = r[IMX_R_OP];
-        IMX_REQUIRE(op >= IMX_O_BASE_POS_Z && op <= IMX_O_EXTERNAL, "plan: unknown observation op %d", op);
+        IMX_REQUIRE(op >= IMX_O_BASE_POS_Z && op <= IMX_O_BODY_INCOMING_WRENCH, "plan: unknown observation op %d", op);
         const int g = r[IMX_R_WEIGHT];
         IMX_REQUIRE(g >= 0 && g < p->ngroups, "plan: observation record %d names group %d", k, g);
         {
@@ -187,6 +198,13 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
         } else {
             IMX_REQUIRE(!(r[IMX_R_FLAGS] & IMX_F_SCAN_TWIN), "plan: observation record %d: twin flag on a non-scan term", k);
         }
+        if (op == IMX_O_BODY_INCOMING_WRENCH) {
+            IMX_REQUIRE(d == 6 * r[IMX_R_NIDS], "plan: body_incoming_wrench dim %d != 6 x %d bodies", d, r[IMX_R_NIDS]);
+            if (check_ids(w, r[IMX_R_IDS_OFF], r[IMX_R_NIDS], p->NB, "asset body", k)) return 1;
+        }
+        if (op == IMX_O_BASE_YAW_ROLL) IMX_REQUIRE(d == 2, "plan: base_yaw_roll must have dim 2");
+        if (op == IMX_O_BASE_UP_PROJ || op == IMX_O_BASE_HEADING_PROJ || op == IMX_O_BASE_ANGLE_TO_TARGET)
+            IMX_REQUIRE(d == 1, "plan: observation op %d must have dim 1", op);
         if (op == IMX_O_LAST_ACTION) IMX_REQUIRE(d == p->A, "plan: last_action dim %d != A=%d", d, p->A);
         if (op == IMX_O_GENERATED_COMMANDS) IMX_REQUIRE(d == p->CMD, "plan: command dim mismatch");
         if (op == IMX_O_EXTERNAL)
@@ -296,6 +314,10 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
                            op == IMX_O_JOINT_VEL_REL || op == IMX_O_JOINT_POS_LIMIT_NORMALIZED;
         if (joint) x[10] = w[(size_t)w[ro + IMX_R_IDS_OFF] + j];
         if (op == IMX_O_EXTERNAL) x[10] = w[ro + IMX_R_AUX0];
+        if (op == IMX_O_BODY_INCOMING_WRENCH) x[10] = w[(size_t)w[ro + IMX_R_IDS_OFF] + j / 6] * 6 + j % 6;  // body * 6 + component
+        if (op == IMX_O_BASE_HEADING_PROJ || op == IMX_O_BASE_ANGLE_TO_TARGET) {  // target_pos: x in XC_P0, y, z in XC_RX, XC_RY
+            x[11] = w[ro + IMX_R_P1]; x[12] = w[ro + IMX_R_P2];
+        }
         if (op == IMX_O_HEIGHT_SCAN) {
             x[11] = w[(size_t)p->ray_off + 3 * j]; x[12] = w[(size_t)p->ray_off + 3 * j + 1]; x[13] = w[(size_t)p->ray_off + 3 * j + 2];
         }
@@ -362,7 +384,7 @@ extern "C" int imx_plan_update(imx_plan_t* plan, const int32_t* blob, size_t nwo
     IMX_REQUIRE(q.host.size() == plan->host.size() && q.J == plan->J && q.B == plan->B && q.H == plan->H && q.A == plan->A &&
                     q.D == plan->D && q.R == plan->R && q.NB == plan->NB && q.nterm == plan->nterm && q.nrew_all == plan->nrew_all &&
                     q.nobs == plan->nobs && q.DC == plan->DC && q.DX == plan->DX && q.MS == plan->MS && q.ngroups == plan->ngroups &&
-                    q.scan_stateful == plan->scan_stateful,
+                    q.scan_stateful == plan->scan_stateful && q.term_slots == plan->term_slots,
                 "imx_plan_update: the new plan has a different shape (terms, widths or table sizes changed): create a new plan");
     for (int g = 0; g < q.ngroups; ++g) IMX_REQUIRE(q.gD[g] == plan->gD[g], "imx_plan_update: observation group %d changed width", g);
     int32_t* dev = plan->dev;
@@ -409,5 +431,6 @@ PlanView imx_plan_view(const imx_plan* p) {
     v.ray_max_dist = wf(w[IMX_H_RAY_MAXDIST]);
     v.rinv_dz = 1.0f / v.rdz;
     v.ray_yaw_only = w[IMX_H_RAY_YAW_ONLY];
+    v.term_slots = p->term_slots;
     return v;
 }

@@ -51,6 +51,7 @@ struct imx_plan {
     bool gcorrupt[IMX_MAX_OBS_GROUPS] = {false, false, false, false};
     bool scan_stateful = false;
     bool needs_mesh = false;
+    int term_slots = 0;           // rows of imx_buffers.term_state (stateful reward terms)
 };
 
 // view passed by value to kernels
@@ -68,6 +69,7 @@ struct PlanView {
     int ngroups, gD[IMX_MAX_OBS_GROUPS], gbase[IMX_MAX_OBS_GROUPS], gcorrupt;
     int scan_stateful, scan_substeps;
     float scan_period, scan_dt, drift_lo, drift_hi;
+    int term_slots;
 };
 PlanView imx_plan_view(const imx_plan* p);
 

@@ -120,6 +120,95 @@ IMX_DEV bool spot_active(float cx, float cy, float cz, float vx, float vy, float
     return sqrtf((cx * cx + cy * cy) + cz * cz) > 0.0f || sqrtf(vx * vx + vy * vy) > vth;
 }
 
+// ---- classic/humanoid/mdp (isaaclab_tasks .../classic/humanoid/mdp: Isaac-Ant-v0, Isaac-Humanoid-v0)
+// progress_reward's potential (rewards.py:43-78): -torch.norm(target - root_pos_w, dim=-1) / step_dt in the reference's fp32 sequence --
+// separately rounded squares, (x + y) + z, a correctly rounded sqrtf and a true IEEE division by fp32(step_dt) (the potentials are
+// ~6e4: one ulp is 4e-3, so only the exact sequence reproduces the reward).  __call__ zeroes z first (z_on = false); reset() keeps it
+// (z_on = true).  The ONE formula of the step kernel and of k_term_state_reset.
+IMX_DEV float progress_potential(float tx, float ty, float tz, float px, float py, float pz, float dt, bool z_on) {
+    const float dx = tx - px, dy = ty - py, dz = z_on ? tz - pz : 0.0f;
+    return -sqrtf((dx * dx + dy * dy) + dz * dz) / dt;
+}
+// one angle of euler_xyz_from_quat (utils/math.py:414-444) `% (2 pi)`: atan2 lies in [-pi, pi], where torch.remainder by fp32(2 pi) is
+// x + 2 pi for x < 0 and x itself otherwise (-0 included)
+IMX_DEV float euler_mod_2pi(float s, float c) {
+    const float a = atan2f(s, c);
+    return a < 0.0f ? a + 6.28318530717958647692f : a;
+}
+// atan2(sin(a), cos(a)) of observations.py:26-28,75 for a in (-3 pi, 2 pi): a wrapped into (-pi, pi] without sinf / cosf (exact math;
+// within a few ulps of pi the reference's rounding can land on the other side -- a known deviation, compared modulo 2 pi)
+IMX_DEV float wrap_atan2(float a) {
+    const float PI = 3.14159265358979323846f, TWO_PI = 6.28318530717958647692f;
+    return a > PI ? a - TWO_PI : (a <= -PI ? a + TWO_PI : a);
+}
+// base_heading_proj (observations.py:43-58): quat_rotate(q, FORWARD_VEC_B = (1, 0, 0)) (utils/math.py:583-602, a + b + c; with v = x the
+// cross and dot products reduce to single factors exactly) . normalize(target - pos, z = 0) (math.py:82-92: x / max(||x||, 1e-9))
+IMX_DEV float heading_proj(float qw, float qx, float qy, float qz, float tx, float ty, float px, float py) {
+    const float dx = tx - px, dy = ty - py;
+    const float n = fmaxf(sqrtf(dx * dx + dy * dy), 1.0e-9f);
+    const float ux = dx / n, uy = dy / n;
+    const float hx = (2.0f * (qw * qw) - 1.0f) + (qx * qx) * 2.0f;
+    const float hy = (qz * qw) * 2.0f + (qy * qx) * 2.0f;
+    return hx * ux + hy * uy;  // + hz * 0
+}
+// base_angle_to_target (observations.py:61-77): atan2(to_target y, x) - yaw, wrapped
+IMX_DEV float angle_to_target(float qw, float qx, float qy, float qz, float tx, float ty, float px, float py) {
+    const float walk = atan2f(ty - py, tx - px);
+    const float yaw = euler_mod_2pi(2.0f * (qw * qz + qx * qy), 1.0f - 2.0f * (qy * qy + qz * qz));
+    return wrap_atan2(walk - yaw);
+}
+
+// The reward functions of classic/humanoid/mdp/rewards.py for env ec -- the raw value f.  Evaluated in phase 2 of k_term_rew<true>, next
+// to is_alive: progress_reward needs the reset flag there anyway, and phase 2 holds far fewer live values than the phase-1 switch.
+IMX_DEV float classic_reward(const PlanView& P, const imx_state_t& S, const imx_buffers_t& Bf, const int32_t* __restrict__ r, int op,
+                             int64_t ec, int64_t N) {
+    const int J = P.J;
+    const float p0 = f_of(r[IMX_R_P0]);
+    const float4 q4 = reinterpret_cast<const float4*>(S.root_quat_w)[ec];
+    switch (op) {
+        case IMX_W_UPRIGHT_POSTURE_BONUS: {  // :21-27, up_proj = -projected_gravity_b.z (the phase-0 function, same inputs: same bits)
+            float pgx, pgy, pgz;
+            quat_rotate_inverse(q4.x, q4.y, q4.z, q4.w, P.gx, P.gy, P.gz, pgx, pgy, pgz);
+            return (-pgz > p0) ? 1.0f : 0.0f;
+        }
+        case IMX_W_MOVE_TO_TARGET_BONUS: {  // :30-40
+            const float hp = heading_proj(q4.x, q4.y, q4.z, q4.w, f_of(r[IMX_R_P1]), f_of(r[IMX_R_P2]), S.root_pos_w[ec * 3], S.root_pos_w[ec * 3 + 1]);
+            return hp > p0 ? 1.0f : hp / p0;
+        }
+        case IMX_W_PROGRESS_REWARD: {  // :64-78: potentials - prev_potentials (the caller stores the new potential)
+            const float cur = progress_potential(p0, f_of(r[IMX_R_P1]), 0.0f, S.root_pos_w[ec * 3], S.root_pos_w[ec * 3 + 1], 0.0f, P.step_dt, false);
+            return cur - Bf.term_state[(size_t)r[IMX_R_AUX0] * N + ec];
+        }
+        case IMX_W_JOINT_POS_LIMITS_PENALTY_RATIO: {  // :81-111, every joint; gear table at ids2; p1 = f32(1 - threshold)
+            const int32_t* ids = P.w + r[IMX_R_IDS_OFF];
+            const float* __restrict__ gr = reinterpret_cast<const float*>(P.w + r[IMX_R_IDS2_OFF]);
+            const float p1 = f_of(r[IMX_R_P1]);
+            float acc = 0.0f;  // (sum_ids' left-to-right order, one joint per trip: its 8 loads in flight cost registers the kernel has not)
+            for (int i = 0, n = r[IMX_R_NIDS]; i < n; ++i) {
+                const int j = ids[i];
+                const float2 lim = reinterpret_cast<const float2*>(S.soft_joint_pos_limits)[ec * J + j];
+                const float offset = (lim.x + lim.y) * 0.5f;  // scale_transform (utils/math.py:22-40)
+                const float s = fabsf(2.0f * (S.joint_pos[ec * J + j] - offset) / (lim.y - lim.x));
+                const float v = (s - p0) / p1 * gr[j];
+                acc += (s > p0 ? 1.0f : 0.0f) * v;
+            }
+            return acc;
+        }
+        case IMX_W_POWER_CONSUMPTION: {  // :114-140: |raw action x joint_vel x gear| (env.action_manager.action, A == J)
+            const int32_t* ids = P.w + r[IMX_R_IDS_OFF];
+            const float* __restrict__ gr = reinterpret_cast<const float*>(P.w + r[IMX_R_IDS2_OFF]);
+            const int A = P.A;
+            float acc = 0.0f;
+            for (int i = 0, n = r[IMX_R_NIDS]; i < n; ++i) {
+                const int j = ids[i];
+                acc += fabsf(Bf.action[ec * A + j] * S.joint_vel[ec * J + j] * gr[j]);
+            }
+            return acc;
+        }
+        default: return 0.0f;
+    }
+}
+
 // scratch layout for k_term_rew (4-byte words, nw = number of env groups; sized for the smallest group: ceil(N/16) groups)
 //   [0, nw*KA)               float  per-group partial sums of episode_sums over reset envs
 //   [.., + nw*NT)            int    per-group counts of term_dones over reset envs
@@ -357,6 +446,10 @@ IMX_DEV void step_tail(const PlanView& P, int64_t N, const imx_buffers_t& Bf, co
 // critical path became the SLOWEST item's instruction count -- the force-history terms evaluated 8 padded slots x 4 history slots
 // with a square root each (9.7 us for undesired_contacts against 2 us for a joint sum) -- hence exact trip counts and one square
 // root per body (max_hist_force), and the end of the step moved out of the kernel (step_tail: 4.9 us of fence + ticket).
+// CLASSIC: the plan has reward ops of classic/humanoid/mdp (classic_reward, progress_reward's term_state).  Their code lives in this
+// instantiation only: k_term_rew sits at 128 VGPRs, and any further code in the one shared kernel made it spill (36 to 84 bytes per
+// lane at compile time, one extra case alone enough) -- so every other plan runs the kernel exactly as it was.
+template <bool CLASSIC>
 __global__ void __launch_bounds__(64 * IMX_TR_MAX_WAVES)
 k_term_rew(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, StepScratch sc, float* __restrict__ frame, int G, int defer_tail,
            imx_rollout_slot_t ro) {
@@ -704,11 +797,19 @@ k_term_rew(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, StepScratch s
                 for (int i = 0; i < n; ++i) sum += ((term_bits >> ids[i]) & 1u) ? 1.0f : 0.0f;
                 f = sum * (truncated ? 0.0f : 1.0f);
             }
+            if (CLASSIC && op >= IMX_W_UPRIGHT_POSTURE_BONUS) f = classic_reward(P, S, Bf, r, op, live ? e : min(grp * G, N - 1), N);
             value = f * weight * dt;
             es = es0 + value;
             if (live) Bf.step_reward[(size_t)e * nrew + k] = value / dt;
         }
         // (a skipped term leaves step_reward as it was and still takes part in the reset / log pass, reward_manager.py:100-126,145)
+        if (CLASSIC && r[IMX_R_OP] == IMX_W_PROGRESS_REWARD && live && (weight != 0.0f || reset)) {
+            // potentials after the step: __call__'s value (a zero-weight term is not called), then RewardManager.reset -> progress_reward.
+            // reset (rewards.py:54-60) for a reset env: the 3-D distance of this step's root position
+            const float tx = f_of(r[IMX_R_P0]), ty = f_of(r[IMX_R_P1]), tz = f_of(r[IMX_R_P2]);
+            Bf.term_state[(size_t)r[IMX_R_AUX0] * N + e] =
+                progress_potential(tx, ty, tz, S.root_pos_w[e * 3], S.root_pos_w[e * 3 + 1], S.root_pos_w[e * 3 + 2], dt, reset);
+        }
         s_val[k * 64 + lane] = value;
         if (live && (weight != 0.0f || reset)) Bf.episode_sums[(size_t)k * N + e] = reset ? 0.0f : es;
         // RewardManager.reset log (reward_manager.py:115-121): mean over reset envs of the episodic sum
@@ -968,6 +1069,16 @@ IMX_DEV float obs_plain_value(const PlanView& P, const imx_state_t& S, const imx
         case IMX_O_LAST_ACTION: return Bf.action[e * P.A + j];
         case IMX_O_GENERATED_COMMANDS: return S.command[e * P.CMD + j];
         case IMX_O_EXTERNAL: return S.ext_obs[e * (int64_t)W[IMX_H_NEXT_OBS] + aux + j];
+        // classic/humanoid/mdp/observations.py; target_pos x, y in XC_P0, XC_RX
+        case IMX_O_BASE_YAW_ROLL: {  // :19-30: yaw, roll
+            const float qw = es[12], qx = es[13], qy = es[14], qz = es[15];
+            return wrap_atan2(j == 0 ? euler_mod_2pi(2.0f * (qw * qz + qx * qy), 1.0f - 2.0f * (qy * qy + qz * qz))
+                                     : euler_mod_2pi(2.0f * (qw * qx + qy * qz), 1.0f - 2.0f * (qx * qx + qy * qy)));
+        }
+        case IMX_O_BASE_UP_PROJ: return -es[8];  // :33-40
+        case IMX_O_BASE_HEADING_PROJ: return heading_proj(es[12], es[13], es[14], es[15], f_of(x.b.x), f_of(x.c.w), es[9], es[10]);
+        case IMX_O_BASE_ANGLE_TO_TARGET: return angle_to_target(es[12], es[13], es[14], es[15], f_of(x.b.x), f_of(x.c.w), es[9], es[10]);
+        case IMX_O_BODY_INCOMING_WRENCH: return S.link_incoming_joint_force[e * (int64_t)P.NB * 6 + aux];  // envs/mdp/observations.py:176-185
         default: return 0.0f;
     }
 }
@@ -1375,10 +1486,16 @@ extern "C" int imx_terminations_rewards_rollout(const imx_plan_t* plan, int64_t 
                 break;
             case IMX_W_JOINT_TORQUES_PENALTY: if (need(st->applied_torque, "applied_torque")) return 1; break;
             case IMX_W_JOINT_VELOCITY_PENALTY: if (need(st->joint_vel, "joint_vel")) return 1; break;
+            case IMX_W_MOVE_TO_TARGET_BONUS: case IMX_W_PROGRESS_REWARD: if (need(st->root_pos_w, "root_pos_w")) return 1; break;
+            case IMX_W_JOINT_POS_LIMITS_PENALTY_RATIO: if (need(st->joint_pos, "joint_pos") || need(st->soft_joint_pos_limits, "soft_joint_pos_limits")) return 1; break;
+            case IMX_W_POWER_CONSUMPTION: if (need(st->joint_vel, "joint_vel")) return 1; break;
             default: break;
         }
     }
     if (plan->CMD > 0 && !st->command) IMX_FAIL("command tensor missing");
+    IMX_REQUIRE(plan->term_slots == 0 || bf->term_state,
+                "imx_terminations_rewards: the plan has %d stateful reward terms (progress_reward): term_state (%d, N) is required",
+                plan->term_slots, plan->term_slots);
     IMX_REQUIRE(!plan->scan_stateful || !st->root_pos_w || bf->scan_state,
                 "imx_terminations_rewards: the height scanner has an update period / drift range: scan_state (N,8) is required");
     const int G = step_group_size(N);
@@ -1390,8 +1507,39 @@ extern "C" int imx_terminations_rewards_rollout(const imx_plan_t* plan, int64_t 
     const size_t lds = ((size_t)(plan->nterm > 0 ? plan->nterm : 1) * 64 + 3 * (size_t)(plan->nrew > 0 ? plan->nrew : 1) * 64) * 4;
     // with the root position at hand the kernel also leaves the frame table imx_observations needs (flag 4 there skips k_frame)
     float* frame = st->root_pos_w ? reinterpret_cast<float*>(reinterpret_cast<char*>(bf->scratch) + frame_offset_bytes(plan, N)) : nullptr;
-    hipLaunchKernelGGL(k_term_rew, dim3(grid), dim3(64 * NW), lds, (hipStream_t)stream, imx_plan_view(plan), N, *st, *bf, sc, frame, G,
-                       flags & 1, ro);
+    bool classic = false;
+    for (int k = 0; k < plan->nrew; ++k) classic = classic || w[plan->rew_off + k * IMX_REC_WORDS + IMX_R_OP] >= IMX_W_UPRIGHT_POSTURE_BONUS;
+    if (classic)
+        hipLaunchKernelGGL(k_term_rew<true>, dim3(grid), dim3(64 * NW), lds, (hipStream_t)stream, imx_plan_view(plan), N, *st, *bf, sc, frame,
+                           G, flags & 1, ro);
+    else
+        hipLaunchKernelGGL(k_term_rew<false>, dim3(grid), dim3(64 * NW), lds, (hipStream_t)stream, imx_plan_view(plan), N, *st, *bf, sc, frame,
+                           G, flags & 1, ro);
+    IMX_HIP(hipGetLastError());
+    return 0;
+}
+
+// RewardManager.reset(env_ids) of the stateful reward terms outside a step (env.reset()): progress_reward.reset (rewards.py:54-60), the
+// reset branch of k_term_rew's phase 2 -- same device function, same inputs.  One lane per env, the reward records through the scalar cache.
+__global__ void k_term_state_reset(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, const uint8_t* __restrict__ mask) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N || (mask && !mask[e])) return;
+    for (int k = 0; k < P.nrew; ++k) {
+        const int32_t* r = P.w + P.rew_off + k * IMX_REC_WORDS;
+        if (r[IMX_R_OP] != IMX_W_PROGRESS_REWARD) continue;
+        Bf.term_state[(size_t)r[IMX_R_AUX0] * N + e] = progress_potential(f_of(r[IMX_R_P0]), f_of(r[IMX_R_P1]), f_of(r[IMX_R_P2]), S.root_pos_w[e * 3],
+                                                                          S.root_pos_w[e * 3 + 1], S.root_pos_w[e * 3 + 2], P.step_dt, true);
+    }
+}
+
+extern "C" int imx_term_state_reset(const imx_plan_t* plan, int64_t N, const imx_state_t* st, const imx_buffers_t* bf, const uint8_t* mask_d,
+                                    imx_stream_t stream) {
+    IMX_REQUIRE(plan && st && bf && N > 0, "imx_term_state_reset: null argument");
+    if (plan->term_slots == 0) return 0;
+    IMX_REQUIRE(bf->term_state, "imx_term_state_reset: term_state (%d, N) is required", plan->term_slots);
+    IMX_REQUIRE(st->root_pos_w, "imx_term_state_reset: state tensor 'root_pos_w' is required by progress_reward but missing");
+    hipLaunchKernelGGL(k_term_state_reset, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, imx_plan_view(plan), N, *st, *bf,
+                       mask_d);
     IMX_HIP(hipGetLastError());
     return 0;
 }
@@ -1457,6 +1605,8 @@ extern "C" int imx_observations(const imx_plan_t* plan, int64_t N, const imx_sta
             case IMX_O_LAST_ACTION: p = bf->action; name = "action"; break;
             case IMX_O_GENERATED_COMMANDS: p = st->command; name = "command"; break;
             case IMX_O_EXTERNAL: p = st->ext_obs; name = "ext_obs"; break;
+            case IMX_O_BODY_INCOMING_WRENCH: p = st->link_incoming_joint_force; name = "link_incoming_joint_force"; break;
+            case IMX_O_BASE_HEADING_PROJ: case IMX_O_BASE_ANGLE_TO_TARGET: p = st->root_pos_w; name = "root_pos_w"; break;
             default: break;
         }
         IMX_REQUIRE(p, "state tensor '%s' is required by an observation term but missing", name);

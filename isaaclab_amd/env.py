@@ -661,6 +661,9 @@ class ManagerBasedRLEnv:
         self._scratch = torch.zeros(int(self._lib.imx_plan_scratch_bytes(self._plan_h, N)), dtype=torch.uint8, device=dev)
         # DigitalFilter / Integrator state of observation modifiers (utils/modifiers/modifier.py), zeroed per env on reset by k_obs
         self._mod_state = torch.zeros(N, plan.mod_state_dim, device=dev) if plan.mod_state_dim > 0 else None
+        # per-env state of stateful reward terms (progress_reward.potentials, classic/humanoid/mdp/rewards.py:43-78): one row per term,
+        # carried across steps by the step kernel, set at reset by imx_term_state_reset
+        self._term_state = z(plan.term_slots, N) if plan.term_slots > 0 else None
         self._bufs = ImxBuffers(
             episode_length_buf=self._episode_length_buf.data_ptr(), action=self._action.data_ptr(),
             prev_action=self._prev_action.data_ptr(), processed_action=self._processed_action.data_ptr(),
@@ -670,7 +673,7 @@ class ManagerBasedRLEnv:
             reset_buf=self.reset_buf.data_ptr(), reset_env_ids=self._reset_env_ids.data_ptr(),
             counters=self._counters.data_ptr(), log_out=self._log_out.data_ptr(), obs=self._obs.data_ptr(),
             scratch=self._scratch.data_ptr(), mod_state=self._mod_state.data_ptr() if self._mod_state is not None else None,
-            scan_state=_lib.ptr(self._scan_state), scan_hit_z=_lib.ptr(self._scan_hit_z),
+            scan_state=_lib.ptr(self._scan_state), scan_hit_z=_lib.ptr(self._scan_hit_z), term_state=_lib.ptr(self._term_state),
             **{f"obs_extra{g}": self._obs_groups[g].data_ptr() for g in range(1, len(self._obs_groups))})
         self._state_cache: dict[int, ImxState] = {}
         self._root_cache = None
@@ -1081,6 +1084,15 @@ class ManagerBasedRLEnv:
         f = self.feed
         if self.articulation is not None:  # ArticulationData of the state the env starts from
             self.articulation.update(f.physx("root_transforms"), f.physx("root_velocities"), f["joint_vel"], self.step_dt)
+        if self._term_state is not None:
+            # RewardManager.reset -> progress_reward.reset (classic/humanoid/mdp/rewards.py:54-60): the potentials of the reset envs from
+            # this state's root position -- the device function of the step kernel's reset branch
+            mask = None
+            if env_ids is not None:
+                mask = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
+                mask[ids] = 1
+            check(self._lib.imx_term_state_reset(self._plan_h, self.num_envs, ctypes.byref(self._state()), ctypes.byref(self._bufs),
+                                                 _lib.ptr(mask), _lib.current_stream(self.device)))
         if self.contact_sensor is not None:
             self.contact_sensor.reset(None if env_ids is None else env_ids)
         if self.actuator_net is not None:

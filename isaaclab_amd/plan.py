@@ -31,7 +31,7 @@ H = dict(MAGIC=0, VERSION=1, J=2, B=3, H=4, A=5, D=6, R=7, NTERM=8, NREW=9, NOBS
          STEP_DT=13, TERM_OFF=14, REW_OFF=15, OBS_OFF=16, ACT_OFF=17, TOTAL_WORDS=18, NB=19, GRAV_X=20, GRAV_Y=21,
          GRAV_Z=22, NREW_ALL=23, RAY_OFF=24, RAYDIR_X=25, RAYDIR_Y=26, RAYDIR_Z=27, RAY_MAXDIST=28, MAX_EP_LEN_S=29,
          NEXT_REW=30, NEXT_TERM=31, NEXT_OBS=32, RAY_YAW_ONLY=33, CMD_DIM=34, MOD_STATE=35, NGROUPS=36, GROUP_OFF=37,
-         SCAN_PERIOD=38, SCAN_DT=39, SCAN_SUBSTEPS=40, SCAN_DRIFT_LO=41, SCAN_DRIFT_HI=42, SCAN_STATEFUL=43)
+         SCAN_PERIOD=38, SCAN_DT=39, SCAN_SUBSTEPS=40, SCAN_DRIFT_LO=41, SCAN_DRIFT_HI=42, SCAN_STATEFUL=43, TERM_SLOTS=44)
 R = dict(OP=0, IDS_OFF=1, NIDS=2, IDS2_OFF=3, NIDS2=4, WEIGHT=5, P0=6, P1=7, P2=8, P3=9, OUT=10, DIM=11, FLAGS=12,
          NOISE_LO=13, NOISE_HI=14, CLIP_LO=15, CLIP_HI=16, SCALE=17, AUX0=18, AUX1=19)
 F_NOISE_ADD, F_NOISE_SCALE, F_NOISE_ABS, F_CLIP, F_SCALE, F_QUAT_UNIQUE, F_MODIFIERS, F_SCAN_TWIN = 1, 2, 4, 8, 16, 32, 64, 128
@@ -53,16 +53,20 @@ W_OPS = dict(IS_ALIVE=1, IS_TERMINATED=2, IS_TERMINATED_TERM=3, LIN_VEL_Z_L2=4, 
              BODY_LIN_ACC_L2=29, AIR_TIME_REWARD=30, BASE_ANGULAR_VELOCITY_REWARD=31, BASE_LINEAR_VELOCITY_REWARD=32, GAIT_REWARD=33,
              FOOT_CLEARANCE_REWARD=34, ACTION_SMOOTHNESS_PENALTY=35, AIR_TIME_VARIANCE_PENALTY=36, BASE_MOTION_PENALTY=37,
              BASE_ORIENTATION_PENALTY=38, FOOT_SLIP_PENALTY=39, JOINT_ACCELERATION_PENALTY=40, JOINT_POSITION_PENALTY=41,
-             JOINT_TORQUES_PENALTY=42, JOINT_VELOCITY_PENALTY=43)
+             JOINT_TORQUES_PENALTY=42, JOINT_VELOCITY_PENALTY=43, UPRIGHT_POSTURE_BONUS=44, MOVE_TO_TARGET_BONUS=45, PROGRESS_REWARD=46,
+             JOINT_POS_LIMITS_PENALTY_RATIO=47, POWER_CONSUMPTION=48)
 O_OPS = dict(BASE_POS_Z=1, BASE_LIN_VEL=2, BASE_ANG_VEL=3, PROJECTED_GRAVITY=4, ROOT_POS_W=5, ROOT_QUAT_W=6,
              ROOT_LIN_VEL_W=7, ROOT_ANG_VEL_W=8, JOINT_POS=9, JOINT_POS_REL=10, JOINT_POS_LIMIT_NORMALIZED=11,
-             JOINT_VEL=12, JOINT_VEL_REL=13, HEIGHT_SCAN=14, LAST_ACTION=15, GENERATED_COMMANDS=16, EXTERNAL=17)
+             JOINT_VEL=12, JOINT_VEL_REL=13, HEIGHT_SCAN=14, LAST_ACTION=15, GENERATED_COMMANDS=16, EXTERNAL=17,
+             BASE_YAW_ROLL=18, BASE_UP_PROJ=19, BASE_HEADING_PROJ=20, BASE_ANGLE_TO_TARGET=21, BODY_INCOMING_WRENCH=22)
 A_JOINT_AFFINE = 1
 
 _MDP = "isaaclab.envs.mdp"
 _VEL = "isaaclab_tasks.manager_based.locomotion.velocity.mdp"
 _CART = "isaaclab_tasks.manager_based.classic.cartpole.mdp"
 _SPOT = "isaaclab_tasks.manager_based.locomotion.velocity.config.spot.mdp.rewards"
+_CLASSIC = "isaaclab_tasks.manager_based.classic.humanoid.mdp"  # its own modules; what it re-exports from isaaclab.envs.mdp keeps _MDP names
+_CLASSIC_MODULES = (f"{_CLASSIC}.observations", f"{_CLASSIC}.rewards")
 
 
 def f32(x: float) -> float:
@@ -147,6 +151,7 @@ class Plan:
     obs_dim_total: int = 0  # sum of the group widths (= width of the parity-mode noise feed)
     scan_stateful: bool = False  # the height scanner keeps per-env timestamps / drift (update_period > 0 or a drift range)
     scan_drift_range: tuple[float, float] = (0.0, 0.0)
+    term_slots: int = 0  # rows of per-env reward-term state (imx_buffers.term_state): one per progress_reward term
 
 
 @dataclasses.dataclass
@@ -370,6 +375,70 @@ class PlanCompiler:
         else:
             raise NotImplementedError(f"reward term '{name}': {_SPOT}:{fn} has no fused op")
 
+    # -- the classic tasks' own terms (isaaclab_tasks .../classic/humanoid/mdp: Isaac-Ant-v0, Isaac-Humanoid-v0) ------------------------
+    def gear_ratio_scaled(self, gear_ratio: dict) -> np.ndarray:
+        """``gear_ratio_scaled`` of joint_pos_limits_penalty_ratio / power_consumption.__init__ (rewards.py:87-97): ones, the matched
+        joints set from ``{regex: ratio}`` (fp32 values), divided by the fp32 maximum."""
+        g = np.ones(len(self.joint_names), np.float32)
+        idx, _, vals = resolve_matching_names_values(gear_ratio, self.joint_names)
+        g[idx] = np.asarray(vals, np.float32)
+        return (g / g.max()).astype(np.float32)
+
+    def _classic_reward(self, name: str, fn: str, p: dict, rec: dict, blob: _Blob, A: int, slots: list) -> None:
+        """Fills ``rec`` for one of the five reward terms of classic/humanoid/mdp/rewards.py; ``NotImplementedError`` for anything else of
+        that module.  The two gear-ratio terms read every joint whatever ``asset_cfg`` selects (``asset.data.joint_pos`` unindexed,
+        rewards.py:108-111,140): their id list is all joints, their gear table one float per joint."""
+        all_joints = list(range(len(self.joint_names)))
+
+        def target():
+            t = p["target_pos"]
+            if len(t) != 3:
+                raise ValueError(f"reward term '{name}': target_pos must have 3 components, got {t}")
+            return [f32(t[0]), f32(t[1]), f32(t[2])]
+
+        if fn == "upright_posture_bonus":  # :21-27
+            rec.update(op=W_OPS["UPRIGHT_POSTURE_BONUS"], p0=f32(p["threshold"]))
+        elif fn == "move_to_target_bonus":  # :30-40 (base_heading_proj ignores the target's z)
+            t = target()
+            rec.update(op=W_OPS["MOVE_TO_TARGET_BONUS"], p0=f32(p["threshold"]), p1=t[0], p2=t[1])
+        elif fn == "progress_reward":  # :43-78: ManagerTermBase with per-env potentials -> one term_state slot
+            t = target()
+            rec.update(op=W_OPS["PROGRESS_REWARD"], p0=t[0], p1=t[1], p2=t[2], aux0=len(slots))
+            slots.append(name)
+        elif fn in ("joint_pos_limits_penalty_ratio", "power_consumption"):  # :81-140
+            self.resolve_ids(p.get("asset_cfg"), "joint")  # the cfg must still resolve though the function reads every joint
+            gr = self.gear_ratio_scaled(p["gear_ratio"])
+            rec.update(ids_off=blob.ints(all_joints), nids=len(all_joints), ids2_off=blob.floats(gr.tolist()), nids2=len(all_joints))
+            if fn == "power_consumption":
+                if A != len(all_joints):  # (N, A) actions times (N, J) joint velocities
+                    raise ValueError(f"reward term '{name}': power_consumption multiplies the {A} actions with the {len(all_joints)} joint velocities")
+                rec["op"] = W_OPS["POWER_CONSUMPTION"]
+            else:
+                th = float(p["threshold"])
+                rec.update(op=W_OPS["JOINT_POS_LIMITS_PENALTY_RATIO"], p0=f32(th), p1=f32(1.0 - th))  # (1 - threshold): a Python double
+        else:
+            raise NotImplementedError(f"reward term '{name}': {_CLASSIC}.rewards:{fn} has no fused op")
+
+    def _classic_obs(self, name: str, fn: str, p: dict, rec: dict) -> int:
+        """The four observation functions of classic/humanoid/mdp/observations.py -> their width; ``NotImplementedError`` otherwise."""
+        def target():
+            t = p["target_pos"]
+            if len(t) != 3:
+                raise ValueError(f"observation term '{name}': target_pos must have 3 components, got {t}")
+            rec.update(p0=f32(t[0]), p1=f32(t[1]), p2=f32(t[2]))
+
+        if fn == "base_yaw_roll":  # :19-30
+            rec["op"] = O_OPS["BASE_YAW_ROLL"]
+            return 2
+        if fn == "base_up_proj":  # :33-40
+            rec["op"] = O_OPS["BASE_UP_PROJ"]
+            return 1
+        if fn in ("base_heading_proj", "base_angle_to_target"):  # :43-77
+            rec["op"] = O_OPS["BASE_HEADING_PROJ" if fn == "base_heading_proj" else "BASE_ANGLE_TO_TARGET"]
+            target()
+            return 1
+        raise NotImplementedError(f"observation term '{name}': {_CLASSIC}.observations:{fn} has no fused op")
+
     # -- compile ------------------------------------------------------------------------------------------------
     def compile(self) -> Plan:
         cfg, robot = self.cfg, self.robot
@@ -472,6 +541,8 @@ class PlanCompiler:
             rec = dict(out=k, weight=1 if tcfg.get("time_out") else 0)
             mod, short = _short(fn)
             known = True
+            if mod in _CLASSIC_MODULES:
+                raise NotImplementedError(f"termination term '{name}': {fn} has no fused op")
             if fn == f"{_MDP}.terminations:time_out":
                 rec["op"] = T_OPS["TIME_OUT"]
             elif fn == f"{_MDP}.terminations:illegal_contact":
@@ -520,6 +591,7 @@ class PlanCompiler:
         rew_terms: list[Term] = []
         rew_recs: list[list[int]] = []
         n_ext_rew = 0
+        term_slots: list[str] = []  # stateful reward terms, one term_state row each
         for name, tcfg in (cfg.get("rewards") or {}).items():
             if tcfg is None:
                 continue
@@ -591,6 +663,8 @@ class PlanCompiler:
                 rec.update(op=W_OPS["BODY_LIN_ACC_L2"], ids_off=blob.ints(ids), nids=len(ids))
             elif _short(fn)[0] == _SPOT:
                 self._spot_reward(name, _short(fn)[1], p, rec, blob)
+            elif _short(fn)[0] in _CLASSIC_MODULES:
+                self._classic_reward(name, _short(fn)[1], p, rec, blob, A, term_slots)
             else:
                 known = False
                 rec.update(op=W_OPS["EXTERNAL"], aux0=n_ext_rew)
@@ -686,6 +760,12 @@ class PlanCompiler:
                     rec["op"], dim = O_OPS["LAST_ACTION"], A
                 elif fn == f"{_MDP}.observations:generated_commands":
                     rec["op"], dim = O_OPS["GENERATED_COMMANDS"], 3
+                elif fn == f"{_MDP}.observations:body_incoming_wrench":  # observations.py:176-185: 6 columns per body, body_ids order
+                    ids = self.resolve_ids(p.get("asset_cfg"), "body")
+                    dim = 6 * len(ids)
+                    rec.update(op=O_OPS["BODY_INCOMING_WRENCH"], ids_off=blob.ints(ids), nids=len(ids))
+                elif _short(fn)[0] in _CLASSIC_MODULES:
+                    dim = self._classic_obs(name, _short(fn)[1], p, rec)
                 elif fn == f"{_MDP}.observations:height_scan":
                     if scanner is None:
                         raise ValueError(f"Error while parsing '{name}:sensor_cfg'. The scene entity 'height_scanner' does not exist.")
@@ -794,7 +874,7 @@ class PlanCompiler:
             "NEXT_REW": n_ext_rew, "NEXT_TERM": n_ext_term, "NEXT_OBS": n_ext_obs,
             "RAY_YAW_ONLY": 1 if (scanner and scanner.get("attach_yaw_only")) else 0, "CMD_DIM": 3,
             "MOD_STATE": mod_state, "NGROUPS": len(groups), "GROUP_OFF": group_off, "SCAN_SUBSTEPS": int(cfg["decimation"]),
-            "SCAN_STATEFUL": int(scan_stateful),
+            "SCAN_STATEFUL": int(scan_stateful), "TERM_SLOTS": len(term_slots),
         }
         for k, v in hdr.items():
             w[H[k]] = int(v)
@@ -813,7 +893,7 @@ class PlanCompiler:
                     action_terms=action_terms, enable_corruption=corruption, ray_starts_local=ray_local,
                     ray_direction=ray_dir, ray_max_distance=ray_max, scanner_cfg=scanner, n_ext_rew=n_ext_rew,
                     n_ext_term=n_ext_term, n_ext_obs=n_ext_obs, gravity_dir=tuple(float(x) for x in gdir),
-                    mod_state_dim=mod_state)
+                    mod_state_dim=mod_state, term_slots=len(term_slots))
 
 
 def compile_plan(env_cfg: Any, robot: RobotSpec) -> Plan:

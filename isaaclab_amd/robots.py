@@ -3,7 +3,8 @@
 The reference obtains joint/body names and default joint positions from PhysX after loading the robot USD
 (``Articulation._initialize_impl``); neither PhysX nor the USD files exist here, so the *names* ship as data.
 Defaults follow the asset cfgs (reference ``source/isaaclab_assets/isaaclab_assets/robots/anymal.py:112-121``,
-``unitree.py:290-307`` (G1), ``spot.py:151-160``, ``cartpole.py``).  The G1 and Spot joint / body orders are synthetic
+``unitree.py:290-307`` (G1), ``spot.py:151-160``, ``cartpole.py``, ``ant.py:33-42``, the humanoid task's init state).  The G1, Spot,
+Ant and Humanoid joint / body orders are synthetic
 breadth-first orders of the names the task cfgs' regexes refer to (the true PhysX order is not recoverable offline); term
 semantics do not depend on them because every index list is resolved by name through :func:`resolve_matching_names`.
 """
@@ -159,4 +160,35 @@ SPOT = RobotSpec(
     default_root_height=0.5,
 )
 
-ROBOTS = {r.name: r for r in (ANYMAL_C, G1, CARTPOLE, SPOT)}
+# The MuJoCo-style Ant and Humanoid of the classic tasks (isaaclab_assets/robots/ant.py, classic/humanoid/humanoid_env_cfg.py).  Names
+# are the ones the task cfgs' regexes refer to, in a synthetic breadth-first order (the PhysX order of the USD files is not recoverable
+# offline).  ``joint_pos_limits`` is a round +-1 rad here; the terms that read limits (joint_pos_limit_normalized,
+# joint_pos_limits_penalty_ratio) see the state feed's soft limits, default +- 0.45 rad with positions default + U(-0.5, 0.5): about a
+# fifth of the joints then lie beyond the 0.98 / 0.99 thresholds of the two cfgs.
+_ANT_LEGS = ("front_left", "front_right", "left_back", "right_back")
+
+ANT = RobotSpec(
+    name="ant",
+    # hips (`*_leg`), then ankles (`*_foot`); bodies: the torso, then the four legs, then the four feet (ant_env_cfg.py:86-92)
+    joint_names=[f"{leg}_{j}" for j in ("leg", "foot") for leg in _ANT_LEGS],
+    body_names=["torso"] + [f"{leg}_{b}" for b in ("leg", "foot") for leg in _ANT_LEGS],
+    default_joint_pos={".*_leg": 0.0, "front_left_foot": 0.785398, "front_right_foot": -0.785398, "left_back_foot": -0.785398,
+                       "right_back_foot": 0.785398},
+    default_root_height=0.5,
+    joint_pos_limits=(-1.0, 1.0),
+)
+
+HUMANOID = RobotSpec(
+    name="humanoid",
+    # the 21 joints the scale / gear-ratio regexes of humanoid_env_cfg.py match exactly once each, parent links first
+    joint_names=["lower_waist:0", "lower_waist:1", "right_upper_arm:0", "right_upper_arm:2", "left_upper_arm:0", "left_upper_arm:2",
+                 "pelvis", "right_lower_arm", "left_lower_arm", "right_thigh:0", "right_thigh:1", "right_thigh:2", "left_thigh:0",
+                 "left_thigh:1", "left_thigh:2", "right_shin", "left_shin", "right_foot:0", "right_foot:1", "left_foot:0", "left_foot:1"],
+    body_names=["torso", "head", "lower_waist", "right_upper_arm", "left_upper_arm", "pelvis", "right_lower_arm", "left_lower_arm",
+                "right_thigh", "left_thigh", "right_hand", "left_hand", "right_shin", "left_shin", "right_foot", "left_foot"],
+    default_joint_pos={".*": 0.0},
+    default_root_height=1.34,
+    joint_pos_limits=(-1.0, 1.0),
+)
+
+ROBOTS = {r.name: r for r in (ANYMAL_C, G1, CARTPOLE, SPOT, ANT, HUMANOID)}

@@ -22,9 +22,10 @@ DYNAMIC = (
     "body_lin_vel_w", "command", "net_forces_w_history",
     "last_air_time", "current_air_time", "current_contact_time", "last_contact_time",
 )
-# further per-step tensors only a few optional terms read (body_lin_acc_l2, command_resample, foot_clearance_reward): drawn from their
-# own generators so that the tensors above are unchanged by their presence; recorded fixtures carry them only when their cfg needs them
-EXTRA = ("body_lin_acc_w", "command_time_left", "command_counter", "body_pos_w")
+# further per-step tensors only a few optional terms read (body_lin_acc_l2, command_resample, foot_clearance_reward, body_incoming_wrench):
+# drawn from their own generators so that the tensors above are unchanged by their presence; recorded fixtures carry them only when their
+# cfg needs them
+EXTRA = ("body_lin_acc_w", "command_time_left", "command_counter", "body_pos_w", "link_incoming_joint_force")
 # tensors fixed for the lifetime of the scene
 STATIC = ("default_joint_pos", "default_joint_vel", "soft_joint_pos_limits", "soft_joint_vel_limits", "env_origins")
 
@@ -152,6 +153,15 @@ def generate_body_pos(robot: RobotSpec, num_envs: int, gen: torch.Generator) -> 
     return torch.cat([xy, z], dim=-1).contiguous()
 
 
+def generate_link_wrench(robot: RobotSpec, num_envs: int, gen: torch.Generator) -> torch.Tensor:
+    """``root_physx_view.get_link_incoming_joint_force()`` (N, B, 6): the wrench each body's incoming joint transmits, force N(0, 20) N
+    then torque N(0, 2) N m (what body_incoming_wrench observes)."""
+    N, B = num_envs, robot.num_bodies
+    force = torch.randn(N, B, 3, generator=gen) * 20.0
+    torque = torch.randn(N, B, 3, generator=gen) * 2.0
+    return torch.cat([force, torque], dim=-1).contiguous()
+
+
 class StateFeed:
     """``S`` snapshots of the post-physics state held on ``device``; ``advance()`` moves to the next one.
 
@@ -172,9 +182,11 @@ class StateFeed:
         self._stack: dict[str, torch.Tensor] = {}
         gen_x = torch.Generator().manual_seed(seed + 0x5EED)
         gen_p = torch.Generator().manual_seed(seed + 0xB0D7)
+        gen_w = torch.Generator().manual_seed(seed + 0x1F0C)
         for sn in snaps:
             sn.update(generate_extras(robot, num_envs, gen_x))
             sn["body_pos_w"] = generate_body_pos(robot, num_envs, gen_p)
+            sn["link_incoming_joint_force"] = generate_link_wrench(robot, num_envs, gen_w)
         for name in DYNAMIC + EXTRA:
             self._stack[name] = torch.stack([s[name] for s in snaps], dim=0).to(self.device).contiguous()
         # every snapshot keeps the same origins/defaults; root xy of later snapshots re-uses snapshot-0 origins

@@ -163,7 +163,14 @@ enum imx_rew_op {
                                                   read before the update) */
     IMX_W_JOINT_POS_LIMITS_PENALTY_RATIO, /* :81-111 ids = all joints; ids2 = (J) f32 gear_ratio_scaled; p0 = threshold,
                                                   p1 = f32(1 - threshold) (the Python double) */
-    IMX_W_POWER_CONSUMPTION           /* :114-140 ids = all joints; ids2 = (J) f32 gear_ratio_scaled; reads buf.action (raw, A == J) */
+    IMX_W_POWER_CONSUMPTION,          /* :114-140 ids = all joints; ids2 = (J) f32 gear_ratio_scaled; reads buf.action (raw, A == J) */
+    /* isaaclab_tasks .../manipulation/reach/mdp/rewards.py (Isaac-Reach-Franka-v0, Isaac-Reach-UR10-v0); ids = the ONE asset body
+       (asset_cfg.body_ids[0]); command = (N, 7) pose in the base frame (CMD == 7); des_pos_w = root_pos_w + quat_apply(root_quat_w,
+       cmd[:3]) (combine_frame_transforms, utils/math.py:750-786 -> quat_apply :546-566) */
+    IMX_W_POSITION_COMMAND_ERROR,     /* :19-33  ||body_pos_w[:, id] - des_pos_w|| */
+    IMX_W_POSITION_COMMAND_ERROR_TANH,/* :36-53  1 - tanh(||body_pos_w[:, id] - des_pos_w|| / p0), p0 = std */
+    IMX_W_ORIENTATION_COMMAND_ERROR   /* :56-72  quat_error_magnitude(body_quat_w[:, id], quat_mul(root_quat_w, cmd[3:7])) (math.py:678-690:
+                                                  ||axis_angle_from_quat(quat_mul(q1, quat_conjugate(q2)))||, :646-675) */
 };
 
 /* observation ops -- envs/mdp/observations.py */
@@ -229,6 +236,8 @@ typedef struct imx_state {
     const float* last_contact_time;     /* (N,B) ContactSensorData.last_contact_time, or NULL unless a term reads it */
     const float* link_incoming_joint_force; /* (N,NB,6) root_physx_view.get_link_incoming_joint_force() (force, torque), or NULL
                                                unless a term reads it */
+    const float* body_quat_w;           /* (N,NB,4) ArticulationData.body_quat_w w,x,y,z = body_state_w[..., 3:7] (articulation_data.py:776-782), or NULL
+                                           unless a term reads it (orientation_command_error) */
 } imx_state_t;
 
 /* ---- manager state + outputs (caller-owned, persistent across steps) ------------------------------------------ */

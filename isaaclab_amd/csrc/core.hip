@@ -111,7 +111,7 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
     for (int k = 0; k < p->nrew; ++k) {
         const int32_t* r = &w[p->rew_off + k * IMX_REC_WORDS];
         const int op = r[IMX_R_OP];
-        IMX_REQUIRE(op >= IMX_W_IS_ALIVE && op <= IMX_W_POWER_CONSUMPTION, "plan: unknown reward op %d", op);
+        IMX_REQUIRE(op >= IMX_W_IS_ALIVE && op <= IMX_W_ORIENTATION_COMMAND_ERROR, "plan: unknown reward op %d", op);
         IMX_REQUIRE(r[IMX_R_OUT] == k, "plan: reward record %d has index %d", k, r[IMX_R_OUT]);
         int limit = p->J;
         const char* what = "joint";
@@ -123,7 +123,8 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
         } else if (op == IMX_W_IS_TERMINATED_TERM) {
             limit = p->nterm;
             what = "termination-term";
-        } else if (op == IMX_W_BODY_LIN_ACC_L2 || op == IMX_W_FOOT_CLEARANCE_REWARD) {
+        } else if (op == IMX_W_BODY_LIN_ACC_L2 || op == IMX_W_FOOT_CLEARANCE_REWARD || op == IMX_W_POSITION_COMMAND_ERROR ||
+                   op == IMX_W_POSITION_COMMAND_ERROR_TANH || op == IMX_W_ORIENTATION_COMMAND_ERROR) {
             limit = p->NB;
             what = "asset body";
         }
@@ -131,6 +132,9 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
         if (op == IMX_W_AIR_TIME_REWARD || op == IMX_W_GAIT_REWARD)
             IMX_REQUIRE(r[IMX_R_NIDS] == 4, "plan: reward record %d (op %d) needs exactly 4 feet", k, op);
         if (op == IMX_W_AIR_TIME_VARIANCE_PENALTY) IMX_REQUIRE(r[IMX_R_NIDS] > 0, "plan: air_time_variance_penalty without feet");
+        if (op == IMX_W_POSITION_COMMAND_ERROR || op == IMX_W_POSITION_COMMAND_ERROR_TANH || op == IMX_W_ORIENTATION_COMMAND_ERROR)
+            IMX_REQUIRE(r[IMX_R_NIDS] == 1 && p->CMD == 7, "plan: reward record %d (op %d) needs one body and a 7-wide pose command (CMD=%d)",
+                        k, op, p->CMD);
         if (op == IMX_W_PROGRESS_REWARD)
             IMX_REQUIRE(r[IMX_R_AUX0] >= 0 && r[IMX_R_AUX0] < p->term_slots, "plan: reward record %d: state slot %d outside [0, %d)", k,
                         r[IMX_R_AUX0], p->term_slots);

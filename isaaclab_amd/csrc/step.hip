@@ -158,8 +158,9 @@ IMX_DEV float angle_to_target(float qw, float qx, float qy, float qz, float tx, 
     return wrap_atan2(walk - yaw);
 }
 
-// The reward functions of classic/humanoid/mdp/rewards.py for env ec -- the raw value f.  Evaluated in phase 2 of k_term_rew<true>, next
-// to is_alive: progress_reward needs the reset flag there anyway, and phase 2 holds far fewer live values than the phase-1 switch.
+// The reward functions of classic/humanoid/mdp/rewards.py for env ec -- the raw value f.  Evaluated in phase 2 of
+// k_term_rew<true, false>, next to is_alive: progress_reward needs the reset flag there anyway, and phase 2 holds far fewer live values
+// than the phase-1 switch.
 IMX_DEV float classic_reward(const PlanView& P, const imx_state_t& S, const imx_buffers_t& Bf, const int32_t* __restrict__ r, int op,
                              int64_t ec, int64_t N) {
     const int J = P.J;
@@ -207,6 +208,53 @@ IMX_DEV float classic_reward(const PlanView& P, const imx_state_t& S, const imx_
         }
         default: return 0.0f;
     }
+}
+
+// ---- manipulation/reach/mdp (isaaclab_tasks .../manipulation/reach/mdp: Isaac-Reach-Franka-v0, Isaac-Reach-UR10-v0)
+// quat_mul (utils/math.py:464-500): the reference's eight-product form with its association, quaternions w, x, y, z in .x .. .w
+IMX_DEV float4 quat_mul_ref(float4 a, float4 b) {
+    const float w1 = a.x, x1 = a.y, y1 = a.z, z1 = a.w, w2 = b.x, x2 = b.y, y2 = b.z, z2 = b.w;
+    const float ww = (z1 + x1) * (x2 + y2);
+    const float yy = (w1 - y1) * (w2 + z2);
+    const float zz = (w1 + y1) * (w2 - z2);
+    const float xx = ww + yy + zz;
+    const float qq = 0.5f * (xx + (z1 - x1) * (x2 - y2));
+    return make_float4(qq - ww + (z1 - y1) * (y2 - z2), qq - xx + (x1 + w1) * (x2 + w2), qq - yy + (w1 - x1) * (y2 + z2),
+                       qq - zz + (z1 + y1) * (w2 - x2));
+}
+// quat_error_magnitude(q1, q2) (utils/math.py:678-690) = ||axis_angle_from_quat(quat_mul(q1, quat_conjugate(q2)))||, axis_angle_from_quat
+// (:646-675) step by step: the w < 0 flip (q * (1 - 2 (w < 0))), half = atan2(||xyz||, w), angle = 2 half, the |angle| <= 1e-6 Taylor
+// branch 0.5 - angle^2 / 48, then xyz / that factor and its norm
+IMX_DEV float quat_error_magnitude(float4 q1, float4 q2) {
+    const float4 d = quat_mul_ref(q1, make_float4(q2.x, -q2.y, -q2.z, -q2.w));
+    const float sg = 1.0f - 2.0f * (d.x < 0.0f ? 1.0f : 0.0f);
+    const float w = d.x * sg, x = d.y * sg, y = d.z * sg, z = d.w * sg;
+    const float mag = sqrtf((x * x + y * y) + z * z);
+    const float half = atan2f(mag, w);
+    const float angle = 2.0f * half;
+    const float s = fabsf(angle) > 1.0e-6f ? sinf(half) / angle : 0.5f - angle * angle / 48.0f;
+    const float ax = x / s, ay = y / s, az = z / s;
+    return sqrtf((ax * ax + ay * ay) + az * az);
+}
+// The reward functions of manipulation/reach/mdp/rewards.py for env ec -- the raw value f.  Evaluated in phase 2 of k_term_rew<false,
+// true> (the classic terms' place: phase 2 holds far fewer live values than the phase-1 switch).  ids[0] = asset_cfg.body_ids[0].
+IMX_DEV float reach_reward(const PlanView& P, const imx_state_t& S, const int32_t* __restrict__ r, int op, int64_t ec) {
+    const int b = P.w[r[IMX_R_IDS_OFF]];
+    const float4 rq = reinterpret_cast<const float4*>(S.root_quat_w)[ec];
+    const float* __restrict__ cmd = S.command + ec * P.CMD;
+    if (op == IMX_W_ORIENTATION_COMMAND_ERROR) {  // :56-72: des_quat_w = quat_mul(root_quat_w, cmd[3:7])
+        const float4 des = quat_mul_ref(rq, make_float4(cmd[3], cmd[4], cmd[5], cmd[6]));
+        const float4 cur = reinterpret_cast<const float4*>(S.body_quat_w)[ec * P.NB + b];
+        return quat_error_magnitude(cur, des);
+    }
+    // :19-53: des_pos_w = root_pos_w + quat_apply(root_quat_w, cmd[:3]) (combine_frame_transforms: t01 + quat_apply(q01, t12))
+    float ox, oy, oz;
+    quat_apply(rq.x, rq.y, rq.z, rq.w, cmd[0], cmd[1], cmd[2], ox, oy, oz);
+    const float dx = S.body_pos_w[(ec * P.NB + b) * 3] - (S.root_pos_w[ec * 3] + ox);
+    const float dy = S.body_pos_w[(ec * P.NB + b) * 3 + 1] - (S.root_pos_w[ec * 3 + 1] + oy);
+    const float dz = S.body_pos_w[(ec * P.NB + b) * 3 + 2] - (S.root_pos_w[ec * 3 + 2] + oz);
+    const float d = sqrtf((dx * dx + dy * dy) + dz * dz);
+    return op == IMX_W_POSITION_COMMAND_ERROR_TANH ? 1.0f - tanhf(d / f_of(r[IMX_R_P0])) : d;
 }
 
 // scratch layout for k_term_rew (4-byte words, nw = number of env groups; sized for the smallest group: ceil(N/16) groups)
@@ -449,7 +497,8 @@ IMX_DEV void step_tail(const PlanView& P, int64_t N, const imx_buffers_t& Bf, co
 // CLASSIC: the plan has reward ops of classic/humanoid/mdp (classic_reward, progress_reward's term_state).  Their code lives in this
 // instantiation only: k_term_rew sits at 128 VGPRs, and any further code in the one shared kernel made it spill (36 to 84 bytes per
 // lane at compile time, one extra case alone enough) -- so every other plan runs the kernel exactly as it was.
-template <bool CLASSIC>
+// REACH: the plan has reward ops of manipulation/reach/mdp (reach_reward), evaluated in a third instantiation for the same reason.
+template <bool CLASSIC, bool REACH>
 __global__ void __launch_bounds__(64 * IMX_TR_MAX_WAVES)
 k_term_rew(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, StepScratch sc, float* __restrict__ frame, int G, int defer_tail,
            imx_rollout_slot_t ro) {
@@ -798,6 +847,7 @@ k_term_rew(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, StepScratch s
                 f = sum * (truncated ? 0.0f : 1.0f);
             }
             if (CLASSIC && op >= IMX_W_UPRIGHT_POSTURE_BONUS) f = classic_reward(P, S, Bf, r, op, live ? e : min(grp * G, N - 1), N);
+            if (REACH && op >= IMX_W_POSITION_COMMAND_ERROR) f = reach_reward(P, S, r, op, live ? e : min(grp * G, N - 1));
             value = f * weight * dt;
             es = es0 + value;
             if (live) Bf.step_reward[(size_t)e * nrew + k] = value / dt;
@@ -1489,6 +1539,10 @@ extern "C" int imx_terminations_rewards_rollout(const imx_plan_t* plan, int64_t 
             case IMX_W_MOVE_TO_TARGET_BONUS: case IMX_W_PROGRESS_REWARD: if (need(st->root_pos_w, "root_pos_w")) return 1; break;
             case IMX_W_JOINT_POS_LIMITS_PENALTY_RATIO: if (need(st->joint_pos, "joint_pos") || need(st->soft_joint_pos_limits, "soft_joint_pos_limits")) return 1; break;
             case IMX_W_POWER_CONSUMPTION: if (need(st->joint_vel, "joint_vel")) return 1; break;
+            case IMX_W_POSITION_COMMAND_ERROR: case IMX_W_POSITION_COMMAND_ERROR_TANH:
+                if (need(st->command, "command") || need(st->root_pos_w, "root_pos_w") || need(st->body_pos_w, "body_pos_w")) return 1;
+                break;
+            case IMX_W_ORIENTATION_COMMAND_ERROR: if (need(st->command, "command") || need(st->body_quat_w, "body_quat_w")) return 1; break;
             default: break;
         }
     }
@@ -1507,14 +1561,22 @@ extern "C" int imx_terminations_rewards_rollout(const imx_plan_t* plan, int64_t 
     const size_t lds = ((size_t)(plan->nterm > 0 ? plan->nterm : 1) * 64 + 3 * (size_t)(plan->nrew > 0 ? plan->nrew : 1) * 64) * 4;
     // with the root position at hand the kernel also leaves the frame table imx_observations needs (flag 4 there skips k_frame)
     float* frame = st->root_pos_w ? reinterpret_cast<float*>(reinterpret_cast<char*>(bf->scratch) + frame_offset_bytes(plan, N)) : nullptr;
-    bool classic = false;
-    for (int k = 0; k < plan->nrew; ++k) classic = classic || w[plan->rew_off + k * IMX_REC_WORDS + IMX_R_OP] >= IMX_W_UPRIGHT_POSTURE_BONUS;
+    bool classic = false, reach = false;
+    for (int k = 0; k < plan->nrew; ++k) {
+        const int op = w[plan->rew_off + k * IMX_REC_WORDS + IMX_R_OP];
+        classic = classic || (op >= IMX_W_UPRIGHT_POSTURE_BONUS && op <= IMX_W_POWER_CONSUMPTION);
+        reach = reach || op >= IMX_W_POSITION_COMMAND_ERROR;
+    }
+    IMX_REQUIRE(!(classic && reach), "imx_terminations_rewards: a plan with both classic/humanoid and manipulation/reach reward ops is not supported");
     if (classic)
-        hipLaunchKernelGGL(k_term_rew<true>, dim3(grid), dim3(64 * NW), lds, (hipStream_t)stream, imx_plan_view(plan), N, *st, *bf, sc, frame,
-                           G, flags & 1, ro);
+        hipLaunchKernelGGL((k_term_rew<true, false>), dim3(grid), dim3(64 * NW), lds, (hipStream_t)stream, imx_plan_view(plan), N, *st, *bf, sc,
+                           frame, G, flags & 1, ro);
+    else if (reach)
+        hipLaunchKernelGGL((k_term_rew<false, true>), dim3(grid), dim3(64 * NW), lds, (hipStream_t)stream, imx_plan_view(plan), N, *st, *bf, sc,
+                           frame, G, flags & 1, ro);
     else
-        hipLaunchKernelGGL(k_term_rew<false>, dim3(grid), dim3(64 * NW), lds, (hipStream_t)stream, imx_plan_view(plan), N, *st, *bf, sc, frame,
-                           G, flags & 1, ro);
+        hipLaunchKernelGGL((k_term_rew<false, false>), dim3(grid), dim3(64 * NW), lds, (hipStream_t)stream, imx_plan_view(plan), N, *st, *bf, sc,
+                           frame, G, flags & 1, ro);
     IMX_HIP(hipGetLastError());
     return 0;
 }

@@ -691,7 +691,14 @@ class ManagerBasedRLEnv:
             cmds = (env_dict.get("commands") or {})
             if not cmds:
                 raise ValueError("use_command_term=True but the env cfg has no command terms")
+            if plan.cmd_dim != 3:
+                raise NotImplementedError(f"use_command_term=True: this cfg's command is {plan.cmd_dim} wide (a UniformPoseCommand), which has "
+                                          "no fused producer yet; the env's own command term is a UniformVelocityCommand.  Take the "
+                                          "pose command from the state feed")
             self.command_term = UniformVelocityCommand(next(iter(cmds.values())), N, plan.step_dt, self.device, seed=noise_seed)
+        elif "command" in state_feed.names() and state_feed["command"].shape[-1] != plan.cmd_dim:
+            raise ValueError(f"the state feed's command is {state_feed['command'].shape[-1]} wide, the plan's {plan.cmd_dim} "
+                             f"(robot {state_feed.robot.name}: command_dim {state_feed.robot.command_dim})")
         self.contact_sensor = None
         if use_contact_sensor:
             from .producers import ContactSensorState

@@ -54,7 +54,8 @@ W_OPS = dict(IS_ALIVE=1, IS_TERMINATED=2, IS_TERMINATED_TERM=3, LIN_VEL_Z_L2=4, 
              FOOT_CLEARANCE_REWARD=34, ACTION_SMOOTHNESS_PENALTY=35, AIR_TIME_VARIANCE_PENALTY=36, BASE_MOTION_PENALTY=37,
              BASE_ORIENTATION_PENALTY=38, FOOT_SLIP_PENALTY=39, JOINT_ACCELERATION_PENALTY=40, JOINT_POSITION_PENALTY=41,
              JOINT_TORQUES_PENALTY=42, JOINT_VELOCITY_PENALTY=43, UPRIGHT_POSTURE_BONUS=44, MOVE_TO_TARGET_BONUS=45, PROGRESS_REWARD=46,
-             JOINT_POS_LIMITS_PENALTY_RATIO=47, POWER_CONSUMPTION=48)
+             JOINT_POS_LIMITS_PENALTY_RATIO=47, POWER_CONSUMPTION=48, POSITION_COMMAND_ERROR=49, POSITION_COMMAND_ERROR_TANH=50,
+             ORIENTATION_COMMAND_ERROR=51)
 O_OPS = dict(BASE_POS_Z=1, BASE_LIN_VEL=2, BASE_ANG_VEL=3, PROJECTED_GRAVITY=4, ROOT_POS_W=5, ROOT_QUAT_W=6,
              ROOT_LIN_VEL_W=7, ROOT_ANG_VEL_W=8, JOINT_POS=9, JOINT_POS_REL=10, JOINT_POS_LIMIT_NORMALIZED=11,
              JOINT_VEL=12, JOINT_VEL_REL=13, HEIGHT_SCAN=14, LAST_ACTION=15, GENERATED_COMMANDS=16, EXTERNAL=17,
@@ -67,6 +68,14 @@ _CART = "isaaclab_tasks.manager_based.classic.cartpole.mdp"
 _SPOT = "isaaclab_tasks.manager_based.locomotion.velocity.config.spot.mdp.rewards"
 _CLASSIC = "isaaclab_tasks.manager_based.classic.humanoid.mdp"  # its own modules; what it re-exports from isaaclab.envs.mdp keeps _MDP names
 _CLASSIC_MODULES = (f"{_CLASSIC}.observations", f"{_CLASSIC}.rewards")
+_REACH = "isaaclab_tasks.manager_based.manipulation.reach.mdp.rewards"
+_POSE_COMMAND = "isaaclab.envs.mdp.commands.pose_command:UniformPoseCommand"  # command = (N, 7): position + quaternion, base frame
+
+
+def command_width(command_cfg: dict | None) -> int:
+    """Width of a command term's ``command``: 7 for a ``UniformPoseCommand`` (pose_command.py:71-72), 3 for any other (the base velocity
+    command every other task uses)."""
+    return 7 if command_cfg is not None and func_name(command_cfg.get("class_type")) == _POSE_COMMAND else 3
 
 
 def f32(x: float) -> float:
@@ -439,10 +448,30 @@ class PlanCompiler:
             return 1
         raise NotImplementedError(f"observation term '{name}': {_CLASSIC}.observations:{fn} has no fused op")
 
+    # -- the reach tasks' own terms (isaaclab_tasks .../manipulation/reach/mdp/rewards.py: Isaac-Reach-Franka-v0, -UR10-v0) -----------
+    def _reach_reward(self, name: str, fn: str, p: dict, rec: dict, blob: _Blob, cmd_dim: int) -> None:
+        """Fills ``rec`` for one of the three reward functions of manipulation/reach/mdp/rewards.py; ``NotImplementedError`` for anything
+        else of that module.  Each reads ``asset_cfg.body_ids[0]`` (one body id in the record) and the (N, 7) pose command."""
+        if fn not in ("position_command_error", "position_command_error_tanh", "orientation_command_error"):
+            raise NotImplementedError(f"reward term '{name}': {_REACH}:{fn} has no fused op")
+        if cmd_dim != 7:
+            raise ValueError(f"reward term '{name}': {fn} reads a UniformPoseCommand (N, 7); the cfg's command is {cmd_dim} wide")
+        ids = self.resolve_ids(p.get("asset_cfg"), "body")
+        if not ids:
+            raise ValueError(f"reward term '{name}': asset_cfg selects no body")
+        rec.update(op=W_OPS[fn.upper()], ids_off=blob.ints(ids[:1]), nids=1)
+        if fn == "position_command_error_tanh":
+            rec["p0"] = f32(p["std"])
+
     # -- compile ------------------------------------------------------------------------------------------------
     def compile(self) -> Plan:
         cfg, robot = self.cfg, self.robot
         J, B = robot.num_joints, robot.num_bodies
+        # the env's one command tensor: as wide as its command terms' command (CommandManager.get_command)
+        widths = {command_width(c) for c in (cfg.get("commands") or {}).values() if isinstance(c, dict)}
+        if len(widths) > 1:
+            raise NotImplementedError(f"command terms of widths {sorted(widths)}: the fused path carries one command tensor")
+        cmd_dim = widths.pop() if widths else 3
         scene = cfg.get("scene", {})
         contact = scene.get("contact_forces")
         Hh = int(contact.get("history_length", 0)) if contact else 0
@@ -665,6 +694,8 @@ class PlanCompiler:
                 self._spot_reward(name, _short(fn)[1], p, rec, blob)
             elif _short(fn)[0] in _CLASSIC_MODULES:
                 self._classic_reward(name, _short(fn)[1], p, rec, blob, A, term_slots)
+            elif _short(fn)[0] == _REACH:
+                self._reach_reward(name, _short(fn)[1], p, rec, blob, cmd_dim)
             else:
                 known = False
                 rec.update(op=W_OPS["EXTERNAL"], aux0=n_ext_rew)
@@ -759,7 +790,9 @@ class PlanCompiler:
                 elif fn == f"{_MDP}.observations:last_action" and p.get("action_name") is None:
                     rec["op"], dim = O_OPS["LAST_ACTION"], A
                 elif fn == f"{_MDP}.observations:generated_commands":
-                    rec["op"], dim = O_OPS["GENERATED_COMMANDS"], 3
+                    rec["op"], dim = O_OPS["GENERATED_COMMANDS"], command_width((cfg.get("commands") or {}).get(p.get("command_name")))
+                    if dim != cmd_dim:
+                        raise ValueError(f"observation term '{name}': command '{p.get('command_name')}' is {dim} wide, the env's command {cmd_dim}")
                 elif fn == f"{_MDP}.observations:body_incoming_wrench":  # observations.py:176-185: 6 columns per body, body_ids order
                     ids = self.resolve_ids(p.get("asset_cfg"), "body")
                     dim = 6 * len(ids)
@@ -872,7 +905,7 @@ class PlanCompiler:
             "MAX_EP_LEN": max_len, "TERM_OFF": term_off, "REW_OFF": rew_off, "OBS_OFF": obs_off, "ACT_OFF": act_off,
             "TOTAL_WORDS": len(w), "NB": B, "NREW_ALL": len(rew_terms), "RAY_OFF": ray_off,
             "NEXT_REW": n_ext_rew, "NEXT_TERM": n_ext_term, "NEXT_OBS": n_ext_obs,
-            "RAY_YAW_ONLY": 1 if (scanner and scanner.get("attach_yaw_only")) else 0, "CMD_DIM": 3,
+            "RAY_YAW_ONLY": 1 if (scanner and scanner.get("attach_yaw_only")) else 0, "CMD_DIM": cmd_dim,
             "MOD_STATE": mod_state, "NGROUPS": len(groups), "GROUP_OFF": group_off, "SCAN_SUBSTEPS": int(cfg["decimation"]),
             "SCAN_STATEFUL": int(scan_stateful), "TERM_SLOTS": len(term_slots),
         }
@@ -887,7 +920,7 @@ class PlanCompiler:
         arr = np.where(arr >= 2 ** 31, arr - 2 ** 32, arr).astype(np.int32)
         return Plan(blob=arr, robot=robot, num_joints=J, num_bodies=B, history=Hh, action_dim=A, obs_dim=groups[0].dim, num_rays=R_n,
                     obs_groups=groups, obs_dim_total=D, scan_stateful=scan_stateful, scan_drift_range=(float(drift[0]), float(drift[1])),
-                    cmd_dim=3, step_dt=step_dt, max_episode_length=max_len, max_episode_length_s=max_len_s,
+                    cmd_dim=cmd_dim, step_dt=step_dt, max_episode_length=max_len, max_episode_length_s=max_len_s,
                     is_finite_horizon=bool(cfg.get("is_finite_horizon", False)), reward_terms=rew_terms,
                     termination_terms=term_terms, obs_terms=obs_terms, obs_term_dims=obs_dims,
                     action_terms=action_terms, enable_corruption=corruption, ray_starts_local=ray_local,

@@ -3,8 +3,8 @@
 The reference obtains joint/body names and default joint positions from PhysX after loading the robot USD
 (``Articulation._initialize_impl``); neither PhysX nor the USD files exist here, so the *names* ship as data.
 Defaults follow the asset cfgs (reference ``source/isaaclab_assets/isaaclab_assets/robots/anymal.py:112-121``,
-``unitree.py:290-307`` (G1), ``spot.py:151-160``, ``cartpole.py``, ``ant.py:33-42``, the humanoid task's init state).  The G1, Spot,
-Ant and Humanoid joint / body orders are synthetic
+``unitree.py:290-307`` (G1), ``spot.py:151-160``, ``cartpole.py``, ``ant.py:33-42``, the humanoid task's init state, ``franka.py:39-47``,
+``universal_robots.py:35-41``).  The G1, Spot, Ant, Humanoid, Franka and UR10 joint / body orders are synthetic
 breadth-first orders of the names the task cfgs' regexes refer to (the true PhysX order is not recoverable offline); term
 semantics do not depend on them because every index list is resolved by name through :func:`resolve_matching_names`.
 """
@@ -77,6 +77,7 @@ class RobotSpec:
     soft_joint_pos_limit_factor: float = 1.0
     joint_pos_limits: tuple[float, float] = (-2.0 * math.pi, 2.0 * math.pi)
     joint_vel_limit: float = 100.0
+    command_dim: int = 3  # width of the command the state feed serves: 3 = base velocity (vx, vy, wz), 7 = end-effector pose
 
     @property
     def num_joints(self) -> int:
@@ -191,4 +192,28 @@ HUMANOID = RobotSpec(
     joint_pos_limits=(-1.0, 1.0),
 )
 
-ROBOTS = {r.name: r for r in (ANYMAL_C, G1, CARTPOLE, SPOT, ANT, HUMANOID)}
+# The fixed-base arms of the Reach tasks (isaaclab_assets/robots/franka.py, universal_robots.py; manipulation/reach).  Names are the ones
+# the cfgs and the USDs use, joints before fingers and bodies from the base link out, in a synthetic order; the limits are a round
+# +-2 pi (terms see the state feed's soft limits).  The root sits at the env origin (init_state pos (0, 0, 0)).  command_dim = 7: the
+# feed serves a UniformPoseCommand-shaped command, a position and a unit quaternion in the base frame.
+FRANKA_PANDA = RobotSpec(
+    name="franka_panda",
+    joint_names=[f"panda_joint{i}" for i in range(1, 8)] + ["panda_finger_joint1", "panda_finger_joint2"],
+    body_names=[f"panda_link{i}" for i in range(8)] + ["panda_hand", "panda_leftfinger", "panda_rightfinger"],
+    default_joint_pos={"panda_joint1": 0.0, "panda_joint2": -0.569, "panda_joint3": 0.0, "panda_joint4": -2.81, "panda_joint5": 0.0,
+                       "panda_joint6": 3.037, "panda_joint7": 0.741, "panda_finger_joint.*": 0.04},
+    default_root_height=0.0,
+    command_dim=7,
+)
+
+UR10 = RobotSpec(
+    name="ur10",
+    joint_names=["shoulder_pan_joint", "shoulder_lift_joint", "elbow_joint", "wrist_1_joint", "wrist_2_joint", "wrist_3_joint"],
+    body_names=["base_link", "shoulder_link", "upper_arm_link", "forearm_link", "wrist_1_link", "wrist_2_link", "wrist_3_link", "ee_link"],
+    default_joint_pos={"shoulder_pan_joint": 0.0, "shoulder_lift_joint": -1.712, "elbow_joint": 1.712, "wrist_1_joint": 0.0,
+                       "wrist_2_joint": 0.0, "wrist_3_joint": 0.0},
+    default_root_height=0.0,
+    command_dim=7,
+)
+
+ROBOTS = {r.name: r for r in (ANYMAL_C, G1, CARTPOLE, SPOT, ANT, HUMANOID, FRANKA_PANDA, UR10)}

@@ -22,10 +22,10 @@ DYNAMIC = (
     "body_lin_vel_w", "command", "net_forces_w_history",
     "last_air_time", "current_air_time", "current_contact_time", "last_contact_time",
 )
-# further per-step tensors only a few optional terms read (body_lin_acc_l2, command_resample, foot_clearance_reward, body_incoming_wrench):
-# drawn from their own generators so that the tensors above are unchanged by their presence; recorded fixtures carry them only when their
-# cfg needs them
-EXTRA = ("body_lin_acc_w", "command_time_left", "command_counter", "body_pos_w", "link_incoming_joint_force")
+# further per-step tensors only a few optional terms read (body_lin_acc_l2, command_resample, foot_clearance_reward, body_incoming_wrench,
+# the reach rewards): drawn from their own generators so that the tensors above are unchanged by their presence; recorded fixtures carry
+# them only when their cfg needs them
+EXTRA = ("body_lin_acc_w", "command_time_left", "command_counter", "body_pos_w", "link_incoming_joint_force", "body_quat_w")
 # tensors fixed for the lifetime of the scene
 STATIC = ("default_joint_pos", "default_joint_vel", "soft_joint_pos_limits", "soft_joint_vel_limits", "env_origins")
 
@@ -162,6 +162,27 @@ def generate_link_wrench(robot: RobotSpec, num_envs: int, gen: torch.Generator) 
     return torch.cat([force, torque], dim=-1).contiguous()
 
 
+def generate_body_quat(robot: RobotSpec, num_envs: int, gen: torch.Generator) -> torch.Tensor:
+    """``ArticulationData.body_quat_w`` (N, B, 4) w, x, y, z: uniform unit quaternions (normalised N(0, 1) 4-vectors), half of them
+    with w < 0 -- the sign a PhysX pose carries is arbitrary."""
+    q = torch.randn(num_envs, robot.num_bodies, 4, generator=gen)
+    return (q / q.norm(dim=-1, keepdim=True).clamp_min(1e-12)).contiguous()
+
+
+# UniformPoseCommand ranges of the Reach tasks (manipulation/reach/reach_env_cfg.py): the position of the end-effector target in the base
+# frame; the orientation is any unit quaternion (the cfgs' roll 0, pitch pi or pi / 2, yaw +-3.14 Euler draws are a subset of it)
+POSE_COMMAND_POS_RANGE = ((0.35, 0.65), (-0.2, 0.2), (0.15, 0.5))
+
+
+def generate_pose_command(num_envs: int, gen: torch.Generator) -> torch.Tensor:
+    """``UniformPoseCommand.command`` (N, 7): position uniform in :data:`POSE_COMMAND_POS_RANGE`, then a unit quaternion w, x, y, z in
+    the base frame (w < 0 on half of the envs: ``make_quat_unique=False`` keeps either sign)."""
+    pos = torch.stack([torch.rand(num_envs, generator=gen) * (hi - lo) + lo for lo, hi in POSE_COMMAND_POS_RANGE], dim=-1)
+    q = torch.randn(num_envs, 4, generator=gen)
+    q = q / q.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+    return torch.cat([pos, q], dim=-1).contiguous()
+
+
 class StateFeed:
     """``S`` snapshots of the post-physics state held on ``device``; ``advance()`` moves to the next one.
 
@@ -183,10 +204,17 @@ class StateFeed:
         gen_x = torch.Generator().manual_seed(seed + 0x5EED)
         gen_p = torch.Generator().manual_seed(seed + 0xB0D7)
         gen_w = torch.Generator().manual_seed(seed + 0x1F0C)
+        gen_q = torch.Generator().manual_seed(seed + 0x0A7E)
+        gen_c = torch.Generator().manual_seed(seed + 0x9C3D)
         for sn in snaps:
             sn.update(generate_extras(robot, num_envs, gen_x))
             sn["body_pos_w"] = generate_body_pos(robot, num_envs, gen_p)
             sn["link_incoming_joint_force"] = generate_link_wrench(robot, num_envs, gen_w)
+            sn["body_quat_w"] = generate_body_quat(robot, num_envs, gen_q)
+            if robot.command_dim == 7:  # a pose command (the velocity command drawn above is dropped: other tensors keep their draws)
+                sn["command"] = generate_pose_command(num_envs, gen_c)
+            elif robot.command_dim != 3:
+                raise ValueError(f"robot {robot.name}: the feed serves 3- or 7-wide commands, not {robot.command_dim}")
         for name in DYNAMIC + EXTRA:
             self._stack[name] = torch.stack([s[name] for s in snaps], dim=0).to(self.device).contiguous()
         # every snapshot keeps the same origins/defaults; root xy of later snapshots re-uses snapshot-0 origins

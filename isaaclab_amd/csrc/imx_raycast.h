@@ -248,12 +248,17 @@ IMX_DEV bool vertical_cell(const MeshView& m, int ix, int iy, float ox, float oy
             const float hi = oy > cy ? (ox < cx ? h01 : (ox > cx ? h11 : fmaxf(h01, h11))) : -__builtin_huge_valf();
             const float on = oy == cy ? fmaxf(ox <= cx ? fmaxf(h00, h01) : -__builtin_huge_valf(), ox >= cx ? fmaxf(h10, h11) : -__builtin_huge_valf())
                                       : -__builtin_huge_valf();
-            take_hit(Sz * (fmaxf(fmaxf(lo, hi), on) - oz), b4.w, best, face);
-            return complete;
-        } else {  // a ray on a cell boundary, or an upward one: the full list
-            const int2 g = m.cell_list[c];
-            vertical_list(m, g.x, g.x + g.y, ox, oy, oz, flip, Sz, dz, best, face);
+            const float tq = Sz * (fmaxf(fmaxf(lo, hi), on) - oz);
+            if (tq >= 0.0f) {
+                take_hit(tq, b4.w, best, face);
+                return complete;
+            }
+            // the ray starts BELOW the highest surface (inside a box, under a slab): the closest hit with t >= 0 is a lower face, which
+            // the heights do not know -- the full list, and the neighbours (the continuity proof speaks of the highest surface only)
         }
+        // a ray on a cell boundary, an upward one, or one that starts under the top: the full list
+        const int2 g = m.cell_list[c];
+        vertical_list(m, g.x, g.x + g.y, ox, oy, oz, flip, Sz, dz, best, face);
     } else if (kind == IMX_CELL_GENERAL) {
 #ifdef IMX_EXP_NOGENERAL
         return false;

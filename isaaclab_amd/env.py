@@ -18,6 +18,7 @@ import importlib
 import json
 import math
 import os
+import struct
 from collections.abc import Sequence
 from typing import Any
 
@@ -81,6 +82,7 @@ class TerrainMesh:
         self.max_refs, self.num_flat_cells = int(info[4]) & 0xFFFFFFFF, int(info[4]) >> 32  # FLAT: general cells answered by their descriptor
         self.num_lattice_cells, self.num_general_cells = int(info[5]), int(info[6])
         self.num_vertices = v.shape[0]
+        self.cell_size = struct.unpack("f", struct.pack("i", int(info[7])))[0]  # the cell size actually used (the automatic one for cell_size <= 0)
 
     @property
     def handle(self):

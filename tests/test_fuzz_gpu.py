@@ -73,3 +73,10 @@ def test_raycast_sweep(seed):
     import fuzz_raycast
 
     fuzz_raycast.one_case(seed)
+
+
+@pytest.mark.parametrize("seed", [500, 501, 502])
+def test_scanner_mesh_sweep(seed):
+    import fuzz_raycast
+
+    fuzz_raycast.one_case_scanner(seed)

@@ -1,7 +1,10 @@
 """Random sweep of the ray-cast (TerrainMesh.raycast: the height scanner's grid walk) against the brute-force oracles over ALL triangles
 (oracle/raycast_oracle.c: fp32 Woop -- same arithmetic, bit-exact distances expected -- and fp64 Moeller-Trumbore, 1e-5): random terrains
 (tile mix by seed, 1..4 x 1..4 tiles, border), cell sizes, vertical rays (a share of them snapped onto lattice lines), upward rays and
-slanted rays through the DDA path.  Test infrastructure, run on the GPU box:  python tools/fuzz_raycast.py [cases] [seed]"""
+slanted rays through the DDA path.  ``one_case_scanner``: the height scanner's own fast vertical path instead (vertical_cell and the
+mesh builder's cell proofs, which TerrainMesh.raycast never takes) -- a random case of the mesh zoo of tests/_scan_cases.py at a random
+cell size, kernel variant, batch size and ray origin, through the env, under that module's comparison rule.
+Test infrastructure, run on the GPU box:  python tools/fuzz_raycast.py [cases] [seed] [scanner]"""
 import os
 import sys
 
@@ -71,9 +74,34 @@ def one_case(seed: int) -> str:
     return f"{rows}x{cols} tiles of {tile} m border {border} cell {cell} ({len(t)} triangles): vertical hits {int((~miss).sum())}/{R}, slanted hits {int(np.isfinite(dd).sum())}/{R2}, fp64 hit/miss flips {flips}"
 
 
+def one_case_scanner(seed: int) -> str:
+    import dataclasses
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _scan_cases as sc
+
+    rng = np.random.default_rng(seed)
+    zoo = sc.zoo()
+    base = zoo[list(zoo)[int(rng.integers(len(zoo)))]]
+    case = base
+    if base.family != "D" and rng.random() < 0.7:  # another cell size: the premise on the cell kinds no longer applies (D: 200 m wide)
+        case = dataclasses.replace(base, cell=float(rng.choice([0.0, 0.05, 0.08, 0.13, 0.2, 0.25, 0.37])), premise="any", continuous=False)
+    variant = list(sc.VARIANTS)[int(rng.integers(len(sc.VARIANTS)))]
+    mode = "down"
+    if rng.random() < 0.3:
+        mode = "up" if (base.between_z is None or rng.random() < 0.5) else "between"
+    N = int(rng.choice([1, 2, 3, 17, 33, 64, 65]))
+    fig = sc.run_scan_case(case, variant, N=N, mode=mode, product=True, seed=int(rng.integers(1000)))
+    return (f"{base.name} cell {case.cell:g} {fig['kernel']} {mode} N={N} ({fig['triangles']} triangles; LATTICE {fig['lattice']}, QH {fig['qh']}, "
+            f"GENERAL {fig['general']}): {fig['hits']}/{fig['rays']} hits, unsettled share {fig['unsettled_share']:.4f}, "
+            f"worst settled error {fig['worst_settled_err']:.2e}")
+
+
 if __name__ == "__main__":
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     first = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    if len(sys.argv) > 3 and sys.argv[3] == "scanner":
+        one_case = one_case_scanner  # noqa: F811
     bad = 0
     for c in range(first, first + cases):
         try:

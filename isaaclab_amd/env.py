@@ -29,7 +29,7 @@ from . import _lib
 from ._lib import ImxBuffers, ImxState, check, lib
 from .plan import Plan, compile_plan
 from .plan import func_name as func_name_of
-from .robots import ROBOTS, RobotSpec
+from .robots import ROBOTS, RobotSpec, SceneEntityResolver
 from .state_feed import StateFeed
 
 _CFG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs")
@@ -454,16 +454,15 @@ class _SceneEntityView:
     """``SceneEntityCfg`` as a Python-evaluated term sees it after ``resolve()`` (managers/scene_entity_cfg.py:112-250): ``name``,
     ``joint_names`` / ``body_names`` and the resolved ``joint_ids`` / ``body_ids`` (``slice(None)`` when every one is selected)."""
 
-    def __init__(self, ent: dict, compiler):
+    def __init__(self, ent: dict, entities):
         self.name = ent.get("name")
         self.joint_names, self.body_names = ent.get("joint_names"), ent.get("body_names")
         self.preserve_order = bool(ent.get("preserve_order"))
         for kind in ("joint", "body"):
             ids = slice(None)
             try:
-                n_all = len(compiler._entity_names(self.name, kind))
-                r = compiler.resolve_ids(ent, kind)
-                ids = slice(None) if (ent.get(f"{kind}_names") is None and len(r) == n_all) else r
+                r = entities.ids(ent, kind)
+                ids = slice(None) if (ent.get(f"{kind}_names") is None and len(r) == len(entities.names(self.name, kind))) else r
             except ValueError:
                 pass  # entity without such a name table (e.g. the height scanner)
             setattr(self, f"{kind}_ids", ids)
@@ -581,6 +580,7 @@ class ManagerBasedRLEnv:
         # the env's own copy of the cfg in to_dict() form: set_term_cfg edits and recompiles it
         self._cfg_dict = copy.deepcopy(env_cfg if isinstance(env_cfg, dict) else env_cfg.to_dict())
         self._robot = robot_name
+        self._entities = SceneEntityResolver(robot_name)
         self.plan: Plan = compile_plan(self._cfg_dict, robot_name)
         plan = self.plan
         env_dict = self._cfg_dict
@@ -894,14 +894,11 @@ class ManagerBasedRLEnv:
     def _resolve_ext(self, term):
         """Callable + call-time parameters of a Python-evaluated term (ManagerBase._resolve_common_term_cfg,
         managers/manager_base.py:278-395: SceneEntityCfg parameters are resolved against the scene once)."""
-        from .plan import PlanCompiler
-
         import inspect
 
         f = term.external
         fn = _string_to_callable(f) if isinstance(f, str) else f
-        comp = PlanCompiler(self._cfg_dict, self._robot)
-        term.call_params = {k: (_SceneEntityView(v, comp) if _looks_like_scene_entity(v) else v) for k, v in term.params.items()}
+        term.call_params = {k: (_SceneEntityView(v, self._entities) if _looks_like_scene_entity(v) else v) for k, v in term.params.items()}
         term.py_mod_funcs = [(_string_to_callable(m) if isinstance(m, str) else m, mp) for m, mp in term.py_modifiers]
         if inspect.isclass(fn):
             # a class term (manager_base.py:324-327,393-395): instantiated ONCE with (cfg, env); the instance is what gets called every

@@ -102,6 +102,47 @@ class RobotSpec:
         return [(mean - 0.5 * rng * f, mean + 0.5 * rng * f)] * self.num_joints
 
 
+def _is_slice_all(x) -> bool:
+    return x is None or x == slice(None) or (isinstance(x, str) and x.replace(" ", "") == "slice(None,None,None)")
+
+
+class SceneEntityResolver:
+    """``SceneEntityCfg.resolve`` (isaaclab/managers/scene_entity_cfg.py:112-250) over a robot's name tables: the joint / body ids a
+    ``SceneEntityCfg`` selects.  The term compiler resolves the fused terms' entities with it, the env those of Python-evaluated terms."""
+
+    def __init__(self, robot: RobotSpec):
+        self.joint_names = list(robot.joint_names)
+        self.body_names = list(robot.body_names)
+
+    def names(self, entity: str, kind: str) -> list[str]:
+        if entity in ("robot", "contact_forces"):
+            return self.joint_names if kind == "joint" else self.body_names
+        raise ValueError(f"The scene entity '{entity}' does not exist. Available entities: "
+                         f"['robot', 'contact_forces', 'height_scanner'].")
+
+    def ids(self, ent, kind: str, default_entity: str = "robot") -> list[int]:
+        """joint_ids / body_ids of a SceneEntityCfg (dict form, live object, or None = function default)."""
+        if ent is None:
+            return list(range(len(self.names(default_entity, kind))))
+        get = (lambda k: ent.get(k)) if isinstance(ent, dict) else (lambda k: getattr(ent, k, None))
+        name = get("name")
+        names = self.names(name, kind)
+        keys, ids = get(f"{kind}_names"), get(f"{kind}_ids")
+        preserve = bool(get("preserve_order"))
+        if keys is not None:
+            keys = [keys] if isinstance(keys, str) else keys
+            r_ids, _ = resolve_matching_names(keys, names, preserve)
+            if _is_slice_all(ids):
+                return list(r_ids)
+            ids = [ids] if isinstance(ids, int) else ids
+            if list(r_ids) != list(ids) or [names[i] for i in ids] != list(keys):
+                raise ValueError(f"Both '{kind}_names' and '{kind}_ids' are specified, and are not consistent.")
+            return list(ids)
+        if not _is_slice_all(ids):
+            return [ids] if isinstance(ids, int) else [int(i) for i in ids]
+        return list(range(len(names)))
+
+
 _LEGS = ("LF", "LH", "RF", "RH")
 
 ANYMAL_C = RobotSpec(

@@ -258,3 +258,22 @@ def test_task_cfg_merges_the_managers_side_file():
     assert fx["events"]["push_robot"]["interval_range_s"] == [10.0, 15.0] and fx["events"]["push_robot"]["mode"] == "interval"
     assert list(fx["curriculum"]) == ["terrain_levels"] and fx["scene"]["robot"]["init_state"]["pos"] == [0.0, 0.0, 0.6]
     assert "events" not in load_task_cfg("Isaac-Cartpole-v0")["env"]
+
+
+def test_plan_outcomes_are_the_recorded_ones():
+    """The term compiler's outcome on a fixed case list (tests/_cfg_cases.py ``plan_outcomes``) is the recorded one, case by case:
+    2000 random cfgs, every committed task config, and every task config with one term parameter deleted.  An outcome is the plan blob
+    plus the ``Plan`` mirror, or the refusal's type and message; tests/golden/plan_outcomes.npz holds 8 bytes of its SHA-256 per case,
+    recorded by tools/gen_golden_plan_outcomes.py with the package of commit 453ad57 (the last one before the compiler was split into
+    term tables and per-manager methods)."""
+    from _cfg_cases import plan_outcomes
+
+    z = np.load(os.path.join(GOLDEN, "plan_outcomes.npz"))
+    got = plan_outcomes()
+    # the pin must not be dominated by refusals
+    assert int(got["fuzz_compiled"].sum()) >= 1500, int(got["fuzz_compiled"].sum())
+    assert len(got["configs"]) >= 16 and got["configs_compiled"].all()
+    for key in ("fuzz", "configs", "drop_param"):
+        assert got[key].dtype == np.uint64 and got[key].shape == z[key].shape, key
+        differ = np.nonzero(got[key] != z[key])[0]
+        assert differ.size == 0, f"{key}: {differ.size} of {len(z[key])} outcomes differ from the recorded ones, first at case {differ[:8].tolist()}"

@@ -371,7 +371,7 @@ typedef struct imx_orch {
     const int64_t* rand_levels_d;          /* optional (N): the randint_like draw (parity runs) */
     int32_t terrain_rows, terrain_cols;
     float terrain_size_x, max_episode_length_s;
-    /* CommandManager: UniformVelocityCommand; has_command = 0: none */
+    /* CommandManager: has_command = 0: none, 1: UniformVelocityCommand, 2: UniformPoseCommand (its fields are at the struct's end) */
     int32_t has_command, heading_command;
     float command_cfg[16];                 /* as imx_velocity_command's cfg15 */
     float* vel_command_b_d;                /* (N,3) */
@@ -400,6 +400,16 @@ typedef struct imx_orch {
     /* per-workgroup partial sums for the step tail's log entries (imx_buffers.ev_part): {error_vel_xy, error_vel_yaw over the reset
      * envs; terrain levels over all envs; reset count} x ceil(N / 64) */
     float* ev_part_d;
+    /* has_command = 2: the command term is a UniformPoseCommand (envs/mdp/commands/pose_command.py:25-127; pose_command_env).  It shares
+     * command_time_left_d, command_counter_d, command_uniforms_d and command_cfg (imx_pose_command's cfg16) with the velocity command;
+     * metric_error_vel_xy_d / metric_error_vel_yaw_d hold its metrics position_error / orientation_error (the log's first / second
+     * command slot, ev_part columns 0 / 1); the body count is num_bodies.  Not combined with the terrain curriculum. */
+    float* pose_command_b_d;               /* (N,7) position + w, x, y, z quaternion in the base frame */
+    float* pose_command_w_d;               /* (N,7) */
+    const float* body_pos_w_d;             /* (N,NB,3) of the current (post-physics) state */
+    const float* body_quat_w_d;            /* (N,NB,4) */
+    int32_t pose_body_idx;                 /* robot.find_bodies(cfg.body_name)[0][0] */
+    int32_t make_quat_unique;
 } imx_orch_t;
 /* number of floats of ev_part for num_envs */
 size_t imx_orch_part_floats(int64_t num_envs);
@@ -601,6 +611,23 @@ int imx_velocity_command(int64_t N, const float* cfg15, int heading_command, flo
                          float* heading_target_d, uint8_t* is_heading_env_d, uint8_t* is_standing_env_d,
                          float* time_left_d, int64_t* command_counter_d, float* metric_error_vel_xy_d,
                          float* metric_error_vel_yaw_d, imx_stream_t stream);
+
+/* The same two steps for UniformPoseCommand (managers/command_manager.py:120-187, envs/mdp/commands/pose_command.py:25-127):
+ * CommandTerm.reset for the envs flagged in reset_mask_d (may be NULL), then -- when do_compute != 0 -- CommandTerm.compute(dt):
+ * _update_metrics (pose_command_w = combine_frame_transforms(root pose, pose_command_b), utils/math.py:750-781; position_error /
+ * orientation_error = norms of compute_pose_error(..., "axis_angle"), :820-867, against body body_idx of body_pos_w_d (N,NB,3) /
+ * body_quat_w_d (N,NB,4) -- ASSIGNED, not accumulated), time_left -= dt, resampling where time_left <= 0 (six uniform draws, then
+ * quat_from_euler_xyz :252-278 and, with make_quat_unique, quat_unique :448-460).
+ * cfg16 (HOST floats) = {resampling_time lo,hi, pos_x lo,hi, pos_y lo,hi, pos_z lo,hi, roll lo,hi, pitch lo,hi, yaw lo,hi, -, -}.
+ * uniforms_d: optional (2,N,7) samples in [0,1) {time_left, pos_x, pos_y, pos_z, roll, pitch, yaw} for the first / second resampling
+ * of an env within this call (parity mode); NULL -> counter-based in-kernel generator.  pose_command_b_d / pose_command_w_d: (N,7)
+ * position + w, x, y, z quaternion.  Refused: a null state tensor, body_idx outside [0, num_bodies), resampling_time hi <= 0. */
+int imx_pose_command(int64_t N, const float* cfg16, int make_quat_unique, int64_t body_idx, int64_t num_bodies, float dt,
+                     int do_compute, const float* root_pos_w_d, const float* root_quat_w_d, const float* body_pos_w_d,
+                     const float* body_quat_w_d, const uint8_t* reset_mask_d, const float* uniforms_d, uint64_t seed,
+                     const int32_t* step_counter_d, float* pose_command_b_d, float* pose_command_w_d, float* time_left_d,
+                     int64_t* command_counter_d, float* metric_position_error_d, float* metric_orientation_error_d,
+                     imx_stream_t stream);
 
 /* ArticulationData.root_state_w + joint_acc (assets/articulation/articulation_data.py:365-380,546-556): split PhysX's
  * root transforms (N,7: pos, quat XYZW) / velocities (N,6) into root_pos_w, root_quat_w (WXYZ, convert_quat

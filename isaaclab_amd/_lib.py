@@ -80,7 +80,10 @@ class ImxOrch(ctypes.Structure):  # imx_orch_t
                     "cs_is_outdated_d", "cs_net_forces_w_d", "cs_net_forces_w_history_d", "cs_last_air_time_d", "cs_current_air_time_d",
                     "cs_last_contact_time_d", "cs_current_contact_time_d")]
                 + [("cs_num_bodies", c_int32), ("cs_history_length", c_int32), ("lstm_hidden_d", c_void_p), ("lstm_cell_d", c_void_p),
-                   ("lstm_layers", c_int32), ("lstm_hidden_dim", c_int32), ("ev_part_d", c_void_p)])
+                   ("lstm_layers", c_int32), ("lstm_hidden_dim", c_int32), ("ev_part_d", c_void_p)]
+                # has_command = 2 (UniformPoseCommand): appended, nothing above moved
+                + [(n, c_void_p) for n in ("pose_command_b_d", "pose_command_w_d", "body_pos_w_d", "body_quat_w_d")]
+                + [("pose_body_idx", c_int32), ("make_quat_unique", c_int32)])
 
 
 class ImxError(RuntimeError):
@@ -142,6 +145,8 @@ _SIGNATURES = {
                                   + [c_void_p]),
     "imx_velocity_command": (c_int, [c_int64, c_void_p, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_uint64, c_void_p] + [c_void_p] * 8 + [c_void_p]),
+    "imx_pose_command": (c_int, [c_int64, c_void_p, c_int, c_int64, c_int64, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_uint64, c_void_p] + [c_void_p] * 6 + [c_void_p]),
     "imx_articulation_update": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_float] + [c_void_p] * 6 + [c_void_p]),
     "imx_actuator_pd": (c_int, [c_int64, c_int64, c_int, c_float] + [c_void_p] * 11 + [c_void_p]),
     "imx_actuator_delayed_pd": (c_int, [c_int64, c_int64, c_int, c_int64] + [c_void_p] * 12 + [c_int] + [c_void_p] * 2 + [c_void_p]),

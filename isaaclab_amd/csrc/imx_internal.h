@@ -171,6 +171,30 @@ IMX_DEV void quat_apply(float w, float x, float y, float z, float vx, float vy, 
     oz = vz + w * tz + (x * ty - y * tx);
 }
 
+// quat_mul (utils/math.py:464-500): the reference's eight-product form with its association, quaternions w, x, y, z in .x .. .w
+IMX_DEV float4 quat_mul_ref(float4 a, float4 b) {
+    const float w1 = a.x, x1 = a.y, y1 = a.z, z1 = a.w, w2 = b.x, x2 = b.y, y2 = b.z, z2 = b.w;
+    const float ww = (z1 + x1) * (x2 + y2);
+    const float yy = (w1 - y1) * (w2 + z2);
+    const float zz = (w1 + y1) * (w2 - z2);
+    const float xx = ww + yy + zz;
+    const float qq = 0.5f * (xx + (z1 - x1) * (x2 - y2));
+    return make_float4(qq - ww + (z1 - y1) * (y2 - z2), qq - xx + (x1 + w1) * (x2 + w2), qq - yy + (w1 - x1) * (y2 + z2),
+                       qq - zz + (z1 + y1) * (w2 - x2));
+}
+// ||axis_angle_from_quat(d)|| (utils/math.py:646-675) step by step: the w < 0 flip (q * (1 - 2 (w < 0))), half = atan2(||xyz||, w),
+// angle = 2 half, the |angle| <= 1e-6 Taylor branch 0.5 - angle^2 / 48, then xyz / that factor and its norm
+IMX_DEV float axis_angle_magnitude(float4 d) {
+    const float sg = 1.0f - 2.0f * (d.x < 0.0f ? 1.0f : 0.0f);
+    const float w = d.x * sg, x = d.y * sg, y = d.z * sg, z = d.w * sg;
+    const float mag = sqrtf((x * x + y * y) + z * z);
+    const float half = atan2f(mag, w);
+    const float angle = 2.0f * half;
+    const float s = fabsf(angle) > 1.0e-6f ? sinf(half) / angle : 0.5f - angle * angle / 48.0f;
+    const float ax = x / s, ay = y / s, az = z / s;
+    return sqrtf((ax * ax + ay * ay) + az * az);
+}
+
 // wrap_to_pi (isaaclab/utils/math.py:95-117), torch.remainder semantics
 // reset_joints_around_default (isaaclab_tasks/.../velocity/config/spot/mdp/events.py:48-58): lo/hi = clamp(default + range, limits),
 // then sample_uniform (utils/math.py:1313-1331) = u * (hi - lo) + lo

@@ -30,6 +30,9 @@ __device__ __forceinline__ float wsum(float v) {
     return v;
 }
 
+// POSE: the command term is a UniformPoseCommand (has_command == 2) instead of the velocity command; an instantiation of its own so that
+// the velocity cfgs run the register budget they always had, dispatched on the host
+template <bool POSE>
 __global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate(imx_orch_t o) {
     const int lane = threadIdx.x;
     const int64_t N = o.num_envs;
@@ -204,7 +207,20 @@ __global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate(imx_orch_t o) 
 
     // ---- CommandTerm.reset for the reset envs (logs + zeroes the metrics, resamples), then CommandManager.compute(dt)
     float mxy0 = 0.0f, myaw0 = 0.0f;
-    if (o.has_command && live) {
+    if (POSE && live) {  // the same place, the same reset flag and the same two log columns as the velocity command
+        PoseCmdCfg c;
+        c.resample_lo = o.command_cfg[0]; c.resample_hi = o.command_cfg[1];
+        c.pos_x_lo = o.command_cfg[2]; c.pos_x_hi = o.command_cfg[3]; c.pos_y_lo = o.command_cfg[4]; c.pos_y_hi = o.command_cfg[5];
+        c.pos_z_lo = o.command_cfg[6]; c.pos_z_hi = o.command_cfg[7]; c.roll_lo = o.command_cfg[8]; c.roll_hi = o.command_cfg[9];
+        c.pitch_lo = o.command_cfg[10]; c.pitch_hi = o.command_cfg[11]; c.yaw_lo = o.command_cfg[12]; c.yaw_hi = o.command_cfg[13];
+        c.make_quat_unique = o.make_quat_unique;
+        c.body_idx = o.pose_body_idx; c.num_bodies = NB;
+        const PoseCmdState st{o.pose_command_b_d, o.pose_command_w_d, o.command_time_left_d, o.command_counter_d, o.metric_error_vel_xy_d,
+                              o.metric_error_vel_yaw_d};
+        pose_command_env(N, e, c, o.dt, o.do_step, o.root_pos_w_d, o.root_quat_w_d, o.body_pos_w_d, o.body_quat_w_d, reset,
+                         o.command_uniforms_d, o.seed ^ 0xC0FFEEull, step, st, mxy0, myaw0);
+    }
+    if (!POSE && o.has_command && live) {
         VelCmdCfg c;
         c.resample_lo = o.command_cfg[0]; c.resample_hi = o.command_cfg[1];
         c.lin_x_lo = o.command_cfg[2]; c.lin_x_hi = o.command_cfg[3]; c.lin_y_lo = o.command_cfg[4]; c.lin_y_hi = o.command_cfg[5];
@@ -322,7 +338,22 @@ extern "C" int imx_reset_orchestrate(const imx_orch_t* o, imx_stream_t stream) {
         IMX_REQUIRE(o->terrain_origins_d && o->terrain_types_d && o->terrain_rows > 0 && o->terrain_cols > 0 && o->vel_command_b_d,
                     "imx_reset_orchestrate: the terrain curriculum needs terrain origins, types, the grid size and the velocity command");
     }
-    if (o->has_command) {
+    IMX_REQUIRE(o->has_command >= 0 && o->has_command <= 2, "imx_reset_orchestrate: has_command is %d (0 none, 1 velocity, 2 pose)", o->has_command);
+    if (o->has_command == 2) {
+        need_root = true;
+        IMX_REQUIRE(!o->terrain_levels_d, "imx_reset_orchestrate: the terrain curriculum (terrain_levels_vel) reads a velocity command; the "
+                    "command term is a pose command");
+        IMX_REQUIRE(o->pose_command_b_d, "imx_reset_orchestrate: the pose command lacks pose_command_b");
+        IMX_REQUIRE(o->pose_command_w_d, "imx_reset_orchestrate: the pose command lacks pose_command_w");
+        IMX_REQUIRE(o->command_time_left_d && o->command_counter_d, "imx_reset_orchestrate: the pose command lacks its timer or counter");
+        IMX_REQUIRE(o->metric_error_vel_xy_d && o->metric_error_vel_yaw_d, "imx_reset_orchestrate: the pose command lacks a metric tensor");
+        IMX_REQUIRE(o->root_quat_w_d, "imx_reset_orchestrate: root_quat_w missing");
+        IMX_REQUIRE(o->body_pos_w_d && o->body_quat_w_d, "imx_reset_orchestrate: the pose command needs body_pos_w and body_quat_w");
+        IMX_REQUIRE(o->num_bodies > 0 && o->pose_body_idx >= 0 && o->pose_body_idx < o->num_bodies,
+                    "imx_reset_orchestrate: pose_body_idx %d outside [0, %lld)", o->pose_body_idx, (long long)o->num_bodies);
+        IMX_REQUIRE(o->command_cfg[1] > 0.0f, "imx_reset_orchestrate: resampling_time_range[1] must be positive");
+    }
+    if (o->has_command == 1) {
         need_vel = true;
         IMX_REQUIRE(o->root_quat_w_d && o->vel_command_b_d && o->heading_target_d && o->is_heading_env_d && o->is_standing_env_d &&
                     o->command_time_left_d && o->command_counter_d && o->metric_error_vel_xy_d && o->metric_error_vel_yaw_d,
@@ -340,7 +371,10 @@ extern "C" int imx_reset_orchestrate(const imx_orch_t* o, imx_stream_t stream) {
     if (o->lstm_hidden_d) IMX_REQUIRE(o->lstm_cell_d && o->lstm_layers > 0 && o->lstm_hidden_dim > 0 && o->num_joints > 0,
                                       "imx_reset_orchestrate: incomplete actuator-net state");
     const unsigned grid = (unsigned)((o->num_envs + ORCH_BLOCK - 1) / ORCH_BLOCK);
-    hipLaunchKernelGGL(k_reset_orchestrate, dim3(grid), dim3(ORCH_BLOCK), 0, (hipStream_t)stream, *o);
+    if (o->has_command == 2)
+        hipLaunchKernelGGL(k_reset_orchestrate<true>, dim3(grid), dim3(ORCH_BLOCK), 0, (hipStream_t)stream, *o);
+    else
+        hipLaunchKernelGGL(k_reset_orchestrate<false>, dim3(grid), dim3(ORCH_BLOCK), 0, (hipStream_t)stream, *o);
     IMX_HIP(hipGetLastError());
     return 0;
 }

@@ -4,6 +4,8 @@
 //   * CommandManager.compute / UniformVelocityCommand (isaaclab/managers/command_manager.py:122-187,
 //     isaaclab/envs/mdp/commands/velocity_command.py:111-160): metrics, resampling timer, uniform resampling,
 //     heading P-controller (wrap_to_pi), standing envs.
+//   * CommandManager.compute / UniformPoseCommand (isaaclab/envs/mdp/commands/pose_command.py:25-127): pose error metrics through the
+//     root pose, resampling timer, uniform position + Euler angle resampling (quat_from_euler_xyz, quat_unique).
 #include "imx_internal.h"
 #include "imx_producers.h"
 
@@ -117,6 +119,40 @@ extern "C" int imx_velocity_command(int64_t N, const float* cfg15, int heading_c
                    metric_error_vel_xy_d, metric_error_vel_yaw_d};
     hipLaunchKernelGGL(k_velocity_command, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, N, c, dt,
                        do_compute, root_quat_w_d, root_lin_vel_w_d, root_ang_vel_w_d, reset_mask_d, uniforms_d, seed, step_counter_d, st);
+    IMX_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------- pose command
+// lane = env (the per-env logic is pose_command_env, imx_producers.h: shared with the orchestration kernel); no LDS, no atomics
+__global__ void __launch_bounds__(256)
+k_pose_command(int64_t N, PoseCmdCfg c, float dt, int do_compute, const float* __restrict__ root_pos, const float* __restrict__ root_quat,
+               const float* __restrict__ body_pos, const float* __restrict__ body_quat, const uint8_t* __restrict__ reset_mask,
+               const float* __restrict__ uniforms, uint64_t seed, const int32_t* __restrict__ step_d, PoseCmdState s) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    const uint32_t step = step_d ? (uint32_t)step_d[0] : 0u;
+    float m0, m1;
+    pose_command_env(N, e, c, dt, do_compute, root_pos, root_quat, body_pos, body_quat, reset_mask && reset_mask[e], uniforms, seed, step,
+                     s, m0, m1);
+}
+
+extern "C" int imx_pose_command(int64_t N, const float* cfg16, int make_quat_unique, int64_t body_idx, int64_t num_bodies, float dt,
+                                int do_compute, const float* root_pos_w_d, const float* root_quat_w_d, const float* body_pos_w_d,
+                                const float* body_quat_w_d, const uint8_t* reset_mask_d, const float* uniforms_d, uint64_t seed,
+                                const int32_t* step_counter_d, float* pose_command_b_d, float* pose_command_w_d, float* time_left_d,
+                                int64_t* command_counter_d, float* metric_position_error_d, float* metric_orientation_error_d,
+                                imx_stream_t stream) {
+    IMX_REQUIRE(N > 0 && N < (1ll << 31) && cfg16, "imx_pose_command: bad arguments");
+    IMX_REQUIRE(root_pos_w_d && root_quat_w_d && body_pos_w_d && body_quat_w_d && pose_command_b_d && pose_command_w_d && time_left_d &&
+                    command_counter_d && metric_position_error_d && metric_orientation_error_d, "imx_pose_command: null argument");
+    IMX_REQUIRE(num_bodies > 0 && num_bodies < (1ll << 20) && body_idx >= 0 && body_idx < num_bodies,
+                "imx_pose_command: body_idx %lld outside [0, %lld)", (long long)body_idx, (long long)num_bodies);
+    IMX_REQUIRE(cfg16[1] > 0.0f, "imx_pose_command: resampling_time_range[1] must be positive");
+    const PoseCmdCfg c = pose_cmd_cfg_from16(cfg16, make_quat_unique != 0, (int)body_idx, (int)num_bodies);
+    PoseCmdState st{pose_command_b_d, pose_command_w_d, time_left_d, command_counter_d, metric_position_error_d, metric_orientation_error_d};
+    hipLaunchKernelGGL(k_pose_command, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, N, c, dt, do_compute,
+                       root_pos_w_d, root_quat_w_d, body_pos_w_d, body_quat_w_d, reset_mask_d, uniforms_d, seed, step_counter_d, st);
     IMX_HIP(hipGetLastError());
     return 0;
 }

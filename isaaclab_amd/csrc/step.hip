@@ -211,30 +211,10 @@ IMX_DEV float classic_reward(const PlanView& P, const imx_state_t& S, const imx_
 }
 
 // ---- manipulation/reach/mdp (isaaclab_tasks .../manipulation/reach/mdp: Isaac-Reach-Franka-v0, Isaac-Reach-UR10-v0)
-// quat_mul (utils/math.py:464-500): the reference's eight-product form with its association, quaternions w, x, y, z in .x .. .w
-IMX_DEV float4 quat_mul_ref(float4 a, float4 b) {
-    const float w1 = a.x, x1 = a.y, y1 = a.z, z1 = a.w, w2 = b.x, x2 = b.y, y2 = b.z, z2 = b.w;
-    const float ww = (z1 + x1) * (x2 + y2);
-    const float yy = (w1 - y1) * (w2 + z2);
-    const float zz = (w1 + y1) * (w2 - z2);
-    const float xx = ww + yy + zz;
-    const float qq = 0.5f * (xx + (z1 - x1) * (x2 - y2));
-    return make_float4(qq - ww + (z1 - y1) * (y2 - z2), qq - xx + (x1 + w1) * (x2 + w2), qq - yy + (w1 - x1) * (y2 + z2),
-                       qq - zz + (z1 + y1) * (w2 - x2));
-}
-// quat_error_magnitude(q1, q2) (utils/math.py:678-690) = ||axis_angle_from_quat(quat_mul(q1, quat_conjugate(q2)))||, axis_angle_from_quat
-// (:646-675) step by step: the w < 0 flip (q * (1 - 2 (w < 0))), half = atan2(||xyz||, w), angle = 2 half, the |angle| <= 1e-6 Taylor
-// branch 0.5 - angle^2 / 48, then xyz / that factor and its norm
+// quat_error_magnitude(q1, q2) (utils/math.py:678-690) = ||axis_angle_from_quat(quat_mul(q1, quat_conjugate(q2)))||; quat_mul_ref and
+// axis_angle_magnitude live in imx_internal.h (the pose command's metrics use them too)
 IMX_DEV float quat_error_magnitude(float4 q1, float4 q2) {
-    const float4 d = quat_mul_ref(q1, make_float4(q2.x, -q2.y, -q2.z, -q2.w));
-    const float sg = 1.0f - 2.0f * (d.x < 0.0f ? 1.0f : 0.0f);
-    const float w = d.x * sg, x = d.y * sg, y = d.z * sg, z = d.w * sg;
-    const float mag = sqrtf((x * x + y * y) + z * z);
-    const float half = atan2f(mag, w);
-    const float angle = 2.0f * half;
-    const float s = fabsf(angle) > 1.0e-6f ? sinf(half) / angle : 0.5f - angle * angle / 48.0f;
-    const float ax = x / s, ay = y / s, az = z / s;
-    return sqrtf((ax * ax + ay * ay) + az * az);
+    return axis_angle_magnitude(quat_mul_ref(q1, make_float4(q2.x, -q2.y, -q2.z, -q2.w)));
 }
 // The reward functions of manipulation/reach/mdp/rewards.py for env ec -- the raw value f.  Evaluated in phase 2 of k_term_rew<false,
 // true> (the classic terms' place: phase 2 holds far fewer live values than the phase-1 switch).  ids[0] = asset_cfg.body_ids[0].

@@ -398,7 +398,8 @@ class TerminationManager:
 
 
 class CommandManager:
-    """Commands come from the feed (UniformVelocityCommand is a SURVEY 8f 'next' row)."""
+    """Commands come from the env's own command term (``command_term=``: a ``producers.UniformVelocityCommand`` or
+    ``UniformPoseCommand``) or, without one, from the feed."""
 
     def __init__(self, env):
         self._env = env
@@ -407,6 +408,17 @@ class CommandManager:
         if self._env.command_term is not None:
             return self._env.command_term.command
         return self._env.feed["command"]
+
+    @property
+    def active_terms(self) -> list:
+        """Names of the env-owned command terms (command_manager.py:281-284); a command served by the feed has no term object."""
+        return [self._env.command_term_name] if self._env.command_term is not None else []
+
+    def get_term(self, name: str):
+        """The env-owned term (command_manager.py:376-386): ``time_left``, ``command_counter``, ``metrics``, ``command``."""
+        if self._env.command_term is None or name != self._env.command_term_name:
+            raise KeyError(f"command term '{name}' is not run by the env itself (its own terms: {self.active_terms}); pass command_term=")
+        return self._env.command_term
 
     def compute(self, dt: float):
         pass
@@ -547,16 +559,19 @@ class ManagerBasedRLEnv:
                  device: str | torch.device | None = None, seed: int | None = None, noise_seed: int = 0,
                  terrain_cell: float = 0.0, use_command_term: bool = False, use_contact_sensor: bool = False,
                  events_cfg: dict | bool | None = None, use_curriculum: bool = False, terrain_importer=None, own_managers: bool = False,
-                 **kwargs):
-        """``own_managers=True``: the env runs its cfg's EventManager (reset / interval terms), CommandManager (UniformVelocityCommand)
-        and CurriculumManager (terrain_levels_vel) itself -- ``_reset_idx`` + the command / interval updates of ``step`` as ONE
-        orchestration launch (``imx_reset_orchestrate``) -- instead of taking commands from the feed; the single switches
-        (``events_cfg`` = a dict or True for the cfg's own, ``use_command_term``, ``use_curriculum``) select parts of it.
+                 command_term=None, **kwargs):
+        """``own_managers=True``: the env runs its cfg's EventManager (reset / interval terms), CommandManager (UniformVelocityCommand or
+        UniformPoseCommand, by the term's ``class_type``) and CurriculumManager (terrain_levels_vel) itself -- ``_reset_idx`` + the
+        command / interval updates of ``step`` as ONE orchestration launch (``imx_reset_orchestrate``) -- instead of taking commands
+        from the feed; the single switches (``events_cfg`` = a dict or True for the cfg's own, ``command_term``, ``use_curriculum``)
+        select parts of it.  ``command_term``: the name of a command term of the cfg (``"ee_pose"``, ``"base_velocity"``), built by its
+        ``class_type``, or a ready ``producers.Uniform*Command``; ``use_command_term=True`` is the older velocity-only switch.
         ``terrain_importer``: an ``events.TerrainImporterState`` (default: built from the cfg's terrain generator grid)."""
         if own_managers:
             ec = cfg.get("env", cfg) if isinstance(cfg, dict) else None
             ec = ec if ec is not None else (load_task_cfg(cfg)["env"] if isinstance(cfg, str) else cfg.to_dict())
-            use_command_term = use_command_term or bool(ec.get("commands"))
+            if command_term is None and not use_command_term and ec.get("commands"):
+                command_term = next(iter(ec["commands"]))  # built by its class_type below
             events_cfg = events_cfg if events_cfg is not None else (True if ec.get("events") else None)
             use_curriculum = use_curriculum or any(v is not None for v in (ec.get("curriculum") or {}).values())
         if isinstance(cfg, str):
@@ -687,20 +702,54 @@ class ManagerBasedRLEnv:
         self.command_manager = CommandManager(self)
         # -- optional producers run by the env itself instead of arriving through the feed
         self.command_term = None
-        if use_command_term:
+        self.command_term_name: str | None = None
+        cmds = (env_dict.get("commands") or {})
+        if command_term is not None:
+            from .plan import command_width
+            from .producers import UniformPoseCommand, UniformVelocityCommand
+
+            if use_command_term:
+                raise ValueError("pass either command_term= or use_command_term=True, not both")
+            if isinstance(command_term, str):
+                if cmds.get(command_term) is None:
+                    raise ValueError(f"command_term='{command_term}': the env cfg has no such command term (it has {list(cmds)})")
+                ccfg = cmds[command_term]
+                cls = func_name_of(ccfg.get("class_type")) or ""
+                if command_width(ccfg) == 7:
+                    term = UniformPoseCommand(ccfg, N, plan.step_dt, self.device, seed=noise_seed, robot=plan.robot)
+                elif cls.endswith(":UniformVelocityCommand"):
+                    term = UniformVelocityCommand(ccfg, N, plan.step_dt, self.device, seed=noise_seed)
+                else:
+                    raise NotImplementedError(f"command_term='{command_term}': class_type '{cls}' has no fused producer (UniformVelocityCommand "
+                                              "and UniformPoseCommand have)")
+                self.command_term_name = command_term
+            elif isinstance(command_term, (UniformPoseCommand, UniformVelocityCommand)):
+                term = command_term
+                if term.num_envs != N or term.device != self.device:
+                    raise ValueError(f"command_term: the term has {term.num_envs} envs on {term.device}, the env {N} on {self.device}")
+                if isinstance(term, UniformPoseCommand) and term.num_bodies != plan.robot.num_bodies:
+                    raise ValueError(f"command_term: the pose command was built for {term.num_bodies} bodies, the robot has {plan.robot.num_bodies}")
+                self.command_term_name = next(iter(cmds), "command")
+            else:
+                raise TypeError(f"command_term: a command term's name or a producers.Uniform*Command, not {type(command_term).__name__}")
+            if term.command.shape[-1] != plan.cmd_dim:
+                raise ValueError(f"command_term: the term's command is {term.command.shape[-1]} wide, the plan's {plan.cmd_dim}")
+            self.command_term = term
+        elif use_command_term:
             from .producers import UniformVelocityCommand
 
-            cmds = (env_dict.get("commands") or {})
             if not cmds:
                 raise ValueError("use_command_term=True but the env cfg has no command terms")
             if plan.cmd_dim != 3:
-                raise NotImplementedError(f"use_command_term=True: this cfg's command is {plan.cmd_dim} wide (a UniformPoseCommand), which has "
-                                          "no fused producer yet; the env's own command term is a UniformVelocityCommand.  Take the "
-                                          "pose command from the state feed")
+                raise NotImplementedError(f"use_command_term=True: this cfg's command is {plan.cmd_dim} wide (a UniformPoseCommand); "
+                                          "use_command_term is the velocity-only switch.  Pass command_term=<the term's name> "
+                                          f"(here command_term='{next(iter(cmds))}') to run the env's own pose command")
             self.command_term = UniformVelocityCommand(next(iter(cmds.values())), N, plan.step_dt, self.device, seed=noise_seed)
+            self.command_term_name = next(iter(cmds))
         elif "command" in state_feed.names() and state_feed["command"].shape[-1] != plan.cmd_dim:
             raise ValueError(f"the state feed's command is {state_feed['command'].shape[-1]} wide, the plan's {plan.cmd_dim} "
                              f"(robot {state_feed.robot.name}: command_dim {state_feed.robot.command_dim})")
+        self._pose_command = self.command_term is not None and self.command_term.command.shape[-1] == 7  # has_command = 2
         self.contact_sensor = None
         if use_contact_sensor:
             from .producers import ContactSensorState
@@ -734,15 +783,19 @@ class ManagerBasedRLEnv:
         if use_curriculum:
             from .events import CurriculumManager, TerrainImporterState
 
+            # (first: a curriculum term without a kernel -- the Reach tasks' modify_reward_weight -- is refused by name, terrain or not)
+            self.curriculum_manager = CurriculumManager(env_dict.get("curriculum") or {}, self)
             if terrain_importer is None:
                 tg = ((env_dict.get("scene") or {}).get("terrain") or {}).get("terrain_generator")
                 if not tg:
                     raise ValueError("use_curriculum=True needs a terrain generator grid in the cfg or terrain_importer=")
                 terrain_importer = TerrainImporterState.from_generator_cfg(N, tg, self.device)
             self.terrain_importer = terrain_importer
-            self.curriculum_manager = CurriculumManager(env_dict.get("curriculum") or {}, self)
             if self.command_term is None:
                 raise ValueError("the terrain curriculum reads the env's own velocity command: use_command_term=True")
+            if self._pose_command and self.curriculum_manager.active_terms:
+                raise ValueError("the terrain curriculum (terrain_levels_vel) reads a velocity command; this env's command term "
+                                 f"'{self.command_term_name}' is a UniformPoseCommand")
         if self.event_manager is not None or self.command_term is not None or self.curriculum_manager is not None:
             init = ((env_dict.get("scene") or {}).get("robot") or {}).get("init_state") or {}
             drs = torch.zeros(N, 13, device=self.device)
@@ -772,9 +825,10 @@ class ManagerBasedRLEnv:
         base = len(names_r) + len(names_t) + 1  # (the slot before holds the reset count)
         ev_flags = 0
         if self.command_term is not None:  # CommandManager.reset (command_manager.py:340-358): "Metrics/{term}/{metric}"
-            cname = next(iter(env_dict.get("commands") or {"base_velocity": None}))
-            self._log_index[f"Metrics/{cname}/error_vel_xy"] = base
-            self._log_index[f"Metrics/{cname}/error_vel_yaw"] = base + 1
+            if len(self.command_term.metrics) != 2:
+                raise ValueError("the step tail has two log slots for the command term's metrics")
+            for i, m in enumerate(self.command_term.metrics):  # (error_vel_xy, error_vel_yaw) or (position_error, orientation_error)
+                self._log_index[f"Metrics/{self.command_term_name}/{m}"] = base + i
             ev_flags |= 1
         if self.curriculum_manager is not None:
             for n in self.curriculum_manager.active_terms:  # curriculum_manager.py:95-118
@@ -923,7 +977,7 @@ class ManagerBasedRLEnv:
             snap = self.feed.snapshot(idx)
             kw = {n: snap[n].data_ptr() for n in _lib.STATE_FIELDS if n in snap}
             if self.command_term is not None:
-                kw["command"] = self.command_term.vel_command_b.data_ptr()
+                kw["command"] = self.command_term.command.data_ptr()
                 kw["command_time_left"] = self.command_term.time_left.data_ptr()
                 kw["command_counter"] = self.command_term.command_counter.data_ptr()
             if self.articulation is not None:  # ArticulationData's own buffers (fixed addresses), filled by imx_articulation_update
@@ -1029,7 +1083,17 @@ class ManagerBasedRLEnv:
             o.terrain_rows, o.terrain_cols = int(ti.terrain_origins.shape[0]), int(ti.terrain_origins.shape[1])
             o.terrain_size_x, o.max_episode_length_s = float(ti.size_x), float(self.max_episode_length_s)
         ct = self.command_term
-        if ct is not None:
+        if ct is not None and self._pose_command:
+            o.has_command = 2
+            for k, v in enumerate(ct._cfg16):
+                o.command_cfg[k] = float(v)
+            o.pose_command_b_d, o.pose_command_w_d = p(ct.pose_command_b), p(ct.pose_command_w)
+            o.pose_body_idx, o.make_quat_unique = int(ct.body_idx), int(ct.make_quat_unique)
+            o.command_time_left_d, o.command_counter_d = p(ct.time_left), p(ct.command_counter)
+            # (the two metric slots of the launch: position_error, orientation_error -- ev_part columns 0 / 1 like the velocity metrics)
+            m0, m1 = ct.metrics.values()
+            o.metric_error_vel_xy_d, o.metric_error_vel_yaw_d = p(m0), p(m1)
+        elif ct is not None:
             o.has_command, o.heading_command = 1, int(ct.heading_command)
             for k, v in enumerate(ct._cfg15):
                 o.command_cfg[k] = float(v)
@@ -1065,6 +1129,8 @@ class ManagerBasedRLEnv:
         get = (lambda n: getattr(src, n)) if src is not None else (lambda n: f[n])
         o.root_pos_w_d, o.root_quat_w_d = get("root_pos_w").data_ptr(), get("root_quat_w").data_ptr()
         o.root_lin_vel_w_d, o.root_ang_vel_w_d = get("root_lin_vel_w").data_ptr(), get("root_ang_vel_w").data_ptr()
+        if self._pose_command:  # the body poses of the current snapshot, re-pointed per step like the root state
+            o.body_pos_w_d, o.body_quat_w_d = _lib.ptr(f["body_pos_w"]), _lib.ptr(f["body_quat_w"])
         if self.event_manager is not None:
             for i, t in enumerate(self.event_manager.terms):  # (parity runs re-point these between steps)
                 o.terms[i].uniforms_d, o.terms[i].interval_uniforms_d = _lib.ptr(t.uniforms), _lib.ptr(t.interval_uniforms)
@@ -1111,9 +1177,8 @@ class ManagerBasedRLEnv:
                 mask = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)
                 mask[ids] = True
             if self.command_term is not None:  # CommandTerm.reset logs the metrics before zeroing them (command_manager.py:123-149)
-                cname = [k for k in self._log_index if k.startswith("Metrics/")][0].split("/")[1]
-                for m in ("error_vel_xy", "error_vel_yaw"):
-                    log[f"Metrics/{cname}/{m}"] = torch.mean(self.command_term.metrics[m][ids])
+                for m, v in self.command_term.metrics.items():
+                    log[f"Metrics/{self.command_term_name}/{m}"] = torch.mean(v[ids])
             self._orchestrate(mask, do_step=False)
             if self.curriculum_manager is not None:
                 log.update(self.curriculum_manager.reset(ids))

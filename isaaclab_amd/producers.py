@@ -4,6 +4,8 @@
   isaaclab/sensors/contact_sensor/contact_sensor.py:140-210,320-379; isaaclab/sensors/sensor_base.py:182-205,287-297)
 * :class:`UniformVelocityCommand` -- ``CommandTerm.reset/compute`` + the uniform velocity command
   (isaaclab/managers/command_manager.py:119-187; isaaclab/envs/mdp/commands/velocity_command.py:37-160)
+* :class:`UniformPoseCommand` -- the same two steps for the uniform pose command of the Reach tasks
+  (isaaclab/envs/mdp/commands/pose_command.py:25-127)
 
 Attribute names follow the reference so that term functions reading ``sensor.data.*`` / ``command_manager`` keep working.
 """
@@ -122,6 +124,66 @@ class UniformVelocityCommand:
             self.command_counter.data_ptr(), self.metrics["error_vel_xy"].data_ptr(),
             self.metrics["error_vel_yaw"].data_ptr(), _lib.current_stream(self.device)))
         return self.vel_command_b
+
+
+class UniformPoseCommand:
+    """``cfg``: dict / object with the fields of ``UniformPoseCommandCfg`` (commands_cfg.py); ``robot``: a ``RobotSpec`` (or anything with
+    ``body_names``) through which ``cfg.body_name`` is resolved as ``robot.find_bodies(cfg.body_name)[0][0]`` does (pose_command.py:58-59).
+
+    The ``CommandTerm`` surface of the reference class: ``command`` (= ``pose_command_b``, (N, 7) position + w, x, y, z quaternion in the
+    base frame), ``pose_command_w``, ``time_left``, ``command_counter`` and ``metrics`` (``position_error``, ``orientation_error``)."""
+
+    def __init__(self, cfg, num_envs: int, step_dt: float, device="cuda:0", seed: int = 0, robot=None):
+        from .robots import resolve_matching_names
+
+        get = (lambda k, d=None: cfg.get(k, d)) if isinstance(cfg, dict) else (lambda k, d=None: getattr(cfg, k, d))
+        rng = get("ranges")
+        rget = (lambda k: rng.get(k)) if isinstance(rng, dict) else (lambda k: getattr(rng, k))
+        if robot is None:
+            raise ValueError("UniformPoseCommand needs robot= (its body names resolve cfg.body_name)")
+        self.body_name = get("body_name")
+        self.num_bodies = len(robot.body_names)
+        self.body_idx = int(resolve_matching_names(self.body_name, list(robot.body_names))[0][0])
+        self.make_quat_unique = bool(get("make_quat_unique", False))
+        rt = get("resampling_time_range")
+        self._cfg16 = np.asarray([rt[0], rt[1], *rget("pos_x"), *rget("pos_y"), *rget("pos_z"), *rget("roll"), *rget("pitch"),
+                                  *rget("yaw"), 0.0, 0.0], dtype=np.float32)
+        N = num_envs
+        dev = torch.device(device)
+        self.num_envs, self.device, self.seed, self.step_dt = N, dev, int(seed), float(step_dt)
+        self.pose_command_b = torch.zeros(N, 7, device=dev)
+        self.pose_command_b[:, 3] = 1.0  # pose_command.py:63-64
+        self.pose_command_w = torch.zeros(N, 7, device=dev)
+        self.time_left = torch.zeros(N, device=dev)
+        self.command_counter = torch.zeros(N, dtype=torch.long, device=dev)
+        self.metrics = {"position_error": torch.zeros(N, device=dev), "orientation_error": torch.zeros(N, device=dev)}
+        self._step = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    @property
+    def command(self) -> torch.Tensor:
+        return self.pose_command_b
+
+    def compute(self, dt: float, root_pos_w, root_quat_w, body_pos_w, body_quat_w, reset_mask=None, uniforms=None,
+                do_compute: bool = True):
+        """``reset(ids of reset_mask)`` then (``do_compute``) ``compute(dt)``; ``body_pos_w`` (N, NB, 3) / ``body_quat_w`` (N, NB, 4);
+        ``uniforms``: optional (2,N,7) parity samples."""
+        N, NB = self.num_envs, self.num_bodies
+        for name, t, shape in (("root_pos_w", root_pos_w, (N, 3)), ("root_quat_w", root_quat_w, (N, 4)),
+                               ("body_pos_w", body_pos_w, (N, NB, 3)), ("body_quat_w", body_quat_w, (N, NB, 4))):
+            if tuple(t.shape) != shape or t.dtype != torch.float32:
+                raise ValueError(f"UniformPoseCommand.compute: {name} is {tuple(t.shape)} {t.dtype}, expected {shape} float32")
+        if reset_mask is not None and reset_mask.numel() != N:
+            raise ValueError(f"UniformPoseCommand.compute: reset_mask has {reset_mask.numel()} entries for {N} envs")
+        if uniforms is not None and (tuple(uniforms.shape) != (2, N, 7) or uniforms.dtype != torch.float32):
+            raise ValueError(f"UniformPoseCommand.compute: uniforms is {tuple(uniforms.shape)} {uniforms.dtype}, expected (2, {N}, 7) float32")
+        self._step += 1
+        check(lib().imx_pose_command(
+            N, self._cfg16.ctypes.data, int(self.make_quat_unique), self.body_idx, NB, float(dt), int(do_compute),
+            _lib.ptr(root_pos_w), _lib.ptr(root_quat_w), _lib.ptr(body_pos_w), _lib.ptr(body_quat_w), _lib.ptr(reset_mask),
+            _lib.ptr(uniforms), self.seed, self._step.data_ptr(), self.pose_command_b.data_ptr(), self.pose_command_w.data_ptr(),
+            self.time_left.data_ptr(), self.command_counter.data_ptr(), self.metrics["position_error"].data_ptr(),
+            self.metrics["orientation_error"].data_ptr(), _lib.current_stream(self.device)))
+        return self.pose_command_b
 
 
 class ArticulationRootState:

@@ -2,7 +2,8 @@
 CommandManager / CurriculumManager) against oracle/orchestration_oracle.py (pinned by the real-manager fixture): the fixture's cfg, scene
 and state snapshots, but RANDOM draw tables, actions, episode lengths and step counts -- other reset patterns, timer phases, curriculum
 moves and resampling sequences than the 48 recorded steps.  Simulator writes, trigger state, timers, levels / origins exact or 1e-5.
-Test infrastructure, run on the GPU box:  python tools/fuzz_orchestration.py [cases] [seed]"""
+``one_case_pose`` is the same sweep over the Franka Reach cfg with the env's own UniformPoseCommand (``has_command = 2``).
+Test infrastructure, run on the GPU box:  python tools/fuzz_orchestration.py [cases] [seed] [pose]"""
 import os
 import sys
 
@@ -107,9 +108,98 @@ def one_case(seed: int) -> str:
     return f"steps={steps} resets={resets} pushes={pushes} mean level {float(orc.levels.float().mean()):.2f}"
 
 
+_RG = None
+
+
+def one_case_pose(seed: int) -> str:
+    """The same launch with ``has_command = 2``: the Franka Reach cfg of tests/golden/reach_orchestration.json (UniformPoseCommand +
+    reset_joints_by_scale) with RANDOM draw tables, actions, episode lengths and step counts, against tests/_pose_command_oracle.py and
+    oracle/events_oracle.py.  A separate entry point: ``one_case`` consumes its generators exactly as before."""
+    global _RG
+    from _pose_command_cases import ReachOrchGolden, w_margin_ok
+    from _pose_command_oracle import PoseCommandOracle
+    from oracle import events_oracle as evo
+
+    g = _RG = _RG or ReachOrchGolden()
+    rng = np.random.default_rng(seed)
+    gen = torch.Generator().manual_seed(int(rng.integers(0, 1 << 30)))
+    N, J, meta = g.N, g.robot.num_joints, g.meta
+    fx = g.fixture
+    ccfg = dict(fx["env"]["commands"]["ee_pose"])
+    if rng.integers(0, 2):  # the other branch of _resample_command: every angle free, quat_unique
+        ccfg["make_quat_unique"] = True
+        ccfg["ranges"] = dict(ccfg["ranges"], roll=(-3.14, 3.14), pitch=(-3.14, 3.14))
+    lo = float(rng.choice([0.5, 2.0, 5.0])) * meta["step_dt"]  # 0.5: reset and timer resample in one step (draw 1)
+    ccfg["resampling_time_range"] = (lo, lo * float(rng.choice([1.0, 2.0, 3.0])))
+    fx = dict(fx, env=dict(fx["env"], commands={"ee_pose": ccfg}))
+    env = ManagerBasedRLEnv(fx, state_feed=g.feed("cuda:0"), own_managers=True)
+    cpu_feed = g.feed("cpu")
+    ct, term = env.command_term, env.event_manager.get_term("reset_robot_joints")
+    orc = PoseCommandOracle(ccfg, N, meta["step_dt"], ct.body_idx)
+    p = fx["env"]["events"]["reset_robot_joints"]["params"]
+    djp, djv, plim, vlim = (g.t("static/" + n) for n in ("default_joint_pos", "default_joint_vel", "soft_joint_pos_limits", "soft_joint_vel_limits"))
+    joint_pos, joint_vel = torch.zeros(N, J), torch.zeros(N, J)
+
+    def draws():
+        d = {"reset_robot_joints": torch.rand(N, 2 * J, generator=gen), "command": torch.rand(2, N, 7, generator=gen)}
+        while ccfg.get("make_quat_unique") and not w_margin_ok(ccfg, d["command"]):
+            d["command"] = torch.rand(2, N, 7, generator=gen)
+        term.uniforms = d["reset_robot_joints"].cuda().contiguous()
+        env._orch_draws["command"] = d["command"].cuda().contiguous()
+        return d
+
+    def run_oracle(mask, d, do_compute):
+        ids = mask.nonzero().flatten()
+        if len(ids):  # reset_joints_by_scale (events.py:987-1021); no min_step_count_between_reset: every reset env is valid
+            u = d["reset_robot_joints"]
+            joint_pos[ids], joint_vel[ids] = evo.reset_joints(djp[ids], djv[ids], plim[ids], vlim[ids], tuple(p["position_range"]),
+                                                              tuple(p["velocity_range"]), u[ids, :J], u[ids, J:2 * J], by_offset=False)
+        f = cpu_feed
+        orc.reset_and_compute(meta["step_dt"], f["root_pos_w"], f["root_quat_w"], f["body_pos_w"], f["body_quat_w"], mask, d["command"],
+                              do_compute=do_compute)
+
+    def check(tag):
+        torch.cuda.synchronize()
+        assert_close(env.sim_writes["joint_pos"], joint_pos, FLOAT_TOL, f"{tag} sim_writes[joint_pos]")
+        assert_close(env.sim_writes["joint_vel"], joint_vel, FLOAT_TOL, f"{tag} sim_writes[joint_vel]")
+        for k, a, b in (("command", ct.command, orc.command), ("pose_command_w", ct.pose_command_w, orc.pose_command_w),
+                        ("time_left", ct.time_left, orc.time_left), ("position_error", ct.metrics["position_error"], orc.metrics["position_error"]),
+                        ("orientation_error", ct.metrics["orientation_error"], orc.metrics["orientation_error"])):
+            assert_close(a, b, FLOAT_TOL, f"{tag} {k}")
+        assert torch.equal(ct.command_counter.cpu(), orc.command_counter), f"{tag} command counter"
+
+    d = draws()
+    env.reset()
+    run_oracle(torch.ones(N, dtype=torch.bool), d, False)
+    check("reset")
+    ep = torch.randint(0, env.max_episode_length, (N,), generator=gen)
+    ep[:: int(rng.choice([2, 3, 7]))] = env.max_episode_length - int(rng.integers(1, 4))
+    env.episode_length_buf = ep
+    steps = int(rng.integers(5, 40))
+    resets = twice = 0
+    for s in range(steps):
+        d = draws()
+        _, _, _, _, extras = env.step((torch.randn(N, env.plan.action_dim, generator=gen)).clamp(-3, 3).cuda())
+        cpu_feed.advance()
+        mask = torch.zeros(N, dtype=torch.bool)
+        mask[env.reset_env_ids.cpu()] = True
+        logged = {m: float(torch.mean(v[mask])) for m, v in orc.metrics.items()} if mask.any() else {}
+        run_oracle(mask, d, True)
+        resets += int(mask.sum())
+        twice += int((orc._draw == 2).sum())
+        check(f"step {s}")
+        for m, v in logged.items():  # CommandTerm.reset logs the mean over the reset envs before zeroing
+            got = float(extras["log"][f"Metrics/ee_pose/{m}"])
+            assert abs(got - v) <= FLOAT_TOL * max(1.0, abs(v)), (s, m, got, v)
+    env.close()
+    return f"steps={steps} resets={resets} resampled twice in a step={twice} unique={bool(ccfg.get('make_quat_unique'))} resample={ccfg['resampling_time_range']}"
+
+
 if __name__ == "__main__":
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     first = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    pose = "pose" in sys.argv[3:]
+    one_case = one_case_pose if pose else one_case
     bad = 0
     for c in range(first, first + cases):
         try:

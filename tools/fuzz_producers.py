@@ -1,6 +1,7 @@
 """Random sweeps of the stateful producers against their oracles (which the reference's fixtures pin): ContactSensor update (random
 body / history counts, update period gating, thresholds, forces, partial resets), UniformVelocityCommand (random ranges, heading /
-standing fractions, resampling windows shorter and longer than a step, resets, fed uniforms), and -- against the oracles run in float64,
+standing fractions, resampling windows shorter and longer than a step, resets, fed uniforms), UniformPoseCommand (the same, against
+tests/_pose_command_oracle.py), and -- against the oracles run in float64,
 cases in tests/_producer_cases.py -- the delayed / remotized PD actuator, the LSTM and MLP actuator nets, the empirical normaliser and the
 reset / interval events with the terrain curriculum.  lstm_net picks one of the three ANYdrive-shape kernels per case; the two that
 IMX_LSTM_KERNEL selects run in a persistent child process each.  Test infrastructure, run on the GPU box:
@@ -89,6 +90,18 @@ def case_command(rng):
         assert_close(cmd.metrics["error_vel_xy"], orc.metrics["error_vel_xy"], 1e-5, "error_vel_xy")
         assert_close(cmd.metrics["error_vel_yaw"], orc.metrics["error_vel_yaw"], 1e-5, "error_vel_yaw")
     return f"N={N} step_dt={step_dt} resample={cfg['resampling_time_range']} heading={cfg['heading_command']} steps={steps}"
+
+
+def case_pose_command(rng):
+    """UniformPoseCommand: random ranges, body counts and indices, quat_unique on / off, resampling windows shorter and longer than a
+    step (shorter: reset and timer resample in one call), reset masks all / none / mixed, do_compute 0 / 1, fed uniforms."""
+    from _pose_command_cases import pose_case, random_cfg
+
+    N, step_dt = int(rng.choice([1, 63, 64, 65, 257, 1000, 4096])), float(rng.choice([1.0 / 30.0, 0.02, 0.005]))
+    NB = int(rng.choice([1, 8, 11, 30]))
+    cfg = random_cfg(rng, step_dt, bool(rng.integers(0, 2)), bool(rng.integers(0, 2)))
+    plan = [(str(rng.choice(["all", "none", "mixed"])), bool(rng.random() < 0.8)) for _ in range(int(rng.integers(3, 12)))]
+    return pose_case(N, NB, int(rng.integers(0, NB)), cfg, step_dt, plan, int(rng.integers(0, 1 << 30)))
 
 
 def case_pd_actuator(rng):
@@ -231,7 +244,7 @@ def case_events(rng):
     return events_case(N, J, NB, R, C, int(rng.integers(0, 1 << 30)), body_ids=ids, degenerate=bool(rng.integers(0, 2)))
 
 
-KINDS = (("contact_sensor", case_contact), ("velocity_command", case_command), ("pd_actuator", case_pd_actuator), ("articulation", case_articulation),
+KINDS = (("contact_sensor", case_contact), ("velocity_command", case_command), ("pose_command", case_pose_command), ("pd_actuator", case_pd_actuator), ("articulation", case_articulation),
          ("delayed", case_delayed), ("remotized", case_remotized), ("lstm_net", case_lstm_net), ("mlp_net", case_mlp_net),
          ("normalizer", case_normalizer), ("events", case_events))
 

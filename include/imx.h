@@ -47,7 +47,9 @@ enum imx_header_word {
     IMX_H_SCAN_PERIOD /* f32 cfg.update_period */, IMX_H_SCAN_DT /* f32 physics dt: SensorBase.update(dt) per physics step */,
     IMX_H_SCAN_SUBSTEPS /* decimation: update() calls per env step */, IMX_H_SCAN_DRIFT_LO /* f32 cfg.drift_range */,
     IMX_H_SCAN_DRIFT_HI, IMX_H_SCAN_STATEFUL /* 1: per-env timestamps / drift are kept (imx_buffers.scan_state) */,
-    IMX_H_TERM_SLOTS /* per-env reward-term state slots (imx_buffers.term_state rows): one per IMX_W_PROGRESS_REWARD record */
+    IMX_H_TERM_SLOTS /* per-env reward-term state slots (imx_buffers.term_state rows): one per IMX_W_PROGRESS_REWARD record */,
+    IMX_H_PA /* width of buf.processed_action (joint targets of all action terms side by side); 0 = IMX_H_A: every term writes as many
+                processed columns as it takes raw ones.  Differs for a IMX_A_BINARY_JOINT term (1 raw column, NIDS targets) */
 };
 
 /* record layout (IMX_REC_WORDS int32/f32 words) */
@@ -100,13 +102,16 @@ enum imx_term_op {
     IMX_T_ILLEGAL_CONTACT,         /* :150-158  ids=bodies p0=threshold */
     IMX_T_JOINT_POS_MANUAL_LIMIT,  /* :90-105   ids=joints p0=lo p1=hi */
     IMX_T_BAD_ORIENTATION,         /* :50-59    p0=limit_angle */
-    IMX_T_ROOT_HEIGHT_BELOW_MIN,   /* :62-72    p0=minimum_height */
+    IMX_T_ROOT_HEIGHT_BELOW_MIN,   /* :62-72    p0=minimum_height; aux0 = the asset: 0 robot root (state.root_pos_w), 1 the rigid object
+                                                (state.object_root_pos_w) */
     IMX_T_JOINT_VEL_LIMIT,         /* :108-114  ids=joints */
     IMX_T_JOINT_VEL_MANUAL_LIMIT,  /* :117-124  ids=joints p0=max_velocity */
     IMX_T_JOINT_EFFORT_LIMIT,      /* :127-142  ids=joints (torch.isclose(computed, applied)) */
     IMX_T_TERRAIN_OUT_OF_BOUNDS,   /* isaaclab_tasks .../velocity/mdp/terminations.py:24-52  p0=x_lim p1=y_lim */
     IMX_T_EXTERNAL,                /* value computed by a Python term; aux0 = column in ext_term */
-    IMX_T_COMMAND_RESAMPLE         /* :35-42    p0 = f32(step_dt), nids = num_resamples; state.command_time_left / command_counter */
+    IMX_T_COMMAND_RESAMPLE,        /* :35-42    p0 = f32(step_dt), nids = num_resamples; state.command_time_left / command_counter */
+    IMX_T_OBJECT_REACHED_GOAL      /* isaaclab_tasks .../manipulation/lift/mdp/terminations.py:25-53  ||des_pos_w - object_root_pos_w|| < p0
+                                      (threshold); des_pos_w as for the reach rewards, CMD == 7 */
 };
 
 /* reward ops -- envs/mdp/rewards.py unless noted */
@@ -169,8 +174,15 @@ enum imx_rew_op {
        cmd[:3]) (combine_frame_transforms, utils/math.py:750-786 -> quat_apply :546-566) */
     IMX_W_POSITION_COMMAND_ERROR,     /* :19-33  ||body_pos_w[:, id] - des_pos_w|| */
     IMX_W_POSITION_COMMAND_ERROR_TANH,/* :36-53  1 - tanh(||body_pos_w[:, id] - des_pos_w|| / p0), p0 = std */
-    IMX_W_ORIENTATION_COMMAND_ERROR   /* :56-72  quat_error_magnitude(body_quat_w[:, id], quat_mul(root_quat_w, cmd[3:7])) (math.py:678-690:
+    IMX_W_ORIENTATION_COMMAND_ERROR,  /* :56-72  quat_error_magnitude(body_quat_w[:, id], quat_mul(root_quat_w, cmd[3:7])) (math.py:678-690:
                                                   ||axis_angle_from_quat(quat_mul(q1, quat_conjugate(q2)))||, :646-675) */
+    /* isaaclab_tasks .../manipulation/lift/mdp/rewards.py (Isaac-Lift-Cube-Franka-v0); the object = state.object_root_pos_w */
+    IMX_W_OBJECT_IS_LIFTED,           /* :20-25  object z > p0 (minimal_height) -> 1 / 0 */
+    IMX_W_OBJECT_EE_DISTANCE,         /* :28-45  1 - tanh(||object - ee_w|| / p0), p0 = std; ee_w = the FrameTransformer's first target frame =
+                                                  body_pos_w[:, id] + quat_apply(body_quat_w[:, id], (p1, p2, p3)): ids = the ONE robot body the frame
+                                                  sits on, p1..p3 = its offset position (frame_transformer.py:358; identity offset rotation) */
+    IMX_W_OBJECT_GOAL_DISTANCE        /* :48-67  (object z > p1) * (1 - tanh(||des_pos_w - object|| / p0)), p0 = std, p1 = minimal_height;
+                                                  des_pos_w as for the reach rewards, CMD == 7 */
 };
 
 /* observation ops -- envs/mdp/observations.py */
@@ -197,12 +209,21 @@ enum imx_obs_op {
     IMX_O_BASE_UP_PROJ,     /* :33-40  -projected_gravity_b.z */
     IMX_O_BASE_HEADING_PROJ,/* :43-58  p0..p2 = target_pos: quat_rotate(q, FORWARD_VEC_B) . normalize((target - pos) * (1, 1, 0)) */
     IMX_O_BASE_ANGLE_TO_TARGET, /* :61-77 p0..p2 = target_pos */
-    IMX_O_BODY_INCOMING_WRENCH  /* envs/mdp/observations.py:176-185 ids = asset bodies; 6 columns per body in id order;
+    IMX_O_BODY_INCOMING_WRENCH, /* envs/mdp/observations.py:176-185 ids = asset bodies; 6 columns per body in id order;
                                    state.link_incoming_joint_force */
+    IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME /* isaaclab_tasks .../manipulation/lift/mdp/observations.py:19-31  3 columns:
+                                   quat_apply(quat_inv(root_quat_w), object_root_pos_w - root_pos_w) (subtract_frame_transforms,
+                                   utils/math.py:785-816; quat_inv = normalize(conjugate), :239-248) */
 };
 
-/* action ops -- envs/mdp/actions/joint_actions.py:130-139 (raw*scale+offset[,clamp]) */
-enum imx_act_op { IMX_A_JOINT_AFFINE = 1 };
+/* action ops.  A record takes the raw columns [OUT, OUT + DIM) of the action and writes the processed columns [PCOL, PCOL + NIDS) of
+ * buf.processed_action (row width IMX_H_PA), PCOL = the record's IMX_R_P2 word (int; 0 = OUT, as in every plan whose terms are all
+ * IMX_A_JOINT_AFFINE).
+ *   IMX_A_JOINT_AFFINE  envs/mdp/actions/joint_actions.py:130-139 (raw*scale+offset[,clamp]); DIM == NIDS
+ *   IMX_A_BINARY_JOINT  BinaryJointPositionAction / BinaryJointVelocityAction (binary_joint_actions.py:118-133): DIM == 1; every one of the
+ *                       NIDS joints gets its entry of the close table (AUX1) where the raw action is < 0, else of the open table (AUX0);
+ *                       NIDS floats each, the term's clip already applied to both (clamp commutes with the selection) */
+enum imx_act_op { IMX_A_JOINT_AFFINE = 1, IMX_A_BINARY_JOINT };
 
 /* ---- per-step inputs: the tensors ArticulationData / ContactSensorData / CommandManager expose ---------------- */
 typedef struct imx_state {
@@ -238,6 +259,8 @@ typedef struct imx_state {
                                                unless a term reads it */
     const float* body_quat_w;           /* (N,NB,4) ArticulationData.body_quat_w w,x,y,z = body_state_w[..., 3:7] (articulation_data.py:776-782), or NULL
                                            unless a term reads it (orientation_command_error) */
+    const float* object_root_pos_w;     /* (N,3) RigidObjectData.root_pos_w of the scene's rigid object ("object"), or NULL unless a term reads
+                                           it (the manipulation/lift terms, root_height_below_minimum on the object) */
 } imx_state_t;
 
 /* ---- manager state + outputs (caller-owned, persistent across steps) ------------------------------------------ */
@@ -245,7 +268,7 @@ typedef struct imx_buffers {
     int64_t* episode_length_buf; /* (N)   envs/manager_based_rl_env.py:200 */
     float* action;               /* (N,A) managers/action_manager.py:318-331 */
     float* prev_action;          /* (N,A) */
-    float* processed_action;     /* (N,A) */
+    float* processed_action;     /* (N,PA), PA = IMX_H_PA (= A unless a term's processed width differs from its raw width) */
     float* reward_buf;           /* (N)   managers/reward_manager.py:128-157 */
     float* episode_sums;         /* (NREW_ALL,N) */
     float* step_reward;          /* (N,NREW_ALL) */

@@ -17,7 +17,7 @@ STATE_FIELDS = (
     "soft_joint_vel_limits", "body_lin_vel_w", "command", "net_forces_w_history", "last_air_time",
     "current_air_time", "current_contact_time", "env_origins", "ext_reward", "ext_term", "ext_obs",
     "body_lin_acc_w", "command_time_left", "command_counter", "body_pos_w", "last_contact_time", "link_incoming_joint_force",
-    "body_quat_w",
+    "body_quat_w", "object_root_pos_w",
 )
 BUFFER_FIELDS = (
     "episode_length_buf", "action", "prev_action", "processed_action", "reward_buf", "episode_sums", "step_reward",

@@ -76,6 +76,8 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
     p->act_off = w[IMX_H_ACT_OFF]; p->ray_off = w[IMX_H_RAY_OFF];
     IMX_REQUIRE(p->J >= 0 && p->J <= 4096 && p->B >= 0 && p->B <= 4096 && p->H >= 0 && p->H <= 64, "plan: bad J/B/H");
     IMX_REQUIRE(p->A >= 0 && p->A <= 4096 && p->D >= 0 && p->D <= 65535 && p->R >= 0 && p->R <= 65535, "plan: bad A/D/R");
+    p->PA = w[IMX_H_PA] ? w[IMX_H_PA] : p->A;
+    IMX_REQUIRE(p->PA >= 0 && p->PA <= 4096, "plan: bad processed action width %d", p->PA);
     IMX_REQUIRE(p->nterm >= 0 && p->nterm <= 32, "plan: at most 32 termination terms are supported (got %d)", p->nterm);
     IMX_REQUIRE(p->nrew >= 0 && p->nrew == p->nrew_all && p->nrew_all <= 256, "plan: bad reward term counts (every term carries a record)");
     p->ngroups = w[IMX_H_NGROUPS];
@@ -99,19 +101,23 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
     for (int k = 0; k < p->nterm; ++k) {
         const int32_t* r = &w[p->term_off + k * IMX_REC_WORDS];
         const int op = r[IMX_R_OP];
-        IMX_REQUIRE(op >= IMX_T_TIME_OUT && op <= IMX_T_COMMAND_RESAMPLE, "plan: unknown termination op %d", op);
+        IMX_REQUIRE(op >= IMX_T_TIME_OUT && op <= IMX_T_OBJECT_REACHED_GOAL, "plan: unknown termination op %d", op);
         IMX_REQUIRE(r[IMX_R_OUT] == k, "plan: termination record %d has index %d", k, r[IMX_R_OUT]);
         const bool body = op == IMX_T_ILLEGAL_CONTACT;
         if (op != IMX_T_COMMAND_RESAMPLE &&  // its NIDS word is num_resamples, not a list length
             check_ids(w, r[IMX_R_IDS_OFF], r[IMX_R_NIDS], body ? p->B : p->J, body ? "body" : "joint", k)) return 1;
         if (op == IMX_T_EXTERNAL)
             IMX_REQUIRE(r[IMX_R_AUX0] >= 0 && r[IMX_R_AUX0] < w[IMX_H_NEXT_TERM], "plan: ext_term column out of range");
+        if (op == IMX_T_ROOT_HEIGHT_BELOW_MIN)
+            IMX_REQUIRE(r[IMX_R_AUX0] == 0 || r[IMX_R_AUX0] == 1, "plan: termination record %d: asset selector %d (0 robot, 1 object)", k, r[IMX_R_AUX0]);
+        if (op == IMX_T_OBJECT_REACHED_GOAL)
+            IMX_REQUIRE(p->CMD == 7, "plan: termination record %d (object_reached_goal) needs a 7-wide pose command (CMD=%d)", k, p->CMD);
     }
     // ---- rewards
     for (int k = 0; k < p->nrew; ++k) {
         const int32_t* r = &w[p->rew_off + k * IMX_REC_WORDS];
         const int op = r[IMX_R_OP];
-        IMX_REQUIRE(op >= IMX_W_IS_ALIVE && op <= IMX_W_ORIENTATION_COMMAND_ERROR, "plan: unknown reward op %d", op);
+        IMX_REQUIRE(op >= IMX_W_IS_ALIVE && op <= IMX_W_OBJECT_GOAL_DISTANCE, "plan: unknown reward op %d", op);
         IMX_REQUIRE(r[IMX_R_OUT] == k, "plan: reward record %d has index %d", k, r[IMX_R_OUT]);
         int limit = p->J;
         const char* what = "joint";
@@ -124,7 +130,7 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
             limit = p->nterm;
             what = "termination-term";
         } else if (op == IMX_W_BODY_LIN_ACC_L2 || op == IMX_W_FOOT_CLEARANCE_REWARD || op == IMX_W_POSITION_COMMAND_ERROR ||
-                   op == IMX_W_POSITION_COMMAND_ERROR_TANH || op == IMX_W_ORIENTATION_COMMAND_ERROR) {
+                   op == IMX_W_POSITION_COMMAND_ERROR_TANH || op == IMX_W_ORIENTATION_COMMAND_ERROR || op == IMX_W_OBJECT_EE_DISTANCE) {
             limit = p->NB;
             what = "asset body";
         }
@@ -135,6 +141,9 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
         if (op == IMX_W_POSITION_COMMAND_ERROR || op == IMX_W_POSITION_COMMAND_ERROR_TANH || op == IMX_W_ORIENTATION_COMMAND_ERROR)
             IMX_REQUIRE(r[IMX_R_NIDS] == 1 && p->CMD == 7, "plan: reward record %d (op %d) needs one body and a 7-wide pose command (CMD=%d)",
                         k, op, p->CMD);
+        if (op == IMX_W_OBJECT_EE_DISTANCE) IMX_REQUIRE(r[IMX_R_NIDS] == 1, "plan: reward record %d (object_ee_distance) needs the one body of its frame", k);
+        if (op == IMX_W_OBJECT_GOAL_DISTANCE)
+            IMX_REQUIRE(p->CMD == 7, "plan: reward record %d (object_goal_distance) needs a 7-wide pose command (CMD=%d)", k, p->CMD);
         if (op == IMX_W_PROGRESS_REWARD)
             IMX_REQUIRE(r[IMX_R_AUX0] >= 0 && r[IMX_R_AUX0] < p->term_slots, "plan: reward record %d: state slot %d outside [0, %d)", k,
                         r[IMX_R_AUX0], p->term_slots);
@@ -168,7 +177,7 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
     for (int k = 0; k < p->nobs; ++k) {
         const int32_t* r = &w[p->obs_off + k * IMX_REC_WORDS];
         const int op = r[IMX_R_OP];
-        IMX_REQUIRE(op >= IMX_O_BASE_POS_Z && op <= IMX_O_BODY_INCOMING_WRENCH, "plan: unknown observation op %d", op);
+        IMX_REQUIRE(op >= IMX_O_BASE_POS_Z && op <= IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME, "plan: unknown observation op %d", op);
         const int g = r[IMX_R_WEIGHT];
         IMX_REQUIRE(g >= 0 && g < p->ngroups, "plan: observation record %d names group %d", k, g);
         {
@@ -209,6 +218,7 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
         if (op == IMX_O_BASE_YAW_ROLL) IMX_REQUIRE(d == 2, "plan: base_yaw_roll must have dim 2");
         if (op == IMX_O_BASE_UP_PROJ || op == IMX_O_BASE_HEADING_PROJ || op == IMX_O_BASE_ANGLE_TO_TARGET)
             IMX_REQUIRE(d == 1, "plan: observation op %d must have dim 1", op);
+        if (op == IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME) IMX_REQUIRE(d == 3, "plan: object_position_in_robot_root_frame must have dim 3");
         if (op == IMX_O_LAST_ACTION) IMX_REQUIRE(d == p->A, "plan: last_action dim %d != A=%d", d, p->A);
         if (op == IMX_O_GENERATED_COMMANDS) IMX_REQUIRE(d == p->CMD, "plan: command dim mismatch");
         if (op == IMX_O_EXTERNAL)
@@ -256,16 +266,24 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
                     "plan: bad height-scanner update period / drift words");
     }
     // ---- actions
-    int acols = 0;
+    int acols = 0, pcols = 0;
     for (int k = 0; k < p->nact; ++k) {
         const int32_t* r = &w[p->act_off + k * IMX_REC_WORDS];
-        IMX_REQUIRE(r[IMX_R_OP] == IMX_A_JOINT_AFFINE, "plan: unknown action op %d", r[IMX_R_OP]);
-        IMX_REQUIRE(r[IMX_R_OUT] == acols && r[IMX_R_DIM] == r[IMX_R_NIDS], "plan: action record %d layout", k);
+        const int op = r[IMX_R_OP];
+        IMX_REQUIRE(op == IMX_A_JOINT_AFFINE || op == IMX_A_BINARY_JOINT, "plan: unknown action op %d", op);
+        IMX_REQUIRE(r[IMX_R_OUT] == acols && r[IMX_R_DIM] == (op == IMX_A_BINARY_JOINT ? 1 : r[IMX_R_NIDS]), "plan: action record %d layout", k);
+        IMX_REQUIRE((r[IMX_R_P2] ? r[IMX_R_P2] : acols) == pcols, "plan: action record %d: processed column %d, expected %d", k, r[IMX_R_P2], pcols);
         if (check_ids(w, r[IMX_R_IDS_OFF], r[IMX_R_NIDS], p->J, "joint", k)) return 1;
+        if (op == IMX_A_BINARY_JOINT)  // open / close tables, one float per joint
+            for (int aux : {IMX_R_AUX0, IMX_R_AUX1})
+                IMX_REQUIRE(r[IMX_R_NIDS] > 0 && r[aux] >= IMX_HEADER_WORDS && (size_t)r[aux] + (size_t)r[IMX_R_NIDS] <= nwords,
+                            "plan: action record %d: open / close table out of range", k);
         // optional per-joint scale / offset / clip tables (dim floats each) referenced by aux words
         acols += r[IMX_R_DIM];
+        pcols += r[IMX_R_NIDS];
     }
     IMX_REQUIRE(acols == p->A || p->nact == 0, "plan: action terms cover %d columns, A=%d", acols, p->A);
+    IMX_REQUIRE(pcols == p->PA || p->nact == 0, "plan: action terms write %d processed columns, PA=%d", pcols, p->PA);
 
     // ---- append column tables: [col (D)] [order (D)] with ray columns first; columns of twin height-scan records are not
     //      scheduled on their own (the lane of the primary ray finishes them)
@@ -385,7 +403,7 @@ extern "C" int imx_plan_update(imx_plan_t* plan, const int32_t* blob, size_t nwo
     IMX_REQUIRE(plan && blob, "imx_plan_update: null argument");
     imx_plan q;
     if (parse_plan(blob, nwords, &q)) return 1;
-    IMX_REQUIRE(q.host.size() == plan->host.size() && q.J == plan->J && q.B == plan->B && q.H == plan->H && q.A == plan->A &&
+    IMX_REQUIRE(q.host.size() == plan->host.size() && q.J == plan->J && q.B == plan->B && q.H == plan->H && q.A == plan->A && q.PA == plan->PA &&
                     q.D == plan->D && q.R == plan->R && q.NB == plan->NB && q.nterm == plan->nterm && q.nrew_all == plan->nrew_all &&
                     q.nobs == plan->nobs && q.DC == plan->DC && q.DX == plan->DX && q.MS == plan->MS && q.ngroups == plan->ngroups &&
                     q.scan_stateful == plan->scan_stateful && q.term_slots == plan->term_slots,

@@ -52,6 +52,7 @@ struct imx_plan {
     bool scan_stateful = false;
     bool needs_mesh = false;
     int term_slots = 0;           // rows of imx_buffers.term_state (stateful reward terms)
+    int PA = 0;                   // row width of imx_buffers.processed_action (IMX_H_PA, or A)
 };
 
 // view passed by value to kernels
@@ -213,10 +214,20 @@ IMX_DEV float wrap_to_pi(float a) {
 #define IMX_HALF_LOG_2PI 0.91893853320467274178f
 
 // One element of ActionManager.process_action (action_manager.py:318-337): prev <- cur; cur <- clamp(a); the owning term's
-// processed = raw*scale + offset [clamp | to-limits | EMA]  (joint_actions.py:130-139, joint_actions_to_limits.py).  Shared by k_action and
-// by the actor head of k_mlp_infer (imx_mlp_infer_act), which calls it for the action it has just sampled.
+// processed = raw*scale + offset [clamp | to-limits | EMA]  (joint_actions.py:130-139, joint_actions_to_limits.py), or the open / close
+// table of a binary term (binary_joint_actions.py:118-133).  Raw column c of the (N, A) action; the term's processed columns start at its
+// PCOL word (0 = its raw column) in the (N, PA) processed action, PA = the blob's IMX_H_PA word (0 = A; not in PlanView: the kernel
+// arguments of every kernel that takes one stay as long as they were).  Shared by k_action and by the actor head of k_mlp_infer
+// (imx_mlp_infer_act), which calls it for the action it has just sampled.  BINARY = false: compiled for plans whose terms are all
+// IMX_A_JOINT_AFFINE (PA == A, every PCOL word 0) -- the function as it was before binary terms existed.
+template <bool BINARY = true>
 IMX_DEV void action_process_element(const PlanView& P, const imx_state_t& S, const imx_buffers_t& Bf, int64_t e, int c, float a, float pre_clip) {
     const int64_t i = e * P.A + c;
+    int PA = P.A;
+    if (BINARY) {
+        const int pa = P.w[IMX_H_PA];
+        PA = pa ? pa : P.A;
+    }
     if (pre_clip < __builtin_huge_valf()) a = fminf(fmaxf(a, -pre_clip), pre_clip);  // torch.clamp
     Bf.prev_action[i] = Bf.action[i];
     Bf.action[i] = a;
@@ -226,6 +237,15 @@ IMX_DEV void action_process_element(const PlanView& P, const imx_state_t& S, con
         const int o = r[IMX_R_OUT], d = r[IMX_R_DIM];
         if (c < o || c >= o + d) continue;
         const int j = c - o;
+        const int pc = (BINARY && r[IMX_R_P2]) ? r[IMX_R_P2] : o;
+        if (BINARY && r[IMX_R_OP] == IMX_A_BINARY_JOINT) {  // where(a < 0, close, open): -0.0, +0.0 and NaN open; this one lane writes every joint of the term
+            const int32_t* tab = P.w + (a < 0.0f ? r[IMX_R_AUX1] : r[IMX_R_AUX0]);
+            float* out = Bf.processed_action + (e * PA + pc);
+#pragma unroll 1
+            for (int q = 0, n = r[IMX_R_NIDS]; q < n; ++q) out[q] = f_of(tab[q]);
+            continue;
+        }
+        const int64_t ip = BINARY ? e * PA + pc + j : i;  // (PA == A and pc == o without a binary term)
         const int flags = r[IMX_R_FLAGS];
         const float scale = r[IMX_R_AUX0] ? f_of(P.w[r[IMX_R_AUX0] + j]) : f_of(r[IMX_R_P0]);
         float offset = r[IMX_R_AUX1] ? f_of(P.w[r[IMX_R_AUX1] + j]) : f_of(r[IMX_R_P1]);
@@ -244,11 +264,11 @@ IMX_DEV void action_process_element(const PlanView& P, const imx_state_t& S, con
         }
         if (flags & IMX_F_ACT_EMA) {  // joint_actions_to_limits.py:219-230
             const float2 lim = reinterpret_cast<const float2*>(S.soft_joint_pos_limits)[e * P.J + jid];
-            const float prev = (Bf.reset_buf && Bf.reset_buf[e]) ? S.joint_pos[e * P.J + jid] : Bf.processed_action[i];
+            const float prev = (Bf.reset_buf && Bf.reset_buf[e]) ? S.joint_pos[e * P.J + jid] : Bf.processed_action[ip];
             v = offset * v + (1.0f - offset) * prev;
             v = fminf(fmaxf(v, lim.x), lim.y);
         }
-        Bf.processed_action[i] = v;
+        Bf.processed_action[ip] = v;
     }
 }
 // host-side validation of what action_process_element dereferences (step.hip)

@@ -1153,7 +1153,8 @@ struct ActArgs {
     imx_buffers_t Bf;
 };
 
-template <int ROWS>
+// BINARY: the plan has a binary joint term (processed width != raw width); the affine tasks' kernels are compiled without that path
+template <int ROWS, bool BINARY>
 __device__ __forceinline__ void act_epilogue(const ActArgs& c, const float* __restrict__ mu_s, float* __restrict__ term_s, int64_t m0, int64_t M) {
     const int A = c.A;
     const uint32_t step = c.step_d ? (uint32_t)c.step_d[0] : 0u;
@@ -1172,7 +1173,7 @@ __device__ __forceinline__ void act_epilogue(const ActArgs& c, const float* __re
             c.act_out[e * A + a] = x;
             c.mu_out[e * A + a] = m;
             c.sigma_out[e * A + a] = s;
-            if (c.has_plan) action_process_element(c.P, c.S, c.Bf, e, a, x, c.pre_clip);
+            if (c.has_plan) action_process_element<BINARY>(c.P, c.S, c.Bf, e, a, x, c.pre_clip);
         }
         term_s[row * INF_PITCH + a] = term;
     }
@@ -1302,73 +1303,18 @@ __device__ __forceinline__ void infer_layer(const float* __restrict__ sIn, int K
     }
 }
 
+// (the kernel bodies are textual includes, see mlp_infer_body.inc: *_binary = for a plan with a binary joint term)
 template <bool PACKED>
 __global__ void __launch_bounds__(256, 1) k_mlp_infer(InferArgs a, ActArgs act) {
-    extern __shared__ float smem[];  // two activation buffers of INF_ROWS x INF_PITCH floats
-    float* buf0 = smem;
-    float* buf1 = smem + INF_ROWS * INF_PITCH;
-    const int which = blockIdx.x / a.tiles;
-    const InferNet& net = a.net[which];
-    const int64_t m0 = (int64_t)(blockIdx.x - which * a.tiles) * INF_ROWS;
-    const bool act_here = act.enabled && which == 0;  // the actor's workgroups finish PPO.act + ActionManager.process_action themselves
-    // input rows -> LDS (the 32 rows are one contiguous run when ldx == dim[0]); columns up to the next multiple of 32 are zeroed
-    const int K0 = net.dim[0], K0p = (K0 + 31) & ~31;
-    {
-        // wave w takes rows w, w+4, ...; lanes run along the row.  ALL loads of the tile are issued before the first LDS store -- one HBM
-        // round trip for the whole input (a load -> store loop pays one per iteration: 16 us for 235 columns; two half tiles paid two) --
-        // and only the 64-column pieces the input has (a clamped load of a piece past K0 is still a memory request).
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-        const int ncc = (K0 + 63) >> 6;  // (uniform)
-        float v[8][INF_MAXD / 64];
-#pragma unroll
-        for (int rr = 0; rr < 8; ++rr) {
-            const int row = w + 4 * rr;
-            const float* src = a.X + (m0 + row < a.M ? m0 + row : 0) * a.ldx;
-#pragma unroll
-            for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
-                if (cc < ncc) {
-                    const int c = lane + 64 * cc;
-                    const float x = src[c < K0 ? c : 0];  // clamped, unconditional within the piece
-                    v[rr][cc] = (c < K0 && m0 + row < a.M) ? x : 0.0f;
-                } else {
-                    v[rr][cc] = 0.0f;
-                }
-            }
-        }
-#pragma unroll
-        for (int rr = 0; rr < 8; ++rr) {
-            const int row = w + 4 * rr;
-#pragma unroll
-            for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
-                const int c = lane + 64 * cc;
-                if (c < K0p) buf0[row * INF_PITCH + c] = v[rr][cc];
-                if (act_here && c < K0 && m0 + row < a.M) act.obs_out[(m0 + row) * (int64_t)K0 + c] = v[rr][cc];  // storage.observations[t]
-            }
-        }
-    }
-    __syncthreads();
-    float* in = buf0;
-    float* out = buf1;
-    for (int l = 0; l < net.nlayers; ++l) {
-        const int K = net.dim[l], N = net.dim[l + 1];
-        const bool last = l == net.nlayers - 1;
-        const int nbw = ((N + 31) / 32 + 3) / 4;  // 32-column blocks per wave
-        float* so = (last && !act_here) ? nullptr : out;  // (the actor head of imx_mlp_infer_act keeps its means in LDS)
-        if (!last) {  // zero the padding columns the next layer's 32-wide reduction groups will read
-            const int Np = (N + 31) & ~31;
-            for (int i = threadIdx.x; i < INF_ROWS * (Np - N); i += blockDim.x) {
-                const int row = i / (Np - N), col = N + i - row * (Np - N);
-                out[row * INF_PITCH + col] = 0.0f;
-            }
-        }
-        const float* Wl = PACKED ? net.Wp[l] : net.W[l];
-        if (nbw <= 1) infer_layer<1, PACKED>(in, K, Wl, net.ldw[l], net.b[l], N, !last, net.alpha, so, net.out, m0, a.M);
-        else if (nbw == 2) infer_layer<2, PACKED>(in, K, Wl, net.ldw[l], net.b[l], N, !last, net.alpha, so, net.out, m0, a.M);
-        else infer_layer<4, PACKED>(in, K, Wl, net.ldw[l], net.b[l], N, !last, net.alpha, so, net.out, m0, a.M);
-        __syncthreads();
-        float* t = in; in = out; out = t;
-    }
-    if (act_here) act_epilogue<INF_ROWS>(act, in, out, m0, a.M);
+#define IMX_ACT_BINARY false
+#include "mlp_infer_body.inc"
+#undef IMX_ACT_BINARY
+}
+template <bool PACKED>
+__global__ void __launch_bounds__(256, 1) k_mlp_infer_binary(InferArgs a, ActArgs act) {
+#define IMX_ACT_BINARY true
+#include "mlp_infer_body.inc"
+#undef IMX_ACT_BINARY
 }
 
 // ---- 16-sample variant (v_mfma_f32_16x16x4_f32) for small batches: twice the workgroups (and half the LDS each) when
@@ -1470,62 +1416,14 @@ __device__ __forceinline__ void infer_layer16(const float* __restrict__ sIn, int
 }
 
 __global__ void __launch_bounds__(256, 2) k_mlp_infer16(InferArgs a, ActArgs act) {
-    extern __shared__ float smem[];  // two activation buffers of INF16_ROWS x INF_PITCH floats
-    float* buf0 = smem;
-    float* buf1 = smem + INF16_ROWS * INF_PITCH;
-    const int which = blockIdx.x / a.tiles;
-    const InferNet& net = a.net[which];
-    const int64_t m0 = (int64_t)(blockIdx.x - which * a.tiles) * INF16_ROWS;
-    const bool act_here = act.enabled && which == 0;
-    const int K0 = net.dim[0], K0p = (K0 + 31) & ~31;
-    {
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-        float v[4][INF_MAXD / 64];  // wave w: rows w, w+4, w+8, w+12; all loads before the first LDS store
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            const int row = w + 4 * rr;
-            const float* src = a.X + (m0 + row < a.M ? m0 + row : 0) * a.ldx;
-#pragma unroll
-            for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
-                const int c = lane + 64 * cc;
-                const float x = src[c < K0 ? c : 0];
-                v[rr][cc] = (c < K0 && m0 + row < a.M) ? x : 0.0f;
-            }
-        }
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            const int row = w + 4 * rr;
-#pragma unroll
-            for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
-                const int c = lane + 64 * cc;
-                if (c < K0p) buf0[row * INF_PITCH + c] = v[rr][cc];
-                if (act_here && c < K0 && m0 + row < a.M) act.obs_out[(m0 + row) * (int64_t)K0 + c] = v[rr][cc];
-            }
-        }
-    }
-    __syncthreads();
-    float* in = buf0;
-    float* out = buf1;
-    for (int l = 0; l < net.nlayers; ++l) {
-        const int K = net.dim[l], N = net.dim[l + 1];
-        const bool last = l == net.nlayers - 1;
-        const int nbw = ((N + 15) / 16 + 3) / 4;  // 16-column blocks per wave
-        float* so = (last && !act_here) ? nullptr : out;
-        if (!last) {
-            const int Np = (N + 31) & ~31;
-            for (int i = threadIdx.x; i < INF16_ROWS * (Np - N); i += blockDim.x) {
-                const int row = i / (Np - N), col = N + i - row * (Np - N);
-                out[row * INF_PITCH + col] = 0.0f;
-            }
-        }
-        if (nbw <= 1) infer_layer16<1>(in, K, net.W[l], net.ldw[l], net.b[l], N, !last, net.alpha, so, net.out, m0, a.M);
-        else if (nbw == 2) infer_layer16<2>(in, K, net.W[l], net.ldw[l], net.b[l], N, !last, net.alpha, so, net.out, m0, a.M);
-        else if (nbw <= 4) infer_layer16<4>(in, K, net.W[l], net.ldw[l], net.b[l], N, !last, net.alpha, so, net.out, m0, a.M);
-        else infer_layer16<8>(in, K, net.W[l], net.ldw[l], net.b[l], N, !last, net.alpha, so, net.out, m0, a.M);
-        __syncthreads();
-        float* t = in; in = out; out = t;
-    }
-    if (act_here) act_epilogue<INF16_ROWS>(act, in, out, m0, a.M);
+#define IMX_ACT_BINARY false
+#include "mlp_infer16_body.inc"
+#undef IMX_ACT_BINARY
+}
+__global__ void __launch_bounds__(256, 2) k_mlp_infer16_binary(InferArgs a, ActArgs act) {
+#define IMX_ACT_BINARY true
+#include "mlp_infer16_body.inc"
+#undef IMX_ACT_BINARY
 }
 
 extern "C" int imx_mlp_infer(int64_t M, const float* X_d, int64_t ldx, int nnets, const int* nlayers, const int* dims,
@@ -1615,7 +1513,9 @@ extern "C" int imx_mlp_infer_act(int64_t M, const float* X_d, int64_t ldx, int n
             IMX_REQUIRE(pa->state && pa->buf && pa->plan->dev, "imx_mlp_infer_act: plan without state / buffers / device tables");
             IMX_REQUIRE(pa->plan->A == act.A, "imx_mlp_infer_act: the actor has %d outputs, the plan %d action columns", act.A, pa->plan->A);
             if (imx_check_action_inputs(pa->plan, pa->state, pa->buf, "imx_mlp_infer_act")) return 1;
-            act.has_plan = 1;
+            act.has_plan = pa->plan->PA != pa->plan->A ? 2 : 1;  // 2: processed width != raw width (a binary joint term)
+            for (int k = 0; k < pa->plan->nact; ++k)
+                if (pa->plan->host[pa->plan->act_off + k * IMX_REC_WORDS + IMX_R_OP] == IMX_A_BINARY_JOINT) act.has_plan = 2;
             act.P = imx_plan_view(pa->plan);
             act.S = *pa->state;
             act.Bf = *pa->buf;
@@ -1658,24 +1558,25 @@ extern "C" int imx_mlp_infer_act(int64_t M, const float* X_d, int64_t ldx, int n
     const bool small = (int64_t)a.tiles * nnets * 2 <= g_num_cu;
     static bool attr_set = false;
     if (!attr_set) {
-        IMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_infer<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(2ull * INF_ROWS * INF_PITCH * sizeof(float))));
-        IMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_infer<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(2ull * INF_ROWS * INF_PITCH * sizeof(float))));
-        IMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_infer16), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(2ull * INF16_ROWS * INF_PITCH * sizeof(float))));
+        const void* big[] = {reinterpret_cast<const void*>(k_mlp_infer<false>), reinterpret_cast<const void*>(k_mlp_infer<true>),
+                             reinterpret_cast<const void*>(k_mlp_infer_binary<false>), reinterpret_cast<const void*>(k_mlp_infer_binary<true>)};
+        for (const void* f : big) IMX_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2ull * INF_ROWS * INF_PITCH * sizeof(float))));
+        const void* small16[] = {reinterpret_cast<const void*>(k_mlp_infer16), reinterpret_cast<const void*>(k_mlp_infer16_binary)};
+        for (const void* f : small16) IMX_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2ull * INF16_ROWS * INF_PITCH * sizeof(float))));
         attr_set = true;
     }
+    const bool binary = act.has_plan == 2;  // a plan with a binary joint term: the kernels with that path in the actor head's epilogue
+    const dim3 bs(256);
     if (small) {
         a.tiles = (int)((M + INF16_ROWS - 1) / INF16_ROWS);
-        hipLaunchKernelGGL(k_mlp_infer16, dim3((unsigned)(a.tiles * nnets)), dim3(256), 2ull * INF16_ROWS * INF_PITCH * sizeof(float),
-                           (hipStream_t)stream, a, act);
+        hipLaunchKernelGGL(binary ? k_mlp_infer16_binary : k_mlp_infer16, dim3((unsigned)(a.tiles * nnets)), bs,
+                           2ull * INF16_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act);
     } else if (packed_weights_d) {
-        hipLaunchKernelGGL(k_mlp_infer<true>, dim3((unsigned)(a.tiles * nnets)), dim3(256), 2ull * INF_ROWS * INF_PITCH * sizeof(float),
-                           (hipStream_t)stream, a, act);
+        hipLaunchKernelGGL(binary ? k_mlp_infer_binary<true> : k_mlp_infer<true>, dim3((unsigned)(a.tiles * nnets)), bs,
+                           2ull * INF_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act);
     } else {
-        hipLaunchKernelGGL(k_mlp_infer<false>, dim3((unsigned)(a.tiles * nnets)), dim3(256), 2ull * INF_ROWS * INF_PITCH * sizeof(float),
-                           (hipStream_t)stream, a, act);
+        hipLaunchKernelGGL(binary ? k_mlp_infer_binary<false> : k_mlp_infer<false>, dim3((unsigned)(a.tiles * nnets)), bs,
+                           2ull * INF_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act);
     }
     IMX_HIP(hipGetLastError());
     return 0;

@@ -1,0 +1,59 @@
+// The body of k_mlp_infer16 / k_mlp_infer16_binary (mlp.hip), included once per kernel with IMX_ACT_BINARY = false (the kernel as it always was) or true (the actor
+// head's epilogue with the binary joint term's path).  A textual include, not a device function: the existing kernels then compile to the
+// instruction streams they had.
+    extern __shared__ float smem[];  // two activation buffers of INF16_ROWS x INF_PITCH floats
+    float* buf0 = smem;
+    float* buf1 = smem + INF16_ROWS * INF_PITCH;
+    const int which = blockIdx.x / a.tiles;
+    const InferNet& net = a.net[which];
+    const int64_t m0 = (int64_t)(blockIdx.x - which * a.tiles) * INF16_ROWS;
+    const bool act_here = act.enabled && which == 0;
+    const int K0 = net.dim[0], K0p = (K0 + 31) & ~31;
+    {
+        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+        float v[4][INF_MAXD / 64];  // wave w: rows w, w+4, w+8, w+12; all loads before the first LDS store
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int row = w + 4 * rr;
+            const float* src = a.X + (m0 + row < a.M ? m0 + row : 0) * a.ldx;
+#pragma unroll
+            for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
+                const int c = lane + 64 * cc;
+                const float x = src[c < K0 ? c : 0];
+                v[rr][cc] = (c < K0 && m0 + row < a.M) ? x : 0.0f;
+            }
+        }
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int row = w + 4 * rr;
+#pragma unroll
+            for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
+                const int c = lane + 64 * cc;
+                if (c < K0p) buf0[row * INF_PITCH + c] = v[rr][cc];
+                if (act_here && c < K0 && m0 + row < a.M) act.obs_out[(m0 + row) * (int64_t)K0 + c] = v[rr][cc];
+            }
+        }
+    }
+    __syncthreads();
+    float* in = buf0;
+    float* out = buf1;
+    for (int l = 0; l < net.nlayers; ++l) {
+        const int K = net.dim[l], N = net.dim[l + 1];
+        const bool last = l == net.nlayers - 1;
+        const int nbw = ((N + 15) / 16 + 3) / 4;  // 16-column blocks per wave
+        float* so = (last && !act_here) ? nullptr : out;
+        if (!last) {
+            const int Np = (N + 31) & ~31;
+            for (int i = threadIdx.x; i < INF16_ROWS * (Np - N); i += blockDim.x) {
+                const int row = i / (Np - N), col = N + i - row * (Np - N);
+                out[row * INF_PITCH + col] = 0.0f;
+            }
+        }
+        if (nbw <= 1) infer_layer16<1>(in, K, net.W[l], net.ldw[l], net.b[l], N, !last, net.alpha, so, net.out, m0, a.M);
+        else if (nbw == 2) infer_layer16<2>(in, K, net.W[l], net.ldw[l], net.b[l], N, !last, net.alpha, so, net.out, m0, a.M);
+        else if (nbw <= 4) infer_layer16<4>(in, K, net.W[l], net.ldw[l], net.b[l], N, !last, net.alpha, so, net.out, m0, a.M);
+        else infer_layer16<8>(in, K, net.W[l], net.ldw[l], net.b[l], N, !last, net.alpha, so, net.out, m0, a.M);
+        __syncthreads();
+        float* t = in; in = out; out = t;
+    }
+    if (act_here) act_epilogue<INF16_ROWS, IMX_ACT_BINARY>(act, in, out, m0, a.M);

@@ -1,0 +1,68 @@
+// The body of k_mlp_infer / k_mlp_infer_binary (mlp.hip), included once per kernel with IMX_ACT_BINARY = false (the kernel as it always was) or true (the actor
+// head's epilogue with the binary joint term's path).  A textual include, not a device function: the existing kernels then compile to the
+// instruction streams they had.
+    extern __shared__ float smem[];  // two activation buffers of INF_ROWS x INF_PITCH floats
+    float* buf0 = smem;
+    float* buf1 = smem + INF_ROWS * INF_PITCH;
+    const int which = blockIdx.x / a.tiles;
+    const InferNet& net = a.net[which];
+    const int64_t m0 = (int64_t)(blockIdx.x - which * a.tiles) * INF_ROWS;
+    const bool act_here = act.enabled && which == 0;  // the actor's workgroups finish PPO.act + ActionManager.process_action themselves
+    // input rows -> LDS (the 32 rows are one contiguous run when ldx == dim[0]); columns up to the next multiple of 32 are zeroed
+    const int K0 = net.dim[0], K0p = (K0 + 31) & ~31;
+    {
+        // wave w takes rows w, w+4, ...; lanes run along the row.  ALL loads of the tile are issued before the first LDS store -- one HBM
+        // round trip for the whole input (a load -> store loop pays one per iteration: 16 us for 235 columns; two half tiles paid two) --
+        // and only the 64-column pieces the input has (a clamped load of a piece past K0 is still a memory request).
+        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+        const int ncc = (K0 + 63) >> 6;  // (uniform)
+        float v[8][INF_MAXD / 64];
+#pragma unroll
+        for (int rr = 0; rr < 8; ++rr) {
+            const int row = w + 4 * rr;
+            const float* src = a.X + (m0 + row < a.M ? m0 + row : 0) * a.ldx;
+#pragma unroll
+            for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
+                if (cc < ncc) {
+                    const int c = lane + 64 * cc;
+                    const float x = src[c < K0 ? c : 0];  // clamped, unconditional within the piece
+                    v[rr][cc] = (c < K0 && m0 + row < a.M) ? x : 0.0f;
+                } else {
+                    v[rr][cc] = 0.0f;
+                }
+            }
+        }
+#pragma unroll
+        for (int rr = 0; rr < 8; ++rr) {
+            const int row = w + 4 * rr;
+#pragma unroll
+            for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
+                const int c = lane + 64 * cc;
+                if (c < K0p) buf0[row * INF_PITCH + c] = v[rr][cc];
+                if (act_here && c < K0 && m0 + row < a.M) act.obs_out[(m0 + row) * (int64_t)K0 + c] = v[rr][cc];  // storage.observations[t]
+            }
+        }
+    }
+    __syncthreads();
+    float* in = buf0;
+    float* out = buf1;
+    for (int l = 0; l < net.nlayers; ++l) {
+        const int K = net.dim[l], N = net.dim[l + 1];
+        const bool last = l == net.nlayers - 1;
+        const int nbw = ((N + 31) / 32 + 3) / 4;  // 32-column blocks per wave
+        float* so = (last && !act_here) ? nullptr : out;  // (the actor head of imx_mlp_infer_act keeps its means in LDS)
+        if (!last) {  // zero the padding columns the next layer's 32-wide reduction groups will read
+            const int Np = (N + 31) & ~31;
+            for (int i = threadIdx.x; i < INF_ROWS * (Np - N); i += blockDim.x) {
+                const int row = i / (Np - N), col = N + i - row * (Np - N);
+                out[row * INF_PITCH + col] = 0.0f;
+            }
+        }
+        const float* Wl = PACKED ? net.Wp[l] : net.W[l];
+        if (nbw <= 1) infer_layer<1, PACKED>(in, K, Wl, net.ldw[l], net.b[l], N, !last, net.alpha, so, net.out, m0, a.M);
+        else if (nbw == 2) infer_layer<2, PACKED>(in, K, Wl, net.ldw[l], net.b[l], N, !last, net.alpha, so, net.out, m0, a.M);
+        else infer_layer<4, PACKED>(in, K, Wl, net.ldw[l], net.b[l], N, !last, net.alpha, so, net.out, m0, a.M);
+        __syncthreads();
+        float* t = in; in = out; out = t;
+    }
+    if (act_here) act_epilogue<INF_ROWS, IMX_ACT_BINARY>(act, in, out, m0, a.M);

@@ -36,13 +36,20 @@ _CFG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs")
 
 
 def load_task_cfg(task: str) -> dict:
-    """Config fixture captured from the reference's gym registry entry ``task`` (``cfg.to_dict()`` form)."""
-    path = os.path.join(_CFG_DIR, task + ".json")
-    if not os.path.exists(path):
-        raise FileNotFoundError(f"no config fixture for task '{task}' under {_CFG_DIR}")
+    """Config fixture captured from the reference's gym registry entry ``task`` (``cfg.to_dict()`` form).  ``task``: a task id with a
+    fixture under ``isaaclab_amd/configs``, or the path of a fixture file ``<dir>/<name>.json`` (its ``<name>.managers.json`` beside it)."""
+    if task.endswith(".json"):
+        path = task
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"no config fixture file '{path}'")
+        side = path[:-len(".json")] + ".managers.json"
+    else:
+        path = os.path.join(_CFG_DIR, task + ".json")
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"no config fixture for task '{task}' under {_CFG_DIR}")
+        side = os.path.join(_CFG_DIR, task + ".managers.json")  # events / curriculum / robot init state of the task, dumped separately
     with open(path) as f:
         fx = json.load(f)
-    side = os.path.join(_CFG_DIR, task + ".managers.json")  # events / curriculum / robot init state of the task, dumped separately
     if os.path.exists(side):
         with open(side) as f:
             extra = json.load(f)
@@ -161,8 +168,10 @@ def _cfg_entry(cfg: Any) -> dict:
 
 
 class _ActionTermView:
-    def __init__(self, env, name, col0, dim):
-        self._env, self.name, self._c0, self.action_dim = env, name, col0, dim
+    """One term's columns of the raw action and of the processed action (a binary joint term takes 1 and writes one per joint)."""
+
+    def __init__(self, env, name, col0, dim, pcol0, pdim):
+        self._env, self.name, self._c0, self.action_dim, self._p0, self._pdim = env, name, col0, dim, pcol0, pdim
 
     @property
     def raw_actions(self):
@@ -170,7 +179,7 @@ class _ActionTermView:
 
     @property
     def processed_actions(self):
-        return self._env._processed_action[:, self._c0:self._c0 + self.action_dim]
+        return self._env._processed_action[:, self._p0:self._p0 + self._pdim]
 
 
 class ActionManager:
@@ -181,7 +190,7 @@ class ActionManager:
         self._terms = {}
         c = 0
         for t in env.plan.action_terms:
-            self._terms[t.name] = _ActionTermView(env, t.name, c, t.dim)
+            self._terms[t.name] = _ActionTermView(env, t.name, c, t.dim, t.processed_col, t.processed_dim)
             c += t.dim
 
     @property
@@ -218,17 +227,17 @@ class ActionManager:
         self._env._prev_action[ids] = 0.0
         self._env._action[ids] = 0.0
         # EMAJointPositionToLimitsAction.reset (joint_actions_to_limits.py:208-217): the moving average restarts from the joint positions
-        # (inside env.step() the action kernel does this itself for the envs the step kernel reset)
-        c = 0
+        # (inside env.step() the action kernel does this itself for the envs the step kernel reset).  A binary joint term zeroes its raw
+        # action only (binary_joint_actions.py:135): done above
         for t in self._env.plan.action_terms:
             if t.func.rsplit(":", 1)[-1].rsplit(".", 1)[-1] == "EMAJointPositionToLimitsAction":
                 from .robots import resolve_matching_names
 
                 jids = resolve_matching_names(t.params["joint_names"], self._env.plan.robot.joint_names, bool(t.params.get("preserve_order")))[0]
                 rows = torch.arange(self._env.num_envs, device=self._env.device)[ids]
+                c = t.processed_col
                 self._env._processed_action[rows.unsqueeze(1), torch.arange(c, c + t.dim, device=self._env.device)] = \
                     self._env.feed["joint_pos"][rows][:, jids]
-            c += t.dim
         return {}
 
 
@@ -595,7 +604,7 @@ class ManagerBasedRLEnv:
         # the env's own copy of the cfg in to_dict() form: set_term_cfg edits and recompiles it
         self._cfg_dict = copy.deepcopy(env_cfg if isinstance(env_cfg, dict) else env_cfg.to_dict())
         self._robot = robot_name
-        self._entities = SceneEntityResolver(robot_name)
+        self._entities = SceneEntityResolver(robot_name, self._cfg_dict.get("scene"))
         self.plan: Plan = compile_plan(self._cfg_dict, robot_name)
         plan = self.plan
         env_dict = self._cfg_dict
@@ -641,7 +650,7 @@ class ManagerBasedRLEnv:
         A, D = plan.action_dim, plan.obs_dim
         z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
         self._episode_length_buf = z(N, dtype=torch.long)
-        self._action, self._prev_action, self._processed_action = z(N, max(A, 1)), z(N, max(A, 1)), z(N, max(A, 1))
+        self._action, self._prev_action, self._processed_action = z(N, max(A, 1)), z(N, max(A, 1)), z(N, max(plan.processed_action_dim, 1))
         self._reward_buf = z(N)
         self._episode_sums = z(K, N)
         self._step_reward = z(N, K)
@@ -1057,7 +1066,11 @@ class ManagerBasedRLEnv:
 
     def attach_actuator(self, actuator_net):
         """An env-owned ``producers.ActuatorNetLSTM``: its hidden / cell state restarts with the env (scene.reset -> Articulation.reset ->
-        ActuatorNetLSTM.reset, actuators/actuator_net.py:66-70) inside the orchestration launch."""
+        ActuatorNetLSTM.reset, actuators/actuator_net.py:66-70) inside the orchestration launch.  It is fed the processed action as its
+        (N, J) joint targets, so the action terms must write one target per joint."""
+        if self.plan.processed_action_dim != self.plan.num_joints:
+            raise ValueError(f"attach_actuator: the action terms write {self.plan.processed_action_dim} joint targets, the robot has "
+                             f"{self.plan.num_joints} joints")
         self.actuator_net = actuator_net
         self._orch = None
 

@@ -32,7 +32,7 @@ H = dict(MAGIC=0, VERSION=1, J=2, B=3, H=4, A=5, D=6, R=7, NTERM=8, NREW=9, NOBS
          STEP_DT=13, TERM_OFF=14, REW_OFF=15, OBS_OFF=16, ACT_OFF=17, TOTAL_WORDS=18, NB=19, GRAV_X=20, GRAV_Y=21,
          GRAV_Z=22, NREW_ALL=23, RAY_OFF=24, RAYDIR_X=25, RAYDIR_Y=26, RAYDIR_Z=27, RAY_MAXDIST=28, MAX_EP_LEN_S=29,
          NEXT_REW=30, NEXT_TERM=31, NEXT_OBS=32, RAY_YAW_ONLY=33, CMD_DIM=34, MOD_STATE=35, NGROUPS=36, GROUP_OFF=37,
-         SCAN_PERIOD=38, SCAN_DT=39, SCAN_SUBSTEPS=40, SCAN_DRIFT_LO=41, SCAN_DRIFT_HI=42, SCAN_STATEFUL=43, TERM_SLOTS=44)
+         SCAN_PERIOD=38, SCAN_DT=39, SCAN_SUBSTEPS=40, SCAN_DRIFT_LO=41, SCAN_DRIFT_HI=42, SCAN_STATEFUL=43, TERM_SLOTS=44, PA=45)
 R = dict(OP=0, IDS_OFF=1, NIDS=2, IDS2_OFF=3, NIDS2=4, WEIGHT=5, P0=6, P1=7, P2=8, P3=9, OUT=10, DIM=11, FLAGS=12,
          NOISE_LO=13, NOISE_HI=14, CLIP_LO=15, CLIP_HI=16, SCALE=17, AUX0=18, AUX1=19)
 F_NOISE_ADD, F_NOISE_SCALE, F_NOISE_ABS, F_CLIP, F_SCALE, F_QUAT_UNIQUE, F_MODIFIERS, F_SCAN_TWIN = 1, 2, 4, 8, 16, 32, 64, 128
@@ -44,7 +44,7 @@ F_ACT_DEFAULT_POS_OFFSET, F_ACT_DEFAULT_VEL_OFFSET, F_ACT_CLIP = 1, 2, 4
 
 T_OPS = dict(TIME_OUT=1, ILLEGAL_CONTACT=2, JOINT_POS_MANUAL_LIMIT=3, BAD_ORIENTATION=4, ROOT_HEIGHT_BELOW_MIN=5,
              JOINT_VEL_LIMIT=6, JOINT_VEL_MANUAL_LIMIT=7, JOINT_EFFORT_LIMIT=8, TERRAIN_OUT_OF_BOUNDS=9, EXTERNAL=10,
-             COMMAND_RESAMPLE=11)
+             COMMAND_RESAMPLE=11, OBJECT_REACHED_GOAL=12)
 W_OPS = dict(IS_ALIVE=1, IS_TERMINATED=2, IS_TERMINATED_TERM=3, LIN_VEL_Z_L2=4, ANG_VEL_XY_L2=5, FLAT_ORIENTATION_L2=6,
              BASE_HEIGHT_L2=7, JOINT_TORQUES_L2=8, JOINT_VEL_L1=9, JOINT_VEL_L2=10, JOINT_ACC_L2=11,
              JOINT_DEVIATION_L1=12, JOINT_POS_LIMITS=13, JOINT_VEL_LIMITS=14, APPLIED_TORQUE_LIMITS=15,
@@ -56,12 +56,13 @@ W_OPS = dict(IS_ALIVE=1, IS_TERMINATED=2, IS_TERMINATED_TERM=3, LIN_VEL_Z_L2=4, 
              BASE_ORIENTATION_PENALTY=38, FOOT_SLIP_PENALTY=39, JOINT_ACCELERATION_PENALTY=40, JOINT_POSITION_PENALTY=41,
              JOINT_TORQUES_PENALTY=42, JOINT_VELOCITY_PENALTY=43, UPRIGHT_POSTURE_BONUS=44, MOVE_TO_TARGET_BONUS=45, PROGRESS_REWARD=46,
              JOINT_POS_LIMITS_PENALTY_RATIO=47, POWER_CONSUMPTION=48, POSITION_COMMAND_ERROR=49, POSITION_COMMAND_ERROR_TANH=50,
-             ORIENTATION_COMMAND_ERROR=51)
+             ORIENTATION_COMMAND_ERROR=51, OBJECT_IS_LIFTED=52, OBJECT_EE_DISTANCE=53, OBJECT_GOAL_DISTANCE=54)
 O_OPS = dict(BASE_POS_Z=1, BASE_LIN_VEL=2, BASE_ANG_VEL=3, PROJECTED_GRAVITY=4, ROOT_POS_W=5, ROOT_QUAT_W=6,
              ROOT_LIN_VEL_W=7, ROOT_ANG_VEL_W=8, JOINT_POS=9, JOINT_POS_REL=10, JOINT_POS_LIMIT_NORMALIZED=11,
              JOINT_VEL=12, JOINT_VEL_REL=13, HEIGHT_SCAN=14, LAST_ACTION=15, GENERATED_COMMANDS=16, EXTERNAL=17,
-             BASE_YAW_ROLL=18, BASE_UP_PROJ=19, BASE_HEADING_PROJ=20, BASE_ANGLE_TO_TARGET=21, BODY_INCOMING_WRENCH=22)
-A_JOINT_AFFINE = 1
+             BASE_YAW_ROLL=18, BASE_UP_PROJ=19, BASE_HEADING_PROJ=20, BASE_ANGLE_TO_TARGET=21, BODY_INCOMING_WRENCH=22,
+             OBJECT_POSITION_IN_ROBOT_ROOT_FRAME=23)
+A_JOINT_AFFINE, A_BINARY_JOINT = 1, 2
 
 _MDP = "isaaclab.envs.mdp"
 _VEL = "isaaclab_tasks.manager_based.locomotion.velocity.mdp"
@@ -69,6 +70,7 @@ _CART = "isaaclab_tasks.manager_based.classic.cartpole.mdp"
 _SPOT = "isaaclab_tasks.manager_based.locomotion.velocity.config.spot.mdp.rewards"
 _CLASSIC = "isaaclab_tasks.manager_based.classic.humanoid.mdp"  # its own modules; what it re-exports from isaaclab.envs.mdp keeps _MDP names
 _REACH = "isaaclab_tasks.manager_based.manipulation.reach.mdp.rewards"
+_LIFT = "isaaclab_tasks.manager_based.manipulation.lift.mdp"  # .observations, .rewards, .terminations (Isaac-Lift-Cube-Franka-v0)
 _POSE_COMMAND = "isaaclab.envs.mdp.commands.pose_command:UniformPoseCommand"  # command = (N, 7): position + quaternion, base frame
 
 
@@ -120,6 +122,8 @@ class Term:
     weight: float = 0.0
     time_out: bool = False
     py_modifiers: list = dataclasses.field(default_factory=list)  # (func, params) of a foreign modifier chain applied in Python
+    processed_col: int = 0  # action terms: first column and width of the term in the processed action (dim = its raw columns)
+    processed_dim: int = 0
 
 
 @dataclasses.dataclass
@@ -157,6 +161,7 @@ class Plan:
     scan_stateful: bool = False  # the height scanner keeps per-env timestamps / drift (update_period > 0 or a drift range)
     scan_drift_range: tuple[float, float] = (0.0, 0.0)
     term_slots: int = 0  # rows of per-env reward-term state (imx_buffers.term_state): one per progress_reward term
+    processed_action_dim: int = 0  # width of the processed action (= action_dim unless a term writes more joints than it takes columns)
 
 
 @dataclasses.dataclass
@@ -299,7 +304,8 @@ class _Fused:
 
 # Closed modules -- Spot's rewards, the classic tasks' observations and rewards, the reach rewards -- have no Python fallback: a function
 # of theirs without a table entry is refused in the managers named here.  Any other unknown function is Python-evaluated (``EXTERNAL``).
-_CLOSED = {_SPOT: ("reward",), _REACH: ("reward",), **{f"{_CLASSIC}.{m}": ("termination", "reward", "observation") for m in ("observations", "rewards")}}
+_CLOSED = {_SPOT: ("reward",), _REACH: ("reward",), **{f"{_CLASSIC}.{m}": ("termination", "reward", "observation") for m in ("observations", "rewards")},
+           **{f"{_LIFT}.{m}": ("termination", "reward", "observation") for m in ("observations", "rewards", "terminations")}}
 
 
 def _target_pos(kind: str, name: str, p: dict) -> list[float]:
@@ -337,18 +343,97 @@ def _terrain_out_of_bounds(c, name, p, rec):
         rec.update(p0=f32(0.5 * mw - buf), p1=f32(0.5 * mh - buf))
 
 
+# -- the lift task's own terms (isaaclab_tasks .../manipulation/lift/mdp: Isaac-Lift-Cube-Franka-v0) and what they share
+def _entity_name(ent, default: str) -> str:
+    if ent is None:
+        return default
+    return ent.get("name") if isinstance(ent, dict) else getattr(ent, "name", None)
+
+
+def _object(c, kind, name, p, key="object_cfg", default="object"):
+    """The ``RigidObject`` a term reads (``object.data.root_pos_w``): the scene's one rigid object, served as ``object_root_pos_w``."""
+    ent = _entity_name(p.get(key), default)
+    if ent not in c.entities.rigid_objects:
+        raise ValueError(f"{kind} term '{name}': '{key}' names the scene entity '{ent}', which is not a RigidObject of the scene "
+                         f"(it has {list(c.entities.rigid_objects)})")
+    if len(c.entities.rigid_objects) > 1:
+        raise NotImplementedError(f"{kind} term '{name}': the scene has {len(c.entities.rigid_objects)} rigid objects "
+                                  f"{list(c.entities.rigid_objects)}; the fused path carries one object root position")
+    c.entities.ids(p.get(key), "body", ent)  # the cfg must still resolve (SceneEntityCfg.resolve)
+
+
+def _robot(c, kind, name, p, key="robot_cfg"):
+    ent = _entity_name(p.get(key), "robot")
+    if ent != "robot":
+        raise NotImplementedError(f"{kind} term '{name}': '{key}' names the scene entity '{ent}'; the fused op reads the robot's root state")
+
+
+def _pose_command(c, kind, name, p, default=None):
+    """``command_name`` must name a command term of the cfg whose command is (N, 7) (``command[:, :3]`` = the goal in the base frame)."""
+    cname = p.get("command_name", default)
+    ccfg = (c.cfg.get("commands") or {}).get(cname)
+    if ccfg is None:
+        raise ValueError(f"{kind} term '{name}': command_name '{cname}' is not a command term of the cfg (it has {list(c.cfg.get('commands') or {})})")
+    if command_width(ccfg) != 7 or c.cmd_dim != 7:
+        raise ValueError(f"{kind} term '{name}': command '{cname}' must be a UniformPoseCommand (N, 7); it is {command_width(ccfg)} wide")
+
+
+def _root_height_asset(c, name, p, rec):
+    """``asset_cfg`` selects whose root: the robot (AUX0 = 0, the word every older blob has) or the scene's rigid object (AUX0 = 1)."""
+    ent = _entity_name(p.get("asset_cfg"), "robot")
+    if ent in c.entities.rigid_objects:
+        _object(c, "termination", name, p, key="asset_cfg")
+        rec["aux0"] = 1
+    elif ent != "robot":
+        c.entities.names(ent, "body")  # raises: the entity does not exist
+
+
+def _object_reached_goal(c, name, p, rec):
+    _robot(c, "termination", name, p)
+    _object(c, "termination", name, p)
+    _pose_command(c, "termination", name, p, default="object_pose")
+
+
+def _object_is_lifted(c, name, p, rec):
+    _object(c, "reward", name, p)
+
+
+def _object_goal_distance(c, name, p, rec):
+    _robot(c, "reward", name, p)
+    _object(c, "reward", name, p)
+    _pose_command(c, "reward", name, p)
+
+
+def _object_ee_distance(c, name, p, rec):
+    """``ee_frame.data.target_pos_w[:, 0]``: the record carries the robot body of the frame's first target and its offset position."""
+    _object(c, "reward", name, p)
+    body, pos, rot = c.entities.frame(_entity_name(p.get("ee_frame_cfg"), "ee_frame"))
+    if tuple(rot) != (1.0, 0.0, 0.0, 0.0):
+        raise NotImplementedError(f"reward term '{name}': the target frame's offset rotation {rot} is not the identity; the fused op "
+                                  "adds the rotated offset position only")
+    if body not in c.entities.body_names:
+        raise ValueError(f"reward term '{name}': the target frame sits on '{body}', which is not a body of the robot ({c.entities.body_names})")
+    rec.update(ids_off=c.blob.ints([c.entities.body_names.index(body)]), nids=1, p1=f32(pos[0]), p2=f32(pos[1]), p3=f32(pos[2]))
+
+
+def _object_position(c, name, p, rec):
+    _robot(c, "observation", name, p)
+    _object(c, "observation", name, p)
+
+
 _T = f"{_MDP}.terminations:"
 TERMINATION_TERMS = {
     _T + "time_out": _Fused("TIME_OUT"),
     _T + "illegal_contact": _Fused("ILLEGAL_CONTACT", _Ids("sensor_cfg", "body", required=True), params=("threshold",)),
     _T + "joint_pos_out_of_manual_limit": _Fused("JOINT_POS_MANUAL_LIMIT", _JOINTS, hook=_manual_limit_bounds),
     _T + "bad_orientation": _Fused("BAD_ORIENTATION", params=("limit_angle",)),
-    _T + "root_height_below_minimum": _Fused("ROOT_HEIGHT_BELOW_MIN", params=("minimum_height",)),
+    _T + "root_height_below_minimum": _Fused("ROOT_HEIGHT_BELOW_MIN", params=("minimum_height",), hook=_root_height_asset),
     _T + "joint_vel_out_of_limit": _Fused("JOINT_VEL_LIMIT", _JOINTS),
     _T + "joint_vel_out_of_manual_limit": _Fused("JOINT_VEL_MANUAL_LIMIT", _JOINTS, params=("max_velocity",)),
     _T + "joint_effort_out_of_limit": _Fused("JOINT_EFFORT_LIMIT", _JOINTS),
     _T + "command_resample": _Fused("COMMAND_RESAMPLE", hook=_command_resample),
     f"{_VEL}.terminations:terrain_out_of_bounds": _Fused("TERRAIN_OUT_OF_BOUNDS", hook=_terrain_out_of_bounds),
+    f"{_LIFT}.terminations:object_reached_goal": _Fused("OBJECT_REACHED_GOAL", params=(("threshold", 0.02),), hook=_object_reached_goal),  # :25-53
 }
 
 
@@ -479,6 +564,9 @@ REWARD_TERMS = {
     _WC + "power_consumption": _Fused("POWER_CONSUMPTION", hook=_power_consumption),  # :114-140
     **{f"{_REACH}:{f}": _Fused(f.upper(), params=par, hook=functools.partial(_reach_body, f))
        for f, par in (("position_command_error", ()), ("position_command_error_tanh", ("std",)), ("orientation_command_error", ()))},
+    f"{_LIFT}.rewards:object_is_lifted": _Fused("OBJECT_IS_LIFTED", params=("minimal_height",), hook=_object_is_lifted),  # :20-25
+    f"{_LIFT}.rewards:object_ee_distance": _Fused("OBJECT_EE_DISTANCE", params=("std",), hook=_object_ee_distance),  # :28-45
+    f"{_LIFT}.rewards:object_goal_distance": _Fused("OBJECT_GOAL_DISTANCE", params=("std", "minimal_height"), hook=_object_goal_distance),  # :48-67
 }
 
 
@@ -545,10 +633,12 @@ OBSERVATION_TERMS = {
     _OC + "base_up_proj": _Fused("BASE_UP_PROJ", width=1),  # :33-40
     _OC + "base_heading_proj": _Fused("BASE_HEADING_PROJ", width=1, hook=_target_obs),  # :43-58
     _OC + "base_angle_to_target": _Fused("BASE_ANGLE_TO_TARGET", width=1, hook=_target_obs),  # :61-77
+    f"{_LIFT}.observations:object_position_in_robot_root_frame": _Fused("OBJECT_POSITION_IN_ROBOT_ROOT_FRAME", width=3, hook=_object_position),  # :19-31
 }
 
 _JOINT_ACTIONS = ("JointPositionAction", "JointVelocityAction", "JointEffortAction", "RelativeJointPositionAction",
                   "JointPositionToLimitsAction", "EMAJointPositionToLimitsAction")
+_BINARY_ACTIONS = ("BinaryJointPositionAction", "BinaryJointVelocityAction")
 _NOISE_OPS = {"add": F_NOISE_ADD, "scale": F_NOISE_SCALE, "abs": F_NOISE_ABS}
 # noise function -> the scalar parameters in NOISE_LO / NOISE_HI, flag.  constant_noise: u * (b - b) + b == b for every u: the uniform
 # path, bit-identical
@@ -562,7 +652,7 @@ class PlanCompiler:
     def __init__(self, env_cfg: Any, robot: RobotSpec):
         self.cfg = _to_dict(env_cfg)
         self.robot = robot
-        self.entities = SceneEntityResolver(robot)
+        self.entities = SceneEntityResolver(robot, self.cfg.get("scene"))
         self.blob = _Blob()
 
     def compile(self) -> Plan:
@@ -613,16 +703,22 @@ class PlanCompiler:
         self.action_terms: list[Term] = []
         self.act_recs: list[list[int]] = []
         self.action_dim = 0
+        self.processed_dim = 0  # columns of the processed action so far (a binary term writes more joints than it takes columns)
         for name, tcfg in (self.cfg.get("actions") or {}).items():
             if tcfg is None or not isinstance(tcfg, dict) or "class_type" not in tcfg:
                 continue
             cls = func_name(tcfg["class_type"])
             _, cname = _short(cls)
+            if cname in _BINARY_ACTIONS:
+                self._binary_action(name, cls, tcfg)
+                continue
             if cname not in _JOINT_ACTIONS:
                 raise NotImplementedError(f"action term '{name}': class {cls} is not on the fused path")
             ids, jn = resolve_matching_names(tcfg["joint_names"], self.entities.joint_names, bool(tcfg.get("preserve_order")))
             dim = len(ids)
             rec = dict(op=A_JOINT_AFFINE, ids_off=blob.ints(ids), nids=dim, out=self.action_dim, dim=dim)
+            if self.processed_dim != self.action_dim:  # P2 = the first processed column; 0 = the raw column (every plan without a binary term)
+                rec["p2"] = int(self.processed_dim)
             flags = 0
             scale, offset = tcfg.get("scale", 1.0), tcfg.get("offset", 0.0)
             if cname.endswith("JointPositionToLimitsAction") or (cname == "RelativeJointPositionAction" and tcfg.get("use_zero_offset", True)):
@@ -678,8 +774,39 @@ class PlanCompiler:
                 flags |= F_ACT_CLIP
             rec["flags"] = flags
             self.act_recs.append(_rec(**rec))
-            self.action_terms.append(Term(name, cls, A_JOINT_AFFINE, dict(tcfg), dim=dim))
+            self.action_terms.append(Term(name, cls, A_JOINT_AFFINE, dict(tcfg), dim=dim, processed_col=self.processed_dim, processed_dim=dim))
             self.action_dim += dim
+            self.processed_dim += dim
+
+    def _binary_action(self, name: str, cls: str, tcfg: dict) -> None:
+        """``BinaryJointAction.__init__`` (binary_joint_actions.py:47-96): one raw column; every joint of the term gets its entry of the
+        open or the close table (``process_actions`` :118-133).  The position and the velocity class differ in ``apply_actions`` only."""
+        blob = self.blob
+        ids, jn = resolve_matching_names(tcfg["joint_names"], self.entities.joint_names)
+        n = len(ids)
+        tabs = []
+        for key in ("open_command_expr", "close_command_expr"):
+            tab = [0.0] * n
+            i_, n_, v_ = resolve_matching_names_values(tcfg[key], jn)
+            if len(i_) != n:
+                raise ValueError(f"Could not resolve all joints for the action term. Missing: {set(jn) - set(n_)}")
+            for i, v in zip(i_, v_):
+                tab[i] = f32(v)
+            tabs.append(tab)
+        if tcfg.get("clip") is not None:
+            if not isinstance(tcfg["clip"], dict):
+                raise ValueError(f"Unsupported clip type: {type(tcfg['clip'])}. Supported types are dict.")
+            if n != 1:  # the reference's clip tensor is (N, action_dim = 1, 2): indexing it with the ids of several joints fails there
+                raise NotImplementedError(f"action term '{name}': clip on a binary action term over {n} joints")
+            for _, _, (lo, hi) in zip(*resolve_matching_names_values(tcfg["clip"], jn)):
+                tabs = [[min(max(x, f32(lo)), f32(hi)) for x in tab] for tab in tabs]  # clamp(where(m, c, o)) == where(m, clamp(c), clamp(o))
+        rec = dict(op=A_BINARY_JOINT, ids_off=blob.ints(ids), nids=n, out=self.action_dim, dim=1, aux0=blob.floats(tabs[0]), aux1=blob.floats(tabs[1]))
+        if self.processed_dim != self.action_dim:
+            rec["p2"] = int(self.processed_dim)
+        self.act_recs.append(_rec(**rec))
+        self.action_terms.append(Term(name, cls, A_BINARY_JOINT, dict(tcfg), dim=1, processed_col=self.processed_dim, processed_dim=n))
+        self.action_dim += 1
+        self.processed_dim += n
 
     # -- terminations (TerminationManager._prepare_terms)
     def _terminations(self) -> None:
@@ -869,6 +996,7 @@ class PlanCompiler:
             "RAY_YAW_ONLY": 1 if (scanner and scanner.get("attach_yaw_only")) else 0, "CMD_DIM": self.cmd_dim,
             "MOD_STATE": self.mod_state, "NGROUPS": len(groups), "GROUP_OFF": group_off, "SCAN_SUBSTEPS": int(cfg["decimation"]),
             "SCAN_STATEFUL": int(scan_stateful), "TERM_SLOTS": len(self.term_slots),
+            "PA": self.processed_dim if self.processed_dim != self.action_dim else 0,  # 0 = A: the word of every plan without a binary term
         }
         for k, v in hdr.items():
             w[H[k]] = int(v)
@@ -888,7 +1016,7 @@ class PlanCompiler:
                     enable_corruption=any(g_.enable_corruption for g_ in groups), ray_starts_local=ray_local, ray_direction=ray_dir,
                     ray_max_distance=self.ray_max, scanner_cfg=scanner, n_ext_rew=self.n_ext_rew, n_ext_term=self.n_ext_term,
                     n_ext_obs=self.n_ext_obs, gravity_dir=tuple(float(x) for x in gdir), mod_state_dim=self.mod_state,
-                    term_slots=len(self.term_slots))
+                    term_slots=len(self.term_slots), processed_action_dim=self.processed_dim)
 
 
 def compile_plan(env_cfg: Any, robot: RobotSpec) -> Plan:

@@ -108,17 +108,45 @@ def _is_slice_all(x) -> bool:
 
 class SceneEntityResolver:
     """``SceneEntityCfg.resolve`` (isaaclab/managers/scene_entity_cfg.py:112-250) over a robot's name tables: the joint / body ids a
-    ``SceneEntityCfg`` selects.  The term compiler resolves the fused terms' entities with it, the env those of Python-evaluated terms."""
+    ``SceneEntityCfg`` selects.  The term compiler resolves the fused terms' entities with it, the env those of Python-evaluated terms.
 
-    def __init__(self, robot: RobotSpec):
+    ``scene``: the cfg's ``scene`` dict.  Its entries beyond the robot and the two sensors are learnt by ``class_type``: a ``RigidObject`` has
+    one body, named after the last component of its ``prim_path``, and no joints (``self.rigid_objects``); a ``FrameTransformer`` is
+    resolved to its first target frame by :meth:`frame` (``self.frames`` holds the cfg entries)."""
+
+    def __init__(self, robot: RobotSpec, scene: dict | None = None):
         self.joint_names = list(robot.joint_names)
         self.body_names = list(robot.body_names)
+        self.rigid_objects: dict[str, str] = {}  # entity -> its one body's name
+        self.frames: dict[str, dict] = {}
+        for name, ent in (scene or {}).items():
+            cls = ent.get("class_type") if isinstance(ent, dict) else None
+            cls = cls if isinstance(cls, str) or cls is None else f"{cls.__module__}:{cls.__qualname__}"
+            if cls and cls.endswith(":RigidObject"):
+                self.rigid_objects[name] = str(ent.get("prim_path", name)).rstrip("/").rsplit("/", 1)[-1]
+            elif cls and cls.endswith(":FrameTransformer"):
+                self.frames[name] = ent
 
     def names(self, entity: str, kind: str) -> list[str]:
         if entity in ("robot", "contact_forces"):
             return self.joint_names if kind == "joint" else self.body_names
+        if entity in self.rigid_objects:
+            return [] if kind == "joint" else [self.rigid_objects[entity]]
         raise ValueError(f"The scene entity '{entity}' does not exist. Available entities: "
-                         f"['robot', 'contact_forces', 'height_scanner'].")
+                         f"{['robot', 'contact_forces', 'height_scanner'] + list(self.rigid_objects) + list(self.frames)}.")
+
+    def frame(self, entity: str) -> tuple[str, tuple, tuple]:
+        """``target_frames[0]`` of FrameTransformer ``entity`` -> (robot body name, offset position, offset rotation w, x, y, z): the
+        frame sits on the body its ``prim_path`` ends in (frame_transformer.py:189-254)."""
+        if entity not in self.frames:
+            raise ValueError(f"The scene entity '{entity}' is not a FrameTransformer of the scene (it has {list(self.frames)}).")
+        targets = self.frames[entity].get("target_frames") or []
+        if not targets:
+            raise ValueError(f"FrameTransformer '{entity}' has no target frames")
+        t = targets[0]
+        off = t.get("offset") or {}
+        body = str(t["prim_path"]).rstrip("/").rsplit("/", 1)[-1]
+        return body, tuple(float(x) for x in off.get("pos", (0.0, 0.0, 0.0))), tuple(float(x) for x in off.get("rot", (1.0, 0.0, 0.0, 0.0)))
 
     def ids(self, ent, kind: str, default_entity: str = "robot") -> list[int]:
         """joint_ids / body_ids of a SceneEntityCfg (dict form, live object, or None = function default)."""

@@ -23,9 +23,9 @@ DYNAMIC = (
     "last_air_time", "current_air_time", "current_contact_time", "last_contact_time",
 )
 # further per-step tensors only a few optional terms read (body_lin_acc_l2, command_resample, foot_clearance_reward, body_incoming_wrench,
-# the reach rewards): drawn from their own generators so that the tensors above are unchanged by their presence; recorded fixtures carry
-# them only when their cfg needs them
-EXTRA = ("body_lin_acc_w", "command_time_left", "command_counter", "body_pos_w", "link_incoming_joint_force", "body_quat_w")
+# the reach rewards, the lift terms' object): drawn from their own generators so that the tensors above are unchanged by their presence;
+# recorded fixtures carry them only when their cfg needs them
+EXTRA = ("body_lin_acc_w", "command_time_left", "command_counter", "body_pos_w", "link_incoming_joint_force", "body_quat_w", "object_root_pos_w")
 # tensors fixed for the lifetime of the scene
 STATIC = ("default_joint_pos", "default_joint_vel", "soft_joint_pos_limits", "soft_joint_vel_limits", "env_origins")
 
@@ -169,6 +169,15 @@ def generate_body_quat(robot: RobotSpec, num_envs: int, gen: torch.Generator) ->
     return (q / q.norm(dim=-1, keepdim=True).clamp_min(1e-12)).contiguous()
 
 
+def generate_object_offset(num_envs: int, gen: torch.Generator) -> torch.Tensor:
+    """Where the scene's rigid object lies relative to the robot root (N, 3): around the Lift task's initial (0.5, 0, 0.055) m
+    (lift_env_cfg.py / joint_pos_env_cfg.py), x, y ~ N(0, 0.1) about it, the height uniform in [-0.15, 0.5) m -- below the -0.05 m
+    dropping threshold on a sixth of the envs, below and above the 0.04 m lifting height on the rest."""
+    xy = torch.randn(num_envs, 2, generator=gen) * 0.1 + torch.tensor([0.5, 0.0])
+    z = 0.055 + (torch.rand(num_envs, 1, generator=gen) * 0.65 - 0.205)
+    return torch.cat([xy, z], dim=-1).contiguous()
+
+
 # UniformPoseCommand ranges of the Reach tasks (manipulation/reach/reach_env_cfg.py): the position of the end-effector target in the base
 # frame; the orientation is any unit quaternion (the cfgs' roll 0, pitch pi or pi / 2, yaw +-3.14 Euler draws are a subset of it)
 POSE_COMMAND_POS_RANGE = ((0.35, 0.65), (-0.2, 0.2), (0.15, 0.5))
@@ -206,11 +215,13 @@ class StateFeed:
         gen_w = torch.Generator().manual_seed(seed + 0x1F0C)
         gen_q = torch.Generator().manual_seed(seed + 0x0A7E)
         gen_c = torch.Generator().manual_seed(seed + 0x9C3D)
+        gen_o = torch.Generator().manual_seed(seed + 0x0B1E)
         for sn in snaps:
             sn.update(generate_extras(robot, num_envs, gen_x))
             sn["body_pos_w"] = generate_body_pos(robot, num_envs, gen_p)
             sn["link_incoming_joint_force"] = generate_link_wrench(robot, num_envs, gen_w)
             sn["body_quat_w"] = generate_body_quat(robot, num_envs, gen_q)
+            sn["object_root_pos_w"] = generate_object_offset(num_envs, gen_o)  # (the offset; the root position is added below)
             if robot.command_dim == 7:  # a pose command (the velocity command drawn above is dropped: other tensors keep their draws)
                 sn["command"] = generate_pose_command(num_envs, gen_c)
             elif robot.command_dim != 3:
@@ -222,6 +233,7 @@ class StateFeed:
         for k in range(1, num_snapshots):
             delta = (snaps[k]["root_pos_w"] - snaps[k]["env_origins"]).to(self.device)
             self._stack["root_pos_w"][k] = self._static["env_origins"] + delta
+        self._stack["object_root_pos_w"] += self._stack["root_pos_w"]  # RigidObjectData.root_pos_w: next to the robot, in the world frame
         g = torch.tensor(gravity, dtype=torch.float32)
         self.gravity_dir = (g / g.norm().clamp_min(1e-9)).tolist()
         self.index = 0

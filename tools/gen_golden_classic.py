@@ -140,7 +140,7 @@ def run(task: str):
     path = os.path.join(gg.GOLDEN, task + ".npz")
     z = np.load(path)
     # the per-step tensors no classic term reads are left out (run_task records every EXTRA tensor of a kitchen run)
-    unread = ("body_lin_acc_w", "body_pos_w", "command_time_left", "command_counter", "body_quat_w")
+    unread = ("body_lin_acc_w", "body_pos_w", "command_time_left", "command_counter", "body_quat_w", "object_root_pos_w")
     rec = {k: z[k] for k in z.files if k.rpartition("/")[2] not in unread or "/in/" not in k}
     assert events[0][0] == "reset", events[0][0]
     rec["reset/potentials"] = events[0][1].numpy()

@@ -128,7 +128,7 @@ def run(task: str):
     path = os.path.join(gg.GOLDEN, task + ".npz")
     z = np.load(path)
     # the per-step tensors no reach term reads are left out (run_task records every EXTRA tensor of a kitchen run)
-    unread = ("body_lin_acc_w", "command_time_left", "command_counter", "link_incoming_joint_force")
+    unread = ("body_lin_acc_w", "command_time_left", "command_counter", "link_incoming_joint_force", "object_root_pos_w")
     rec = {k: z[k] for k in z.files if k.rpartition("/")[2] not in unread or "/in/" not in k}
     meta = json.loads(str(rec["meta_json"]))
     b = robot.body_names.index(ee)

@@ -122,7 +122,7 @@ def main():
     # terms, none read by Spot's) are left out, so that the file stays the one committed
     path = os.path.join(gg.GOLDEN, TASK + ".npz")
     z = np.load(path)
-    later = ("link_incoming_joint_force", "body_quat_w")
+    later = ("link_incoming_joint_force", "body_quat_w", "object_root_pos_w")
     rec = {k: z[k] for k in z.files if k.rpartition("/")[2] not in later or "/in/" not in k}
     np.savez_compressed(path, **rec)
     dump_managers(env_cfg_cls())

@@ -440,7 +440,8 @@ int imx_reset_orchestrate(const imx_orch_t* orch, imx_stream_t stream);
 
 /* ---- library ---------------------------------------------------------------------------------------------------- */
 const char* imx_version(void);
-/* sizeof of an ABI struct as this library was compiled (which: 0 imx_state_t, 1 imx_buffers_t, 2 imx_head_loss_t, 3 imx_rollout_slot_t, 4 imx_policy_act_t, 5 imx_orch_t, 6 imx_event_term_t), 0 for an unknown index:
+/* sizeof of an ABI struct as this library was compiled (which: 0 imx_state_t, 1 imx_buffers_t, 2 imx_head_loss_t, 3 imx_rollout_slot_t, 4 imx_policy_act_t, 5 imx_orch_t, 6 imx_event_term_t,
+ * 7 imx_diff_ik_t), 0 for an unknown index:
  * a binding checks its own layout against it at load time. */
 size_t imx_struct_size(int which);
 const char* imx_last_error(void);
@@ -890,6 +891,48 @@ int imx_terrain_levels(int64_t N, int64_t num_levels, int64_t num_types, const u
                        const float* command_d, const float* terrain_origins_d, const int64_t* terrain_types_d, float terrain_size_x,
                        float max_episode_length_s, const int64_t* rand_levels_d, uint64_t seed, const int32_t* step_counter_d,
                        int64_t* terrain_levels_d, float* env_origins_d, float* mean_level_d, imx_stream_t stream);
+
+/* ---- DifferentialInverseKinematicsAction ----------------------------------------------------------------------
+ * Parameters of one term (envs/mdp/actions/task_space_actions.py:53-121, controllers/differential_ik_cfg.py:60-70), resolved by
+ * isaaclab_amd/plan.py (plan.ik_terms).  Kept out of the plan blob and of imx_state_t / imx_buffers_t / imx_orch_t. */
+#define IMX_IK_MAX_JOINTS 8
+enum imx_ik_command { IMX_IK_POSITION = 0, IMX_IK_POSE = 1 };
+enum imx_ik_method { IMX_IK_DLS = 0, IMX_IK_TRANS = 1 };
+typedef struct imx_diff_ik {
+    int32_t command_type;      /* imx_ik_command: processed width 3, or 6 (relative) / 7 (absolute) */
+    int32_t use_relative_mode;
+    int32_t ik_method;         /* imx_ik_method */
+    int32_t has_offset;        /* cfg.body_offset is not None */
+    float lambda_val;          /* dls, default 0.01 */
+    float k_val;               /* trans, default 1.0 */
+    float offset_pos[3];
+    float offset_rot[4];       /* w, x, y, z */
+    int32_t body_idx;          /* row of body_pos_w / body_quat_w */
+    int32_t jacobi_body_idx;   /* row of the Jacobian tensor: body_idx - 1 for a fixed base (:72-77) */
+    int32_t num_joints;        /* 1 .. IMX_IK_MAX_JOINTS */
+    int32_t joint_ids[IMX_IK_MAX_JOINTS];        /* columns of joint_pos */
+    int32_t jacobi_joint_ids[IMX_IK_MAX_JOINTS]; /* columns of the Jacobian: joint_ids (+ 6 for a floating base) */
+    int32_t processed_col;     /* first column of the term in the (N, PA) processed action */
+} imx_diff_ik_t;
+
+/* DifferentialInverseKinematicsAction.process_actions / apply_actions (envs/mdp/actions/task_space_actions.py:155-179, 188-229) with
+ * DifferentialIKController.set_command / compute (controllers/differential_ik.py:98-146, 148-240), one lane per env, one launch.
+ * mode bit 1: the command half of process_actions -- ee_pos_des / ee_quat_des from the term's processed columns and the current
+ *   end-effector pose (_compute_frame_pose :188-207; apply_delta_pose utils/math.py:873-910);
+ * mode bit 2: apply_actions (:168-179) -- jacobian_b (:142-149), _compute_frame_jacobian (:209-229), compute_pose_error (utils/math.py:
+ *   820-867, "axis_angle"), then dls (J^T (J J^T + lambda^2 I)^-1 dx, solved by a Cholesky factorisation: no inverse is formed) or trans
+ *   (k J^T dx), joint_pos_des = joint_pos[joint_ids] + dq.  mode 3 does both.
+ * The reference's global test `ee_quat_curr.norm() != 0` (:173), one host sync that is false only before the simulation has produced a
+ * pose, is NOT reproduced: the kernel always computes.
+ * processed_action_d (N, PA); root_pos_w_d (N,3), root_quat_w_d (N,4); body_pos_w_d (N, num_bodies, 3), body_quat_w_d (N, num_bodies, 4);
+ * jacobians_d (N, NB, 6, ND) as root_physx_view.get_jacobians() hands them out, world frame; joint_pos_d (N, J);
+ * ee_pos_des_d (N,3), ee_quat_des_d (N,4); joint_pos_des_d (N, ld_des) with the term's num_joints columns first.
+ * Refused without a launch: a null pointer the mode needs, num_joints outside [1, 8], a body, joint or column index out of range,
+ * processed columns past PA, ld_des < num_joints, an unknown command type / method / mode. */
+int imx_diff_ik(const imx_diff_ik_t* cfg, int64_t N, int mode, const float* processed_action_d, int64_t PA,
+                const float* root_pos_w_d, const float* root_quat_w_d, const float* body_pos_w_d, const float* body_quat_w_d,
+                int64_t num_bodies, const float* jacobians_d, int64_t NB, int64_t ND, const float* joint_pos_d, int64_t J,
+                float* ee_pos_des_d, float* ee_quat_des_d, float* joint_pos_des_d, int64_t ld_des, imx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,29 @@ class ImxOrch(ctypes.Structure):  # imx_orch_t
                 + [("pose_body_idx", c_int32), ("make_quat_unique", c_int32)])
 
 
+IK_MAX_JOINTS = 8
+
+
+class ImxDiffIk(ctypes.Structure):  # imx_diff_ik_t
+    _fields_ = [("command_type", c_int32), ("use_relative_mode", c_int32), ("ik_method", c_int32), ("has_offset", c_int32),
+                ("lambda_val", c_float), ("k_val", c_float), ("offset_pos", c_float * 3), ("offset_rot", c_float * 4),
+                ("body_idx", c_int32), ("jacobi_body_idx", c_int32), ("num_joints", c_int32), ("joint_ids", c_int32 * IK_MAX_JOINTS),
+                ("jacobi_joint_ids", c_int32 * IK_MAX_JOINTS), ("processed_col", c_int32)]
+
+    @classmethod
+    def from_term(cls, ik) -> "ImxDiffIk":
+        """The C struct of a ``plan.IkTerm``."""
+        n = len(ik.joint_ids)
+        if not 1 <= n <= IK_MAX_JOINTS:
+            raise ImxError(f"action term '{ik.name}': {n} controlled joints (1..{IK_MAX_JOINTS})")
+        pos, rot = ik.offset_pos or (0.0, 0.0, 0.0), ik.offset_rot or (1.0, 0.0, 0.0, 0.0)
+        return cls(command_type={"position": 0, "pose": 1}[ik.command_type], use_relative_mode=int(ik.use_relative_mode),
+                   ik_method={"dls": 0, "trans": 1}[ik.ik_method], has_offset=int(ik.offset_pos is not None), lambda_val=ik.lambda_val,
+                   k_val=ik.k_val, offset_pos=(c_float * 3)(*pos), offset_rot=(c_float * 4)(*rot), body_idx=ik.body_idx,
+                   jacobi_body_idx=ik.jacobi_body_idx, num_joints=n, joint_ids=(c_int32 * IK_MAX_JOINTS)(*ik.joint_ids),
+                   jacobi_joint_ids=(c_int32 * IK_MAX_JOINTS)(*ik.jacobi_joint_ids), processed_col=ik.processed_col)
+
+
 class ImxError(RuntimeError):
     pass
 
@@ -162,6 +185,8 @@ _SIGNATURES = {
                                          c_void_p, c_void_p]),
     "imx_terrain_levels": (c_int, [c_int64, c_int64, c_int64] + [c_void_p] * 5 + [c_float, c_float, c_void_p, c_uint64, c_void_p]
                            + [c_void_p] * 3 + [c_void_p]),
+    "imx_diff_ik": (c_int, [POINTER(ImxDiffIk), c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                            c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "imx_mlp_scratch_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "imx_mlp_dw": (c_int, [c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "imx_mlp_set_dw_cu_budget": (c_int, [c_int]),
@@ -211,7 +236,7 @@ def lib():
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
-    for which, cls in enumerate((ImxState, ImxBuffers, ImxHeadLoss, ImxRolloutSlot, ImxPolicyAct, ImxOrch, ImxEventTerm)):  # the binding's struct layouts against the library's
+    for which, cls in enumerate((ImxState, ImxBuffers, ImxHeadLoss, ImxRolloutSlot, ImxPolicyAct, ImxOrch, ImxEventTerm, ImxDiffIk)):  # the binding's struct layouts against the library's
         if int(L.imx_struct_size(which)) != ctypes.sizeof(cls):
             raise ImxError(f"{LIB_PATH}: sizeof({cls.__name__}) is {int(L.imx_struct_size(which))} in the library, {ctypes.sizeof(cls)} in the "
                            "binding -- rebuild with `python -m isaaclab_amd.build`")

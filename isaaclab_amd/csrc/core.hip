@@ -31,6 +31,7 @@ extern "C" size_t imx_struct_size(int which) {
         case 4: return sizeof(imx_policy_act_t);
         case 5: return sizeof(imx_orch_t);
         case 6: return sizeof(imx_event_term_t);
+        case 7: return sizeof(imx_diff_ik_t);
         default: return 0;
     }
 }

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/imx.h"
+#include "imx_quat.h"
 
 #define IMX_WAVE 64
 
@@ -163,26 +164,7 @@ IMX_DEV void quat_apply_yaw_only(float w, float z, float vx, float vy, float vz,
     oz = vz + w * tz + (0.0f * ty - 0.0f * tx);
 }
 
-// full quat_apply
-IMX_DEV void quat_apply(float w, float x, float y, float z, float vx, float vy, float vz, float& ox, float& oy,
-                        float& oz) {
-    const float tx = (y * vz - z * vy) * 2.0f, ty = (z * vx - x * vz) * 2.0f, tz = (x * vy - y * vx) * 2.0f;
-    ox = vx + w * tx + (y * tz - z * ty);
-    oy = vy + w * ty + (z * tx - x * tz);
-    oz = vz + w * tz + (x * ty - y * tx);
-}
-
-// quat_mul (utils/math.py:464-500): the reference's eight-product form with its association, quaternions w, x, y, z in .x .. .w
-IMX_DEV float4 quat_mul_ref(float4 a, float4 b) {
-    const float w1 = a.x, x1 = a.y, y1 = a.z, z1 = a.w, w2 = b.x, x2 = b.y, y2 = b.z, z2 = b.w;
-    const float ww = (z1 + x1) * (x2 + y2);
-    const float yy = (w1 - y1) * (w2 + z2);
-    const float zz = (w1 + y1) * (w2 - z2);
-    const float xx = ww + yy + zz;
-    const float qq = 0.5f * (xx + (z1 - x1) * (x2 - y2));
-    return make_float4(qq - ww + (z1 - y1) * (y2 - z2), qq - xx + (x1 + w1) * (x2 + w2), qq - yy + (w1 - x1) * (y2 + z2),
-                       qq - zz + (z1 + y1) * (w2 - x2));
-}
+// quat_apply, quat_mul_ref and axis_angle_from_quat_ref live in imx_quat.h (shared with host C++)
 // ||axis_angle_from_quat(d)|| (utils/math.py:646-675) step by step: the w < 0 flip (q * (1 - 2 (w < 0))), half = atan2(||xyz||, w),
 // angle = 2 half, the |angle| <= 1e-6 Taylor branch 0.5 - angle^2 / 48, then xyz / that factor and its norm
 IMX_DEV float axis_angle_magnitude(float4 d) {

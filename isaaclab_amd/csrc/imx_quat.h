@@ -1,0 +1,53 @@
+// Quaternion helpers that compile both as gfx950 device code and as plain host C++ (tools/diff_ik_host.cpp): no HIP header is needed on
+// the host side.  Quaternions are w, x, y, z in .x .. .w of a float4.
+#pragma once
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define IMX_HD static __host__ __device__ __forceinline__
+#define IMX_UNROLL _Pragma("unroll")
+#else
+#include <cmath>
+#include <cstdint>
+struct float4 {
+    float x, y, z, w;
+};
+static inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
+#define IMX_HD static inline
+#define IMX_UNROLL
+#endif
+
+// full quat_apply (isaaclab/utils/math.py:545-564): t = 2*cross(xyz, v);  out = v + w*t + cross(xyz, t)
+IMX_HD void quat_apply(float w, float x, float y, float z, float vx, float vy, float vz, float& ox, float& oy,
+                       float& oz) {
+    const float tx = (y * vz - z * vy) * 2.0f, ty = (z * vx - x * vz) * 2.0f, tz = (x * vy - y * vx) * 2.0f;
+    ox = vx + w * tx + (y * tz - z * ty);
+    oy = vy + w * ty + (z * tx - x * tz);
+    oz = vz + w * tz + (x * ty - y * tx);
+}
+
+// quat_mul (utils/math.py:464-500): the reference's eight-product form with its association, quaternions w, x, y, z in .x .. .w
+IMX_HD float4 quat_mul_ref(float4 a, float4 b) {
+    const float w1 = a.x, x1 = a.y, y1 = a.z, z1 = a.w, w2 = b.x, x2 = b.y, y2 = b.z, z2 = b.w;
+    const float ww = (z1 + x1) * (x2 + y2);
+    const float yy = (w1 - y1) * (w2 + z2);
+    const float zz = (w1 + y1) * (w2 - z2);
+    const float xx = ww + yy + zz;
+    const float qq = 0.5f * (xx + (z1 - x1) * (x2 - y2));
+    return make_float4(qq - ww + (z1 - y1) * (y2 - z2), qq - xx + (x1 + w1) * (x2 + w2), qq - yy + (w1 - x1) * (y2 + z2),
+                       qq - zz + (z1 + y1) * (w2 - x2));
+}
+
+// axis_angle_from_quat (utils/math.py:646-675) step by step: the w < 0 flip (q * (1 - 2 (w < 0))), half = atan2(||xyz||, w),
+// angle = 2 half, the |angle| <= 1e-6 Taylor branch 0.5 - angle^2 / 48, then xyz / that factor
+IMX_HD void axis_angle_from_quat_ref(float4 d, float& ax, float& ay, float& az) {
+    const float sg = 1.0f - 2.0f * (d.x < 0.0f ? 1.0f : 0.0f);
+    const float w = d.x * sg, x = d.y * sg, y = d.z * sg, z = d.w * sg;
+    const float mag = sqrtf((x * x + y * y) + z * z);
+    const float half = atan2f(mag, w);
+    const float angle = 2.0f * half;
+    const float s = fabsf(angle) > 1.0e-6f ? sinf(half) / angle : 0.5f - angle * angle / 48.0f;
+    ax = x / s;
+    ay = y / s;
+    az = z / s;
+}

@@ -182,6 +182,22 @@ class _ActionTermView:
         return self._env._processed_action[:, self._p0:self._p0 + self._pdim]
 
 
+class _IkActionTermView(_ActionTermView):
+    """The DifferentialInverseKinematicsAction term: its desired pose and the joint targets ``apply_action`` leaves."""
+
+    @property
+    def ee_pos_des(self):
+        return self._env._ee_pos_des
+
+    @property
+    def ee_quat_des(self):
+        return self._env._ee_quat_des
+
+    @property
+    def joint_pos_des(self):
+        return self._env._joint_pos_des
+
+
 class ActionManager:
     """View with the public surface of isaaclab/managers/action_manager.py:228-359."""
 
@@ -189,8 +205,10 @@ class ActionManager:
         self._env = env
         self._terms = {}
         c = 0
+        ik_names = {ik.name for ik in env.plan.ik_terms}
         for t in env.plan.action_terms:
-            self._terms[t.name] = _ActionTermView(env, t.name, c, t.dim, t.processed_col, t.processed_dim)
+            view = _IkActionTermView if t.name in ik_names else _ActionTermView
+            self._terms[t.name] = view(env, t.name, c, t.dim, t.processed_col, t.processed_dim)
             c += t.dim
 
     @property
@@ -219,8 +237,11 @@ class ActionManager:
     def process_action(self, action: torch.Tensor):
         self._env._process_action(action)
 
-    def apply_action(self):  # the processed targets would go to PhysX here
-        pass
+    def apply_action(self):
+        """Once per physics substep.  A DifferentialInverseKinematicsAction computes its joint targets here (task_space_actions.py:
+        168-179); for every other term the processed targets would go to PhysX and nothing is left to compute."""
+        if self._env._ik is not None:
+            self._env._diff_ik(2)
 
     def reset(self, env_ids=None) -> dict:
         ids = slice(None) if env_ids is None else env_ids
@@ -228,7 +249,8 @@ class ActionManager:
         self._env._action[ids] = 0.0
         # EMAJointPositionToLimitsAction.reset (joint_actions_to_limits.py:208-217): the moving average restarts from the joint positions
         # (inside env.step() the action kernel does this itself for the envs the step kernel reset).  A binary joint term zeroes its raw
-        # action only (binary_joint_actions.py:135): done above
+        # action only (binary_joint_actions.py:135), and so does a DifferentialInverseKinematicsAction (task_space_actions.py:181-182: the
+        # desired pose survives until the next process_action): done above
         for t in self._env.plan.action_terms:
             if t.func.rsplit(":", 1)[-1].rsplit(".", 1)[-1] == "EMAJointPositionToLimitsAction":
                 from .robots import resolve_matching_names
@@ -651,6 +673,12 @@ class ManagerBasedRLEnv:
         z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
         self._episode_length_buf = z(N, dtype=torch.long)
         self._action, self._prev_action, self._processed_action = z(N, max(A, 1)), z(N, max(A, 1)), z(N, max(plan.processed_action_dim, 1))
+        # a DifferentialInverseKinematicsAction's controller state and output (imx_diff_ik); the Jacobians come from the feed
+        self._ik = plan.ik_terms[0] if plan.ik_terms else None
+        if self._ik is not None:
+            self._ik_cfg = _lib.ImxDiffIk.from_term(self._ik)
+            self._ee_pos_des, self._ee_quat_des, self._joint_pos_des = z(N, 3), z(N, 4), z(N, len(self._ik.joint_ids))
+            self.feed.ensure_jacobians()
         self._reward_buf = z(N)
         self._episode_sums = z(K, N)
         self._step_reward = z(N, K)
@@ -1025,6 +1053,23 @@ class ManagerBasedRLEnv:
         clip = math.inf if self.clip_actions is None else float(self.clip_actions)
         check(self._lib.imx_action_process(self._plan_h, self.num_envs, a.data_ptr(), clip, ctypes.byref(self._state()),
                                            ctypes.byref(self._bufs), _lib.current_stream(self.device)))
+        if self._ik is not None:  # the command half of DifferentialInverseKinematicsAction.process_actions
+            self._diff_ik(1)
+
+    def _diff_ik(self, mode: int):
+        """``imx_diff_ik`` on the current state: mode 1 = the desired pose from the processed action, 2 = apply_actions, 3 = both.  The
+        feed's tensors are per-snapshot views, as in ``_state()``: the pointers are taken per call (a captured rollout records one launch
+        per step, each with the pointers of its snapshot).  No host sync."""
+        f, ik = self.feed, self._ik
+        ar = self.articulation
+        root_pos, root_quat = (ar.root_pos_w, ar.root_quat_w) if ar is not None else (f["root_pos_w"], f["root_quat_w"])
+        jac, bp = f["jacobians"], f["body_pos_w"]
+        check(self._lib.imx_diff_ik(ctypes.byref(self._ik_cfg), self.num_envs, mode, self._processed_action.data_ptr(),
+                                    self._processed_action.shape[1], root_pos.data_ptr(), root_quat.data_ptr(), bp.data_ptr(),
+                                    f["body_quat_w"].data_ptr(), bp.shape[1], jac.data_ptr(), jac.shape[1], jac.shape[3],
+                                    f["joint_pos"].data_ptr(), f["joint_pos"].shape[1], self._ee_pos_des.data_ptr(),
+                                    self._ee_quat_des.data_ptr(), self._joint_pos_des.data_ptr(), self._joint_pos_des.shape[1],
+                                    _lib.current_stream(self.device)))
 
     def _eval_external(self, kind: str):
         for col, (term, fn) in enumerate(self._ext_funcs[kind] if kind != "obs" else ()):  # (each term is called ONCE per step: class terms keep state)
@@ -1068,6 +1113,10 @@ class ManagerBasedRLEnv:
         """An env-owned ``producers.ActuatorNetLSTM``: its hidden / cell state restarts with the env (scene.reset -> Articulation.reset ->
         ActuatorNetLSTM.reset, actuators/actuator_net.py:66-70) inside the orchestration launch.  It is fed the processed action as its
         (N, J) joint targets, so the action terms must write one target per joint."""
+        if self._ik is not None:
+            raise ValueError(f"attach_actuator: the processed action of '{self._ik.name}' (DifferentialInverseKinematicsAction) is a task-space "
+                             "command, not a row of joint targets; the term's targets are joint_pos_des "
+                             f"(action_manager.get_term('{self._ik.name}').joint_pos_des), for its {len(self._ik.joint_ids)} joints only")
         if self.plan.processed_action_dim != self.plan.num_joints:
             raise ValueError(f"attach_actuator: the action terms write {self.plan.processed_action_dim} joint targets, the robot has "
                              f"{self.plan.num_joints} joints")
@@ -1224,6 +1273,11 @@ class ManagerBasedRLEnv:
             f = self.feed
             for _ in range(int(self.cfg_decimation)):
                 self.actuator_net.compute(self._processed_action, f["joint_pos"], f["joint_vel"])
+        if self._ik is not None:
+            # ... and ActionManager.apply_action() before every physics step (:185): the IK term's joint targets from the state of that
+            # substep.  Entered from the fused rollout the actor head has only processed the action: the first launch also sets the command
+            for k in range(int(self.cfg_decimation)):
+                self._diff_ik(3 if (k == 0 and rollout_slot is not None) else 2)
         self._sim_step_counter += int(self.cfg_decimation)
         self.feed.advance()
         if self.articulation is not None:

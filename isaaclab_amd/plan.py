@@ -126,6 +126,97 @@ class Term:
     processed_dim: int = 0
 
 
+IK_MAX_JOINTS = 8  # IMX_IK_MAX_JOINTS (include/imx.h)
+_IK_WIDTH = {("position", False): 3, ("position", True): 3, ("pose", True): 6, ("pose", False): 7}  # DifferentialIKController.action_dim
+
+
+@dataclasses.dataclass
+class IkTerm:
+    """One ``DifferentialInverseKinematicsAction`` as resolved by its ``__init__`` (task_space_actions.py:53-121): the parameters of
+    ``imx_diff_ik_t``.  They travel beside the plan, not in its blob."""
+
+    name: str
+    command_type: str  # "position" | "pose"
+    use_relative_mode: bool
+    ik_method: str  # "dls" | "trans"
+    lambda_val: float
+    k_val: float
+    offset_pos: tuple | None  # cfg.body_offset, or None
+    offset_rot: tuple | None
+    body_name: str
+    body_idx: int
+    jacobi_body_idx: int
+    joint_ids: list
+    jacobi_joint_ids: list
+    action_col: int  # first raw column
+    processed_col: int  # first processed column
+    width: int  # raw = processed columns: 3, 6 or 7
+    scale: list  # per column
+    clip: list | None  # per column (lo, hi), or None
+
+
+def resolve_ik_term(name: str, tcfg: dict, robot: RobotSpec, action_col: int = 0, processed_col: int = 0, joint_names=None) -> IkTerm:
+    """``DifferentialInverseKinematicsAction.__init__`` (task_space_actions.py:53-121) and the controller cfg's defaults
+    (differential_ik_cfg.py:60-70) over a robot's name tables."""
+    ctrl = tcfg.get("controller")
+    missing = [k for k in ("joint_names", "body_name", "controller") if tcfg.get(k) is None]
+    missing += [f"controller.{k}" for k in ("command_type", "ik_method") if isinstance(ctrl, dict) and ctrl.get(k) is None]
+    if missing or not isinstance(ctrl, dict):  # (MISSING fields of the configclass: the reference stops at cfg validation)
+        raise NotImplementedError(f"action term '{name}': a DifferentialInverseKinematicsAction cfg without {missing or ['a controller dict']} "
+                                  "is not on the fused path")
+    command_type, method = ctrl["command_type"], ctrl["ik_method"]
+    relative = bool(ctrl.get("use_relative_mode", False))
+    if command_type not in ("position", "pose"):
+        raise ValueError(f"Unsupported inverse-kinematics command: {command_type}.")
+    if method not in ("pinv", "svd", "trans", "dls"):
+        raise ValueError(f"Unsupported inverse-kinematics method: {method}.")
+    if method in ("pinv", "svd"):
+        raise NotImplementedError(f"action term '{name}': ik_method '{method}' is not on the fused path (it needs an SVD inside the kernel); "
+                                  "'dls' and 'trans' are")
+    params = {"trans": {"k_val": 1.0}, "dls": {"lambda_val": 0.01}}[method]
+    params.update(ctrl.get("ik_params") or {})
+    joint_ids, jn = resolve_matching_names(tcfg["joint_names"], list(joint_names if joint_names is not None else robot.joint_names))
+    body_ids, body_names = resolve_matching_names(tcfg["body_name"], list(robot.body_names))
+    if len(body_ids) != 1:
+        raise ValueError(f"Expected one match for the body name: {tcfg['body_name']}. Found {len(body_ids)}: {body_names}.")
+    n = len(joint_ids)
+    if n > IK_MAX_JOINTS:
+        raise NotImplementedError(f"action term '{name}': {n} controlled joints; the differential-IK kernel takes at most {IK_MAX_JOINTS}")
+    body_idx = body_ids[0]
+    if robot.fixed_base:  # the Jacobian of a fixed base has no row for the root body and no root columns (:72-77)
+        jb, jcols = body_idx - 1, list(joint_ids)
+        if jb < 0:
+            raise ValueError(f"action term '{name}': body '{body_names[0]}' is the root of a fixed-base articulation: it has no Jacobian row")
+    else:
+        jb, jcols = body_idx, [i + 6 for i in joint_ids]
+    width = _IK_WIDTH[(command_type, relative)]
+    scale = tcfg.get("scale", 1.0)
+    if isinstance(scale, (int, float)):
+        scale = [float(scale)] * width
+    else:
+        scale = [float(v) for v in scale]
+        if len(scale) != width:  # torch.tensor(cfg.scale) broadcast into (N, action_dim)
+            raise ValueError(f"action term '{name}': scale has {len(scale)} entries for {width} action columns")
+    clip = None
+    if tcfg.get("clip") is not None:
+        if not isinstance(tcfg["clip"], dict):
+            raise ValueError(f"Unsupported clip type: {type(tcfg['clip'])}. Supported types are dict.")
+        clip = [(-math.inf, math.inf)] * width
+        # the reference resolves the keys against the term's JOINT names and indexes the action columns with the result (:117-118)
+        i_, _, v_ = resolve_matching_names_values(tcfg["clip"], jn)
+        for i, v in zip(i_, v_):
+            if i >= width:
+                raise IndexError(f"action term '{name}': clip key matches joint {i} of the term, past its {width} action columns")
+            clip[i] = (float(v[0]), float(v[1]))
+    off = tcfg.get("body_offset")
+    return IkTerm(name=name, command_type=command_type, use_relative_mode=relative, ik_method=method,
+                  lambda_val=float(params.get("lambda_val", 0.01)), k_val=float(params.get("k_val", 1.0)),
+                  offset_pos=None if off is None else tuple(float(v) for v in off.get("pos", (0.0, 0.0, 0.0))),
+                  offset_rot=None if off is None else tuple(float(v) for v in off.get("rot", (1.0, 0.0, 0.0, 0.0))),
+                  body_name=body_names[0], body_idx=int(body_idx), jacobi_body_idx=int(jb), joint_ids=[int(i) for i in joint_ids],
+                  jacobi_joint_ids=[int(i) for i in jcols], action_col=action_col, processed_col=processed_col, width=width, scale=scale, clip=clip)
+
+
 @dataclasses.dataclass
 class Plan:
     blob: np.ndarray  # int32 words
@@ -162,6 +253,7 @@ class Plan:
     scan_drift_range: tuple[float, float] = (0.0, 0.0)
     term_slots: int = 0  # rows of per-env reward-term state (imx_buffers.term_state): one per progress_reward term
     processed_action_dim: int = 0  # width of the processed action (= action_dim unless a term writes more joints than it takes columns)
+    ik_terms: list = dataclasses.field(default_factory=list)  # IkTerm of the env's DifferentialInverseKinematicsAction (at most one)
 
 
 @dataclasses.dataclass
@@ -639,6 +731,7 @@ OBSERVATION_TERMS = {
 _JOINT_ACTIONS = ("JointPositionAction", "JointVelocityAction", "JointEffortAction", "RelativeJointPositionAction",
                   "JointPositionToLimitsAction", "EMAJointPositionToLimitsAction")
 _BINARY_ACTIONS = ("BinaryJointPositionAction", "BinaryJointVelocityAction")
+_IK_ACTION = "isaaclab.envs.mdp.actions.task_space_actions:DifferentialInverseKinematicsAction"
 _NOISE_OPS = {"add": F_NOISE_ADD, "scale": F_NOISE_SCALE, "abs": F_NOISE_ABS}
 # noise function -> the scalar parameters in NOISE_LO / NOISE_HI, flag.  constant_noise: u * (b - b) + b == b for every u: the uniform
 # path, bit-identical
@@ -704,6 +797,7 @@ class PlanCompiler:
         self.act_recs: list[list[int]] = []
         self.action_dim = 0
         self.processed_dim = 0  # columns of the processed action so far (a binary term writes more joints than it takes columns)
+        self.ik_terms: list[IkTerm] = []
         for name, tcfg in (self.cfg.get("actions") or {}).items():
             if tcfg is None or not isinstance(tcfg, dict) or "class_type" not in tcfg:
                 continue
@@ -711,6 +805,9 @@ class PlanCompiler:
             _, cname = _short(cls)
             if cname in _BINARY_ACTIONS:
                 self._binary_action(name, cls, tcfg)
+                continue
+            if cls == _IK_ACTION:
+                self._ik_action(name, cls, tcfg)
                 continue
             if cname not in _JOINT_ACTIONS:
                 raise NotImplementedError(f"action term '{name}': class {cls} is not on the fused path")
@@ -777,6 +874,36 @@ class PlanCompiler:
             self.action_terms.append(Term(name, cls, A_JOINT_AFFINE, dict(tcfg), dim=dim, processed_col=self.processed_dim, processed_dim=dim))
             self.action_dim += dim
             self.processed_dim += dim
+
+    def _ik_action(self, name: str, cls: str, tcfg: dict) -> None:
+        """``DifferentialInverseKinematicsAction`` (task_space_actions.py:53-166): raw -> processed is ``raw * scale`` and an optional
+        clip, which the A_JOINT_AFFINE record already does (offset 0, no flag but the clip's); the controller's parameters go to
+        ``ik_terms``.  The record's id list only has to pass the blob validation: without the default-offset, to-limits or EMA flag
+        ``action_process_element`` loads the id and never indexes a joint array with it, so it is joint 0 for every column."""
+        if self.ik_terms:
+            raise NotImplementedError(f"action term '{name}': a second DifferentialInverseKinematicsAction (after '{self.ik_terms[0].name}'); "
+                                      "the fused path runs one per env")
+        blob = self.blob
+        ik = resolve_ik_term(name, tcfg, self.robot, action_col=self.action_dim, processed_col=self.processed_dim, joint_names=self.entities.joint_names)
+        dim = ik.width
+        rec = dict(op=A_JOINT_AFFINE, ids_off=blob.ints([0] * dim), nids=dim, out=self.action_dim, dim=dim, p1=0.0)
+        if self.processed_dim != self.action_dim:
+            rec["p2"] = int(self.processed_dim)
+        if len(set(ik.scale)) == 1:
+            rec["p0"] = ik.scale[0]
+        else:
+            rec["aux0"] = blob.floats(ik.scale)
+        flags = 0
+        if ik.clip is not None:
+            rec["ids2_off"] = blob.floats([x for lo_hi in ik.clip for x in lo_hi])
+            rec["nids2"] = 2 * dim
+            flags |= F_ACT_CLIP
+        rec["flags"] = flags
+        self.act_recs.append(_rec(**rec))
+        self.action_terms.append(Term(name, cls, A_JOINT_AFFINE, dict(tcfg), dim=dim, processed_col=self.processed_dim, processed_dim=dim))
+        self.ik_terms.append(ik)
+        self.action_dim += dim
+        self.processed_dim += dim
 
     def _binary_action(self, name: str, cls: str, tcfg: dict) -> None:
         """``BinaryJointAction.__init__`` (binary_joint_actions.py:47-96): one raw column; every joint of the term gets its entry of the
@@ -1016,7 +1143,7 @@ class PlanCompiler:
                     enable_corruption=any(g_.enable_corruption for g_ in groups), ray_starts_local=ray_local, ray_direction=ray_dir,
                     ray_max_distance=self.ray_max, scanner_cfg=scanner, n_ext_rew=self.n_ext_rew, n_ext_term=self.n_ext_term,
                     n_ext_obs=self.n_ext_obs, gravity_dir=tuple(float(x) for x in gdir), mod_state_dim=self.mod_state,
-                    term_slots=len(self.term_slots), processed_action_dim=self.processed_dim)
+                    term_slots=len(self.term_slots), processed_action_dim=self.processed_dim, ik_terms=self.ik_terms)
 
 
 def compile_plan(env_cfg: Any, robot: RobotSpec) -> Plan:

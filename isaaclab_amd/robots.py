@@ -78,6 +78,7 @@ class RobotSpec:
     joint_pos_limits: tuple[float, float] = (-2.0 * math.pi, 2.0 * math.pi)
     joint_vel_limit: float = 100.0
     command_dim: int = 3  # width of the command the state feed serves: 3 = base velocity (vx, vy, wz), 7 = end-effector pose
+    fixed_base: bool = False  # Articulation.is_fixed_base: PhysX then computes no Jacobian row for the root body and no root columns
 
     @property
     def num_joints(self) -> int:
@@ -273,6 +274,7 @@ FRANKA_PANDA = RobotSpec(
                        "panda_joint6": 3.037, "panda_joint7": 0.741, "panda_finger_joint.*": 0.04},
     default_root_height=0.0,
     command_dim=7,
+    fixed_base=True,
 )
 
 UR10 = RobotSpec(
@@ -283,6 +285,7 @@ UR10 = RobotSpec(
                        "wrist_2_joint": 0.0, "wrist_3_joint": 0.0},
     default_root_height=0.0,
     command_dim=7,
+    fixed_base=True,
 )
 
 ROBOTS = {r.name: r for r in (ANYMAL_C, G1, CARTPOLE, SPOT, ANT, HUMANOID, FRANKA_PANDA, UR10)}

@@ -178,6 +178,17 @@ def generate_object_offset(num_envs: int, gen: torch.Generator) -> torch.Tensor:
     return torch.cat([xy, z], dim=-1).contiguous()
 
 
+def generate_jacobians(robot: RobotSpec, num_envs: int, gen: torch.Generator) -> torch.Tensor:
+    """``root_physx_view.get_jacobians()`` (N, NB, 6, ND), world frame: NB = the bodies (without the root body of a fixed base), ND =
+    the joints (after six root columns of a floating base).  Linear rows 0-2 ~ U(-0.8, 0.8), angular rows 3-5 ~ U(-1, 1): the size of
+    an arm's entries a metre from its joints."""
+    NB = robot.num_bodies - 1 if robot.fixed_base else robot.num_bodies
+    ND = robot.num_joints if robot.fixed_base else robot.num_joints + 6
+    lin = torch.rand(num_envs, NB, 3, ND, generator=gen) * 1.6 - 0.8
+    ang = torch.rand(num_envs, NB, 3, ND, generator=gen) * 2.0 - 1.0
+    return torch.cat([lin, ang], dim=2).contiguous()
+
+
 # UniformPoseCommand ranges of the Reach tasks (manipulation/reach/reach_env_cfg.py): the position of the end-effector target in the base
 # frame; the orientation is any unit quaternion (the cfgs' roll 0, pitch pi or pi / 2, yaw +-3.14 Euler draws are a subset of it)
 POSE_COMMAND_POS_RANGE = ((0.35, 0.65), (-0.2, 0.2), (0.15, 0.5))
@@ -201,8 +212,9 @@ class StateFeed:
 
     def __init__(self, robot: RobotSpec, num_envs: int, device: str | torch.device = "cpu", seed: int = 42,
                  num_snapshots: int = 4, history: int = 3, extent_xy: tuple[float, float] | None = None,
-                 gravity=(0.0, 0.0, -9.81)):
+                 gravity=(0.0, 0.0, -9.81), jacobians: bool = False):
         self.robot = robot
+        self.seed = seed
         self.num_envs = num_envs
         self.device = torch.device(device)
         self.num_snapshots = num_snapshots
@@ -237,6 +249,21 @@ class StateFeed:
         g = torch.tensor(gravity, dtype=torch.float32)
         self.gravity_dir = (g / g.norm().clamp_min(1e-9)).tolist()
         self.index = 0
+        if jacobians:
+            self.ensure_jacobians()
+
+    def ensure_jacobians(self) -> None:
+        """Serve ``feed["jacobians"]`` (:func:`generate_jacobians`): built on the first request from a generator of its own seeded off
+        the feed's seed, so no other tensor changes by a bit and a feed that never asks allocates nothing.  A recorded feed
+        (``from_tensors``) has them only when its snapshots carried them."""
+        if "jacobians" in self._stack:
+            return
+        seed = getattr(self, "seed", None)
+        if seed is None:
+            raise KeyError("this recorded feed carries no 'jacobians'")
+        gen = torch.Generator().manual_seed(seed + 0x7AC0)
+        self._stack["jacobians"] = torch.stack([generate_jacobians(self.robot, self.num_envs, gen) for _ in range(self.num_snapshots)],
+                                               dim=0).to(self.device).contiguous()
 
     @classmethod
     def from_tensors(cls, robot: RobotSpec, snapshots: list[dict[str, torch.Tensor]], device="cpu",
@@ -250,7 +277,7 @@ class StateFeed:
         self.history = snapshots[0]["net_forces_w_history"].shape[1]
         self._stack = {
             n: torch.stack([torch.as_tensor(s[n]) for s in snapshots], 0).to(self.device).contiguous()
-            for n in DYNAMIC + EXTRA if n in snapshots[0]
+            for n in DYNAMIC + EXTRA + ("jacobians",) if n in snapshots[0]
         }
         self._static = {n: torch.as_tensor(snapshots[0][n]).to(self.device).contiguous() for n in STATIC}
         self.gravity_dir = [float(x) for x in gravity_dir]

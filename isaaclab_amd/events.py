@@ -15,7 +15,7 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _abi, _lib
 from ._lib import check, lib
 
 AXES = ("x", "y", "z", "roll", "pitch", "yaw")
@@ -140,8 +140,7 @@ class TerrainCurriculum:
 
 
 # ---------------------------------------------------------------------------------------------------- orchestration (imx_reset_orchestrate)
-_EVENT_OPS = {"reset_root_state_uniform": 1, "reset_joints_by_scale": 2, "reset_joints_by_offset": 3, "push_by_setting_velocity": 4,
-              "apply_external_force_torque": 5, "reset_joints_around_default": 6}
+_EVENT_OPS = {member[len("IMX_E_"):].lower(): value for member, value in _abi.ENUMS["imx_event_op"].items()}
 _INTERVAL_OK = ("push_by_setting_velocity", "apply_external_force_torque")
 
 

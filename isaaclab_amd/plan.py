@@ -20,49 +20,25 @@ from typing import Any, Callable, NamedTuple
 
 import numpy as np
 
+from . import _abi
+from ._lib import IK_MAX_JOINTS
 from .robots import RobotSpec, SceneEntityResolver, resolve_matching_names, resolve_matching_names_values
 
-# ---- constants mirrored from include/imx.h (tests/test_boundary.py checks they agree) --------------------------
-MAGIC = 0x31584D49
-PLAN_VERSION = 3
-HEADER_WORDS = 48
-MAX_OBS_GROUPS = 4
-REC_WORDS = 20
-H = dict(MAGIC=0, VERSION=1, J=2, B=3, H=4, A=5, D=6, R=7, NTERM=8, NREW=9, NOBS=10, NACT=11, MAX_EP_LEN=12,
-         STEP_DT=13, TERM_OFF=14, REW_OFF=15, OBS_OFF=16, ACT_OFF=17, TOTAL_WORDS=18, NB=19, GRAV_X=20, GRAV_Y=21,
-         GRAV_Z=22, NREW_ALL=23, RAY_OFF=24, RAYDIR_X=25, RAYDIR_Y=26, RAYDIR_Z=27, RAY_MAXDIST=28, MAX_EP_LEN_S=29,
-         NEXT_REW=30, NEXT_TERM=31, NEXT_OBS=32, RAY_YAW_ONLY=33, CMD_DIM=34, MOD_STATE=35, NGROUPS=36, GROUP_OFF=37,
-         SCAN_PERIOD=38, SCAN_DT=39, SCAN_SUBSTEPS=40, SCAN_DRIFT_LO=41, SCAN_DRIFT_HI=42, SCAN_STATEFUL=43, TERM_SLOTS=44, PA=45)
-R = dict(OP=0, IDS_OFF=1, NIDS=2, IDS2_OFF=3, NIDS2=4, WEIGHT=5, P0=6, P1=7, P2=8, P3=9, OUT=10, DIM=11, FLAGS=12,
-         NOISE_LO=13, NOISE_HI=14, CLIP_LO=15, CLIP_HI=16, SCALE=17, AUX0=18, AUX1=19)
-F_NOISE_ADD, F_NOISE_SCALE, F_NOISE_ABS, F_CLIP, F_SCALE, F_QUAT_UNIQUE, F_MODIFIERS, F_SCAN_TWIN = 1, 2, 4, 8, 16, 32, 64, 128
-F_NOISE_GAUSS = 1024
-F_ACT_TO_LIMITS = 8
-F_ACT_EMA = 16
-M_OPS = dict(SCALE=1, BIAS=2, CLIP=3, INTEGRATOR=4, DIGITAL_FILTER=5)
-F_ACT_DEFAULT_POS_OFFSET, F_ACT_DEFAULT_VEL_OFFSET, F_ACT_CLIP = 1, 2, 4
+# ---- the constants of include/imx.h under their names without the IMX_ prefix (_abi parses the header; nothing is copied here) ------
+def _strip(table: dict, prefix: str) -> dict:
+    return {k[len(prefix):]: v for k, v in table.items() if k.startswith(prefix)}
 
-T_OPS = dict(TIME_OUT=1, ILLEGAL_CONTACT=2, JOINT_POS_MANUAL_LIMIT=3, BAD_ORIENTATION=4, ROOT_HEIGHT_BELOW_MIN=5,
-             JOINT_VEL_LIMIT=6, JOINT_VEL_MANUAL_LIMIT=7, JOINT_EFFORT_LIMIT=8, TERRAIN_OUT_OF_BOUNDS=9, EXTERNAL=10,
-             COMMAND_RESAMPLE=11, OBJECT_REACHED_GOAL=12)
-W_OPS = dict(IS_ALIVE=1, IS_TERMINATED=2, IS_TERMINATED_TERM=3, LIN_VEL_Z_L2=4, ANG_VEL_XY_L2=5, FLAT_ORIENTATION_L2=6,
-             BASE_HEIGHT_L2=7, JOINT_TORQUES_L2=8, JOINT_VEL_L1=9, JOINT_VEL_L2=10, JOINT_ACC_L2=11,
-             JOINT_DEVIATION_L1=12, JOINT_POS_LIMITS=13, JOINT_VEL_LIMITS=14, APPLIED_TORQUE_LIMITS=15,
-             ACTION_RATE_L2=16, ACTION_L2=17, UNDESIRED_CONTACTS=18, CONTACT_FORCES=19, TRACK_LIN_VEL_XY_EXP=20,
-             TRACK_ANG_VEL_Z_EXP=21, FEET_AIR_TIME=22, FEET_AIR_TIME_POSITIVE_BIPED=23, FEET_SLIDE=24,
-             TRACK_LIN_VEL_XY_YAW_FRAME_EXP=25, TRACK_ANG_VEL_Z_WORLD_EXP=26, JOINT_POS_TARGET_L2=27, EXTERNAL=28,
-             BODY_LIN_ACC_L2=29, AIR_TIME_REWARD=30, BASE_ANGULAR_VELOCITY_REWARD=31, BASE_LINEAR_VELOCITY_REWARD=32, GAIT_REWARD=33,
-             FOOT_CLEARANCE_REWARD=34, ACTION_SMOOTHNESS_PENALTY=35, AIR_TIME_VARIANCE_PENALTY=36, BASE_MOTION_PENALTY=37,
-             BASE_ORIENTATION_PENALTY=38, FOOT_SLIP_PENALTY=39, JOINT_ACCELERATION_PENALTY=40, JOINT_POSITION_PENALTY=41,
-             JOINT_TORQUES_PENALTY=42, JOINT_VELOCITY_PENALTY=43, UPRIGHT_POSTURE_BONUS=44, MOVE_TO_TARGET_BONUS=45, PROGRESS_REWARD=46,
-             JOINT_POS_LIMITS_PENALTY_RATIO=47, POWER_CONSUMPTION=48, POSITION_COMMAND_ERROR=49, POSITION_COMMAND_ERROR_TANH=50,
-             ORIENTATION_COMMAND_ERROR=51, OBJECT_IS_LIFTED=52, OBJECT_EE_DISTANCE=53, OBJECT_GOAL_DISTANCE=54)
-O_OPS = dict(BASE_POS_Z=1, BASE_LIN_VEL=2, BASE_ANG_VEL=3, PROJECTED_GRAVITY=4, ROOT_POS_W=5, ROOT_QUAT_W=6,
-             ROOT_LIN_VEL_W=7, ROOT_ANG_VEL_W=8, JOINT_POS=9, JOINT_POS_REL=10, JOINT_POS_LIMIT_NORMALIZED=11,
-             JOINT_VEL=12, JOINT_VEL_REL=13, HEIGHT_SCAN=14, LAST_ACTION=15, GENERATED_COMMANDS=16, EXTERNAL=17,
-             BASE_YAW_ROLL=18, BASE_UP_PROJ=19, BASE_HEADING_PROJ=20, BASE_ANGLE_TO_TARGET=21, BODY_INCOMING_WRENCH=22,
-             OBJECT_POSITION_IN_ROBOT_ROOT_FRAME=23)
-A_JOINT_AFFINE, A_BINARY_JOINT = 1, 2
+
+MAGIC, PLAN_VERSION, HEADER_WORDS, MAX_OBS_GROUPS, REC_WORDS = (
+    _abi.DEFINES["IMX_" + n] for n in ("MAGIC", "PLAN_VERSION", "HEADER_WORDS", "MAX_OBS_GROUPS", "REC_WORDS"))
+H = _strip(_abi.ENUMS["imx_header_word"], "IMX_H_")
+R = _strip(_abi.ENUMS["imx_rec_word"], "IMX_R_")
+M_OPS = _strip(_abi.ENUMS["imx_mod_op"], "IMX_M_")
+T_OPS = _strip(_abi.ENUMS["imx_term_op"], "IMX_T_")
+W_OPS = _strip(_abi.ENUMS["imx_rew_op"], "IMX_W_")
+O_OPS = _strip(_abi.ENUMS["imx_obs_op"], "IMX_O_")
+globals().update(_strip(_abi.ENUMS["imx_act_op"], "IMX_"))  # A_JOINT_AFFINE, A_BINARY_JOINT
+globals().update({k: v for k, v in _strip(_abi.DEFINES, "IMX_").items() if k.startswith("F_")})  # F_NOISE_ADD ... F_ACT_TO_LIMITS: every flag
 
 _MDP = "isaaclab.envs.mdp"
 _VEL = "isaaclab_tasks.manager_based.locomotion.velocity.mdp"
@@ -126,7 +102,6 @@ class Term:
     processed_dim: int = 0
 
 
-IK_MAX_JOINTS = 8  # IMX_IK_MAX_JOINTS (include/imx.h)
 _IK_WIDTH = {("position", False): 3, ("position", True): 3, ("pose", True): 6, ("pose", False): 7}  # DifferentialIKController.action_dim
 
 

@@ -1,5 +1,5 @@
 """CPU: the C-ABI library loads, exports every symbol include/imx.h declares, validates plans on the host, and
-the product package never reaches into oracle/."""
+the product package never reaches into oracle/.  (That the binding equals the header is tests/test_abi.py's.)"""
 
 import ctypes
 import os
@@ -9,63 +9,20 @@ import numpy as np
 import pytest
 
 from _util import KITCHEN, TASKS
-from isaaclab_amd import _lib, plan as planmod
+from isaaclab_amd import _abi, _lib, plan as planmod
 from isaaclab_amd.env import load_task_cfg
 from isaaclab_amd.robots import ROBOTS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "imx.h")).read()
-
-
-def declared_functions():
-    names = re.findall(r"^\s*(?:const\s+)?[A-Za-z_][\w\s\*]*?\b(imx_[a-z0-9_]+)\s*\(", HEADER, flags=re.M)
-    return sorted(set(n for n in names if not n.endswith("_t")))
 
 
 def test_library_exports_every_declared_symbol(libimx):
-    decl = declared_functions()
+    decl = sorted(_abi.FUNCTIONS)
     assert len(decl) >= 20
     for name in decl:
         assert hasattr(libimx, name), f"{name} declared in include/imx.h but not exported by libimx.so"
     assert set(decl) == set(_lib.EXPORTS), set(decl) ^ set(_lib.EXPORTS)
     assert b"gfx950" in libimx.imx_version()
-
-
-def test_header_constants_match_plan_compiler():
-    def define(name):
-        return int(re.search(rf"#define {name}\s+(\S+)", HEADER).group(1), 0)
-
-    assert define("IMX_MAGIC") == planmod.MAGIC
-    assert define("IMX_PLAN_VERSION") == planmod.PLAN_VERSION
-    assert define("IMX_HEADER_WORDS") == planmod.HEADER_WORDS
-    assert define("IMX_REC_WORDS") == planmod.REC_WORDS
-
-    def enum(name):
-        body = re.search(rf"enum {name}\s*\{{(.*?)\}};", HEADER, flags=re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        out, nxt = {}, 0
-        for item in [x.strip() for x in body.split(",") if x.strip()]:
-            if "=" in item:
-                k, v = [s.strip() for s in item.split("=")]
-                nxt = int(v, 0)
-            else:
-                k = item
-            out[k] = nxt
-            nxt += 1
-        return out
-
-    for prefix, table, en in (("IMX_T_", planmod.T_OPS, "imx_term_op"), ("IMX_W_", planmod.W_OPS, "imx_rew_op"),
-                              ("IMX_O_", planmod.O_OPS, "imx_obs_op"), ("IMX_H_", planmod.H, "imx_header_word"),
-                              ("IMX_R_", planmod.R, "imx_rec_word")):
-        e = enum(en)
-        for k, v in table.items():
-            assert e[prefix + k] == v, (prefix + k, e[prefix + k], v)
-    # struct field order
-    for struct, fields in (("imx_state", _lib.STATE_FIELDS), ("imx_buffers", _lib.BUFFER_FIELDS)):
-        body = re.search(rf"typedef struct {struct} \{{(.*?)\}}", HEADER, flags=re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        names = re.findall(r"[\*\s]([a-z_0-9]+)\s*;", body)  # pointer and scalar members
-        assert tuple(names) == tuple(fields), struct
 
 
 @pytest.mark.parametrize("task", TASKS + (KITCHEN,))

@@ -441,7 +441,7 @@ int imx_reset_orchestrate(const imx_orch_t* orch, imx_stream_t stream);
 /* ---- library ---------------------------------------------------------------------------------------------------- */
 const char* imx_version(void);
 /* sizeof of an ABI struct as this library was compiled (which: 0 imx_state_t, 1 imx_buffers_t, 2 imx_head_loss_t, 3 imx_rollout_slot_t, 4 imx_policy_act_t, 5 imx_orch_t, 6 imx_event_term_t,
- * 7 imx_diff_ik_t), 0 for an unknown index:
+ * 7 imx_diff_ik_t, 8 imx_osc_t), 0 for an unknown index:
  * a binding checks its own layout against it at load time. */
 size_t imx_struct_size(int which);
 const char* imx_last_error(void);
@@ -933,6 +933,48 @@ int imx_diff_ik(const imx_diff_ik_t* cfg, int64_t N, int mode, const float* proc
                 const float* root_pos_w_d, const float* root_quat_w_d, const float* body_pos_w_d, const float* body_quat_w_d,
                 int64_t num_bodies, const float* jacobians_d, int64_t NB, int64_t ND, const float* joint_pos_d, int64_t J,
                 float* ee_pos_des_d, float* ee_quat_des_d, float* joint_pos_des_d, int64_t ld_des, imx_stream_t stream);
+
+/* ---- OperationalSpaceControllerAction --------------------------------------------------------------------------
+ * Parameters of one term (envs/mdp/actions/task_space_actions.py:248-378 __init__, :504-537 _resolve_command_indexes, :539-566
+ * _resolve_nullspace_joint_pos_targets; controllers/operational_space.py:34-140 __init__, :146-160 action_dim and the defaults of
+ * operational_space_cfg.py), resolved by isaaclab_amd/plan.py (plan.osc_terms).  Kept out of the plan blob and of imx_state_t /
+ * imx_buffers_t / imx_orch_t.  Only the identity task frame is built (task_frame_rel_path is refused by the term compiler), so the
+ * task-frame gains, selection matrices and targets are the root-frame ones. */
+#define IMX_OSC_CMD_WIDTH 25
+enum imx_osc_pose { IMX_OSC_POSE_ABS = 0, IMX_OSC_POSE_REL = 1 };
+enum imx_osc_impedance { IMX_OSC_FIXED = 0, IMX_OSC_VARIABLE_KP = 1, IMX_OSC_VARIABLE = 2 };
+enum imx_osc_decoupling { IMX_OSC_DECOUPLING_NONE = 0, IMX_OSC_DECOUPLING_FULL = 1, IMX_OSC_DECOUPLING_PARTIAL = 2 };
+/* The struct itself is in imx_osc_struct.h, which this header includes: imx.h declares the type and the entry point. */
+typedef struct imx_osc imx_osc_t;
+#include "imx_osc_struct.h"
+
+/* OperationalSpaceControllerAction.process_actions / apply_actions (envs/mdp/actions/task_space_actions.py:416-438, :440-462; reset
+ * :464-474 zeroes raw actions only and is the env's) with OperationalSpaceController.set_command / compute
+ * (controllers/operational_space.py:173-343, :345-548), one lane per env, one launch.  The raw -> processed half (_preprocess_actions
+ * :664-700) is an ordinary action record of the plan.
+ * mode bit 1: the command half of process_actions -- the end-effector pose in the root frame (_compute_ee_pose :597-615), the term's
+ *   processed columns split into target, stiffness and damping ratio and clamped as set_command does, Kp = S_motion diag(stiffness),
+ *   Kd = 2 sqrt(Kp) ratio, the desired pose (apply_delta_pose for pose_rel, the seven values as they are for pose_abs: not normalised),
+ *   the desired wrench.  Written to the env's row of command_state_d: pose 7, Kp 6, Kd 6, wrench 6 (IMX_OSC_CMD_WIDTH).
+ * mode bit 2: apply_actions -- jacobian_b (:403-410) with the offset correction (_compute_ee_jacobian :576-595), the pose and the velocity
+ *   relative to the root (_compute_ee_velocity :617-634), _compute_dynamic_quantities (:568-574: mass matrix and gravity indexed by
+ *   joint_ids), _compute_joint_states (:645-649), the axis-angle pose error, a = Kp e - Kd v, Lambda = (J M^-1 J^T)^-1 (whole, two 3 x 3
+ *   blocks, or none), tau = J^T S_m Lambda a + J^T S_f F + g + (I - J^T Lambda J M^-1) M (kp_n (q* - q) - kd_n qd).  M and J M^-1 J^T
+ *   are factored by an unrolled Cholesky and solved, no inverse is formed; only the lower triangle of M is read; the null-space term is
+ *   M qdd - J^T Lambda (J qdd).  mode 3 does both.
+ * processed_action_d (N, PA); root_pos_w_d (N,3), root_quat_w_d (N,4), root_lin_vel_w_d / root_ang_vel_w_d (N,3); body_pos_w_d,
+ * body_lin_vel_w_d, body_ang_vel_w_d (N, num_bodies, 3), body_quat_w_d (N, num_bodies, 4); jacobians_d (N, NB, 6, ND), mass_matrices_d
+ * (N, NM, NM), gravity_d (N, NM) as root_physx_view hands them out; joint_pos_d, joint_vel_d (N, J); nullspace_target_d (N, num_joints);
+ * command_state_d (N, ld_cmd); joint_efforts_d (N, ld_eff) with the term's num_joints columns first.
+ * Refused without a launch: a null pointer the mode and cfg need, num_joints outside [1, 8], a body, joint, row or column index out of
+ * range, processed columns past PA, ld_cmd < 25, ld_eff < num_joints, null-space control without full decoupling or on six joints or
+ * fewer, an unknown pose type / impedance mode / decoupling / mode. */
+int imx_osc(const imx_osc_t* cfg, int64_t N, int mode, const float* processed_action_d, int64_t PA,
+            const float* root_pos_w_d, const float* root_quat_w_d, const float* root_lin_vel_w_d, const float* root_ang_vel_w_d,
+            const float* body_pos_w_d, const float* body_quat_w_d, const float* body_lin_vel_w_d, const float* body_ang_vel_w_d,
+            int64_t num_bodies, const float* jacobians_d, int64_t NB, int64_t ND, const float* mass_matrices_d, const float* gravity_d,
+            int64_t NM, const float* joint_pos_d, const float* joint_vel_d, int64_t J, const float* nullspace_target_d,
+            float* command_state_d, int64_t ld_cmd, float* joint_efforts_d, int64_t ld_eff, imx_stream_t stream);
 
 #ifdef __cplusplus
 }

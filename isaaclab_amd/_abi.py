@@ -46,9 +46,10 @@ def ctype(t: CType, classes: dict, ret: bool = False):
     return c * t.dim if t.dim else c
 
 
-def parse(text: str, path: str = "imx.h"):
-    """``(DEFINES, ENUMS, STRUCTS, FUNCTIONS)`` of a header text."""
-    defines, enums, structs, functions, opaque, handles = {}, {}, {}, {}, set(), set()
+def parse(text: str, path: str = "imx.h", known_defines: dict | None = None):
+    """``(DEFINES, ENUMS, STRUCTS, FUNCTIONS)`` of a header text.  ``known_defines``: the ``#define IMX_*`` of the header that includes
+    this one (array sizes may use them); they are not returned."""
+    defines, enums, structs, functions, opaque, handles = dict(known_defines or {}), {}, {}, {}, set(), set()
 
     def fail(pos: int, msg: str):
         raise AbiError(f"{path}:{code.count(chr(10), 0, pos) + 1}: {msg}")
@@ -144,11 +145,15 @@ def parse(text: str, path: str = "imx.h"):
             functions[m.group(2)] = (decl(pos, m.group(1).strip(), named=False)[1], [t for _, t in params], [n for n, _ in params])
         else:
             fail(pos, f"'{s.split(chr(10))[0]}' is no declaration of the subset read here")
-    return defines, enums, structs, functions
+    return {k: v for k, v in defines.items() if k not in (known_defines or {})}, enums, structs, functions
 
 
 try:
     with open(HEADER) as _f:
         DEFINES, ENUMS, STRUCTS, FUNCTIONS = parse(_f.read(), HEADER)
+    # imx_osc_struct.h, which imx.h includes for the one struct it declares but does not define (imx_osc_t)
+    OSC_HEADER = os.path.join(os.path.dirname(HEADER), "imx_osc_struct.h")
+    with open(OSC_HEADER) as _f:
+        _, _, OSC_STRUCTS, _ = parse(_f.read(), OSC_HEADER, DEFINES)
 except OSError as e:
     raise AbiError(f"the ABI header {HEADER} cannot be read ({e}): the whole binding is derived from it") from e

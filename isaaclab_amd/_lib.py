@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libimx.so")
 
 ORCH_MAX_TERMS = _abi.DEFINES["IMX_ORCH_MAX_TERMS"]
 IK_MAX_JOINTS = _abi.DEFINES["IMX_IK_MAX_JOINTS"]
+OSC_CMD_WIDTH = _abi.DEFINES["IMX_OSC_CMD_WIDTH"]
 _STRUCTS = {}  # typedef name -> class
 
 
@@ -42,6 +43,34 @@ class ImxDiffIk(ctypes.Structure):  # imx_diff_ik_t
                    jacobi_joint_ids=(c_int32 * IK_MAX_JOINTS)(*ik.jacobi_joint_ids), processed_col=ik.processed_col)
 
 
+class ImxOsc(ctypes.Structure):  # imx_osc_t
+    @classmethod
+    def from_term(cls, t) -> "ImxOsc":
+        """The C struct of a ``plan.OscTerm``."""
+        import math
+
+        n = len(t.joint_ids)
+        if not 1 <= n <= IK_MAX_JOINTS:
+            raise ImxError(f"action term '{t.name}': {n} controlled joints (1..{IK_MAX_JOINTS})")
+        E = _abi.ENUMS
+        pos, rot = t.offset_pos or (0.0, 0.0, 0.0), t.offset_rot or (1.0, 0.0, 0.0, 0.0)
+        col = lambda i: -1 if i is None else t.processed_col + i  # noqa: E731
+        f6 = lambda v: (c_float * 6)(*v)  # noqa: E731
+        kp = c_float(t.nullspace_stiffness).value  # torch.tensor(nullspace_stiffness): fp32 before the square root (:135-140)
+        kd = c_float(c_float(2.0 * c_float(math.sqrt(kp)).value).value * c_float(t.nullspace_damping_ratio).value).value
+        return cls(pose_type=E["imx_osc_pose"]["IMX_OSC_" + t.pose_type.upper()], has_wrench=int(t.wrench_idx is not None),
+                   impedance_mode=E["imx_osc_impedance"]["IMX_OSC_" + t.impedance_mode.upper()],
+                   decoupling=E["imx_osc_decoupling"]["IMX_OSC_DECOUPLING_" + t.decoupling.upper()],
+                   gravity_compensation=int(t.gravity_compensation), nullspace_position=int(t.nullspace_control == "position"),
+                   has_offset=int(t.offset_pos is not None), pose_col=col(t.pose_idx), wrench_col=col(t.wrench_idx),
+                   stiffness_col=col(t.stiffness_idx), damping_ratio_col=col(t.damping_ratio_idx), motion_axes=f6(t.motion_control_axes),
+                   wrench_axes=f6(t.contact_wrench_control_axes), motion_stiffness=f6(t.motion_stiffness),
+                   motion_damping_ratio=f6(t.motion_damping_ratio), stiffness_limits=(c_float * 2)(*t.motion_stiffness_limits),
+                   damping_ratio_limits=(c_float * 2)(*t.motion_damping_ratio_limits), nullspace_kp=kp, nullspace_kd=kd,
+                   offset_pos=(c_float * 3)(*pos), offset_rot=(c_float * 4)(*rot), body_idx=t.body_idx, jacobi_body_idx=t.jacobi_body_idx,
+                   num_joints=n, joint_ids=(c_int32 * IK_MAX_JOINTS)(*t.joint_ids), jacobi_joint_ids=(c_int32 * IK_MAX_JOINTS)(*t.jacobi_joint_ids))
+
+
 ImxState = _struct("imx_state_t")
 ImxBuffers = _struct("imx_buffers_t")
 ImxRolloutSlot = _struct("imx_rollout_slot_t")
@@ -50,6 +79,7 @@ ImxOrch = _struct("imx_orch_t")
 ImxPolicyAct = _struct("imx_policy_act_t")
 ImxHeadLoss = _struct("imx_head_loss_t")
 _struct("imx_diff_ik_t", ImxDiffIk)
+ImxOsc._fields_ = [(field, _abi.ctype(t, _STRUCTS)) for field, t in _abi.OSC_STRUCTS["imx_osc_t"]]  # (imx_osc_struct.h: imx.h only declares the type)
 if set(_STRUCTS) != set(_abi.STRUCTS):
     raise _abi.AbiError(f"{_abi.HEADER}: no class for {sorted(set(_abi.STRUCTS) - set(_STRUCTS))}")
 STATE_FIELDS = tuple(field for field, _ in ImxState._fields_)
@@ -88,7 +118,7 @@ def lib():
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
-    for which, cls in enumerate((ImxState, ImxBuffers, ImxHeadLoss, ImxRolloutSlot, ImxPolicyAct, ImxOrch, ImxEventTerm, ImxDiffIk)):  # the binding's struct layouts against the library's
+    for which, cls in enumerate((ImxState, ImxBuffers, ImxHeadLoss, ImxRolloutSlot, ImxPolicyAct, ImxOrch, ImxEventTerm, ImxDiffIk, ImxOsc)):  # the binding's struct layouts against the library's
         if int(L.imx_struct_size(which)) != ctypes.sizeof(cls):
             raise ImxError(f"{LIB_PATH}: sizeof({cls.__name__}) is {int(L.imx_struct_size(which))} in the library, {ctypes.sizeof(cls)} in the "
                            "binding -- rebuild with `python -m isaaclab_amd.build`")

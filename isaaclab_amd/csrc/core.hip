@@ -32,6 +32,7 @@ extern "C" size_t imx_struct_size(int which) {
         case 5: return sizeof(imx_orch_t);
         case 6: return sizeof(imx_event_term_t);
         case 7: return sizeof(imx_diff_ik_t);
+        case 8: return sizeof(imx_osc_t);
         default: return 0;
     }
 }

@@ -198,6 +198,23 @@ class _IkActionTermView(_ActionTermView):
         return self._env._joint_pos_des
 
 
+class _OscActionTermView(_ActionTermView):
+    """The OperationalSpaceControllerAction term: the controller's command state and the joint efforts ``apply_action`` leaves."""
+
+    @property
+    def command_state(self):
+        """(N, 25): desired pose 7 (root frame), Kp 6, Kd 6, desired wrench 6."""
+        return self._env._osc_cmd
+
+    @property
+    def desired_ee_pose_b(self):
+        return self._env._osc_cmd[:, 0:7]
+
+    @property
+    def joint_efforts(self):
+        return self._env._joint_efforts
+
+
 class ActionManager:
     """View with the public surface of isaaclab/managers/action_manager.py:228-359."""
 
@@ -206,8 +223,9 @@ class ActionManager:
         self._terms = {}
         c = 0
         ik_names = {ik.name for ik in env.plan.ik_terms}
+        osc_names = {o.name for o in env.plan.osc_terms}
         for t in env.plan.action_terms:
-            view = _IkActionTermView if t.name in ik_names else _ActionTermView
+            view = _IkActionTermView if t.name in ik_names else _OscActionTermView if t.name in osc_names else _ActionTermView
             self._terms[t.name] = view(env, t.name, c, t.dim, t.processed_col, t.processed_dim)
             c += t.dim
 
@@ -242,6 +260,8 @@ class ActionManager:
         168-179); for every other term the processed targets would go to PhysX and nothing is left to compute."""
         if self._env._ik is not None:
             self._env._diff_ik(2)
+        if self._env._osc is not None:  # ... and an OperationalSpaceControllerAction its joint efforts (:440-462)
+            self._env._osc_launch(2)
 
     def reset(self, env_ids=None) -> dict:
         ids = slice(None) if env_ids is None else env_ids
@@ -250,7 +270,8 @@ class ActionManager:
         # EMAJointPositionToLimitsAction.reset (joint_actions_to_limits.py:208-217): the moving average restarts from the joint positions
         # (inside env.step() the action kernel does this itself for the envs the step kernel reset).  A binary joint term zeroes its raw
         # action only (binary_joint_actions.py:135), and so does a DifferentialInverseKinematicsAction (task_space_actions.py:181-182: the
-        # desired pose survives until the next process_action): done above
+        # desired pose survives until the next process_action) and an OperationalSpaceControllerAction (:464-474: the controller's
+        # command is never reset): done above
         for t in self._env.plan.action_terms:
             if t.func.rsplit(":", 1)[-1].rsplit(".", 1)[-1] == "EMAJointPositionToLimitsAction":
                 from .robots import resolve_matching_names
@@ -679,6 +700,21 @@ class ManagerBasedRLEnv:
             self._ik_cfg = _lib.ImxDiffIk.from_term(self._ik)
             self._ee_pos_des, self._ee_quat_des, self._joint_pos_des = z(N, 3), z(N, 4), z(N, len(self._ik.joint_ids))
             self.feed.ensure_jacobians()
+        # an OperationalSpaceControllerAction's command state and output (imx_osc); Jacobians, mass matrices, gravity from the feed
+        self._osc = plan.osc_terms[0] if plan.osc_terms else None
+        if self._osc is not None:
+            o = self._osc
+            self._osc_cfg = _lib.ImxOsc.from_term(o)
+            self._osc_cmd, self._joint_efforts = z(N, _lib.OSC_CMD_WIDTH), z(N, len(o.joint_ids))
+            self.feed.ensure_jacobians()
+            self.feed.ensure_dynamics()
+            # _resolve_nullspace_joint_pos_targets (task_space_actions.py:539-566), once
+            if o.nullspace_joint_pos_target == "center":
+                self._osc_target = torch.mean(self.feed["soft_joint_pos_limits"][:, o.joint_ids, :], dim=-1).contiguous()
+            elif o.nullspace_joint_pos_target == "default":
+                self._osc_target = self.feed["default_joint_pos"][:, o.joint_ids].contiguous()
+            else:
+                self._osc_target = z(N, len(o.joint_ids))
         self._reward_buf = z(N)
         self._episode_sums = z(K, N)
         self._step_reward = z(N, K)
@@ -1055,6 +1091,25 @@ class ManagerBasedRLEnv:
                                            ctypes.byref(self._bufs), _lib.current_stream(self.device)))
         if self._ik is not None:  # the command half of DifferentialInverseKinematicsAction.process_actions
             self._diff_ik(1)
+        if self._osc is not None:  # the command half of OperationalSpaceControllerAction.process_actions
+            self._osc_launch(1)
+
+    def _osc_launch(self, mode: int):
+        """``imx_osc`` on the current state: mode 1 = the command state from the processed action, 2 = apply_actions, 3 = both.  Pointers
+        are taken per call, as in ``_diff_ik`` (a captured rollout records one launch per substep with its snapshot's pointers).  No host
+        sync."""
+        f = self.feed
+        ar = self.articulation
+        root_pos, root_quat = (ar.root_pos_w, ar.root_quat_w) if ar is not None else (f["root_pos_w"], f["root_quat_w"])
+        root_lin, root_ang = (ar.root_lin_vel_w, ar.root_ang_vel_w) if ar is not None else (f["root_lin_vel_w"], f["root_ang_vel_w"])
+        jac, bp, m, jp = f["jacobians"], f["body_pos_w"], f["mass_matrices"], f["joint_pos"]
+        check(self._lib.imx_osc(ctypes.byref(self._osc_cfg), self.num_envs, mode, self._processed_action.data_ptr(),
+                                self._processed_action.shape[1], root_pos.data_ptr(), root_quat.data_ptr(), root_lin.data_ptr(),
+                                root_ang.data_ptr(), bp.data_ptr(), f["body_quat_w"].data_ptr(), f["body_lin_vel_w"].data_ptr(),
+                                f["body_ang_vel_w"].data_ptr(), bp.shape[1], jac.data_ptr(), jac.shape[1], jac.shape[3], m.data_ptr(),
+                                f["gravity_compensation_forces"].data_ptr(), m.shape[1], jp.data_ptr(), f["joint_vel"].data_ptr(), jp.shape[1],
+                                self._osc_target.data_ptr(), self._osc_cmd.data_ptr(), self._osc_cmd.shape[1],
+                                self._joint_efforts.data_ptr(), self._joint_efforts.shape[1], _lib.current_stream(self.device)))
 
     def _diff_ik(self, mode: int):
         """``imx_diff_ik`` on the current state: mode 1 = the desired pose from the processed action, 2 = apply_actions, 3 = both.  The
@@ -1117,6 +1172,10 @@ class ManagerBasedRLEnv:
             raise ValueError(f"attach_actuator: the processed action of '{self._ik.name}' (DifferentialInverseKinematicsAction) is a task-space "
                              "command, not a row of joint targets; the term's targets are joint_pos_des "
                              f"(action_manager.get_term('{self._ik.name}').joint_pos_des), for its {len(self._ik.joint_ids)} joints only")
+        if self._osc is not None:
+            raise ValueError(f"attach_actuator: the processed action of '{self._osc.name}' (OperationalSpaceControllerAction) is a task-space "
+                             "command, not a row of joint targets; the term's output is joint_efforts "
+                             f"(action_manager.get_term('{self._osc.name}').joint_efforts), for its {len(self._osc.joint_ids)} joints only")
         if self.plan.processed_action_dim != self.plan.num_joints:
             raise ValueError(f"attach_actuator: the action terms write {self.plan.processed_action_dim} joint targets, the robot has "
                              f"{self.plan.num_joints} joints")
@@ -1278,6 +1337,9 @@ class ManagerBasedRLEnv:
             # substep.  Entered from the fused rollout the actor head has only processed the action: the first launch also sets the command
             for k in range(int(self.cfg_decimation)):
                 self._diff_ik(3 if (k == 0 and rollout_slot is not None) else 2)
+        if self._osc is not None:  # the OSC term's joint efforts, likewise once per physics substep
+            for k in range(int(self.cfg_decimation)):
+                self._osc_launch(3 if (k == 0 and rollout_slot is not None) else 2)
         self._sim_step_counter += int(self.cfg_decimation)
         self.feed.advance()
         if self.articulation is not None:

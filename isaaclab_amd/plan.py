@@ -192,6 +192,162 @@ def resolve_ik_term(name: str, tcfg: dict, robot: RobotSpec, action_col: int = 0
                   jacobi_joint_ids=[int(i) for i in jcols], action_col=action_col, processed_col=processed_col, width=width, scale=scale, clip=clip)
 
 
+_OSC_TARGET_WIDTH = {"pose_abs": 7, "pose_rel": 6, "wrench_abs": 6}  # OperationalSpaceController.__init__ (operational_space.py:50-61)
+
+
+@dataclasses.dataclass
+class OscTerm:
+    """One ``OperationalSpaceControllerAction`` as resolved by its ``__init__`` (task_space_actions.py:248-378) and its controller's
+    (operational_space.py:34-140): the parameters of ``imx_osc_t``.  They travel beside the plan, not in its blob."""
+
+    name: str
+    target_types: list  # "pose_abs" | "pose_rel", then optionally "wrench_abs" (in cfg order)
+    impedance_mode: str  # "fixed" | "variable_kp" | "variable"
+    decoupling: str  # "none" | "full" | "partial"
+    gravity_compensation: bool
+    nullspace_control: str  # "none" | "position"
+    nullspace_joint_pos_target: str  # "none" | "zero" | "center" | "default"
+    nullspace_stiffness: float
+    nullspace_damping_ratio: float
+    motion_control_axes: list  # 6
+    contact_wrench_control_axes: list  # 6
+    motion_stiffness: list  # 6
+    motion_damping_ratio: list  # 6
+    motion_stiffness_limits: tuple
+    motion_damping_ratio_limits: tuple
+    offset_pos: tuple | None  # cfg.body_offset, or None
+    offset_rot: tuple | None
+    body_name: str
+    body_idx: int
+    jacobi_body_idx: int
+    joint_ids: list  # columns of joint_pos / joint_vel, rows and columns of the mass matrix (:571-574)
+    jacobi_joint_ids: list
+    action_col: int  # first raw column
+    processed_col: int  # first processed column
+    width: int  # action_dim: raw = processed columns
+    pose_idx: int  # first column of each part inside the term (_resolve_command_indexes :504-537); None = absent
+    wrench_idx: int | None
+    stiffness_idx: int | None
+    damping_ratio_idx: int | None
+    scale: list  # per column (_preprocess_actions :664-700)
+    clip: list  # per column (lo, hi); +-inf on the columns the reference does not clamp
+
+    @property
+    def pose_type(self) -> str:
+        return "pose_rel" if "pose_rel" in self.target_types else "pose_abs"
+
+
+def _six(name: str, key: str, v, scalar_ok: bool = True) -> list:
+    if isinstance(v, (int, float)) and scalar_ok:
+        return [float(v)] * 6
+    v = [float(x) for x in v]
+    if len(v) != 6:
+        raise ValueError(f"action term '{name}': {key} has {len(v)} entries, not 6")
+    return v
+
+
+def resolve_osc_term(name: str, tcfg: dict, robot: RobotSpec, action_col: int = 0, processed_col: int = 0, joint_names=None) -> OscTerm:
+    """``OperationalSpaceControllerAction.__init__`` (task_space_actions.py:248-378), ``_resolve_command_indexes`` (:504-537),
+    ``_resolve_nullspace_joint_pos_targets`` (:539-566) and ``OperationalSpaceController.__init__`` / ``action_dim``
+    (operational_space.py:34-160) with the defaults of operational_space_cfg.py, over a robot's name tables."""
+    ctrl = tcfg.get("controller_cfg")
+    missing = [k for k in ("joint_names", "body_name", "controller_cfg") if tcfg.get(k) is None]
+    missing += [f"controller_cfg.{k}" for k in ("target_types",) if isinstance(ctrl, dict) and ctrl.get(k) is None]
+    if missing or not isinstance(ctrl, dict):  # (MISSING fields of the configclass: the reference stops at cfg validation)
+        raise NotImplementedError(f"action term '{name}': an OperationalSpaceControllerAction cfg without {missing or ['a controller_cfg dict']} "
+                                  "is not on the fused path")
+    targets = list(ctrl["target_types"])
+    for t in targets:
+        if t not in _OSC_TARGET_WIDTH:
+            raise ValueError(f"Invalid control command: {t}.")
+    mode = ctrl.get("impedance_mode", "fixed")
+    if mode not in ("fixed", "variable_kp", "variable"):
+        raise ValueError(f"Invalid impedance mode: {mode}.")
+    null_ctrl, null_target = ctrl.get("nullspace_control", "none"), tcfg.get("nullspace_joint_pos_target", "none")
+    if null_target != "none" and null_ctrl != "position":
+        raise ValueError("Nullspace joint targets can only be set when null space control is set to 'position'.")
+    if null_target == "none" and null_ctrl == "position":
+        raise ValueError("Nullspace joint targets must be set when null space control is set to 'position'.")
+    if null_target not in ("none", "zero", "center", "default"):
+        raise ValueError("Invalid value for nullspace joint pos targets.")
+    if null_ctrl not in ("none", "position"):
+        raise ValueError(f"Invalid null-space control method: {null_ctrl}.")
+    joint_ids, _ = resolve_matching_names(tcfg["joint_names"], list(joint_names if joint_names is not None else robot.joint_names))
+    body_ids, body_names = resolve_matching_names(tcfg["body_name"], list(robot.body_names))
+    if len(body_ids) != 1:
+        raise ValueError(f"Expected one match for the ee body name: {tcfg['body_name']}. Found {len(body_ids)}: {body_names}.")
+    n = len(joint_ids)
+    if null_ctrl != "none" and n <= 6:  # (operational_space.py:491-493, raised by the first compute())
+        raise ValueError("Null-space control is only applicable for redundant manipulators.")
+    # ---- what the fused path does not build
+    if tcfg.get("task_frame_rel_path") is not None:
+        raise NotImplementedError(f"action term '{name}': task_frame_rel_path '{tcfg['task_frame_rel_path']}' needs a FrameTransformer on a "
+                                  "rigid body of the scene; only the identity task frame (the root frame) is on the fused path")
+    if "wrench_abs" in targets and ctrl.get("contact_wrench_stiffness_task") is not None:
+        raise NotImplementedError(f"action term '{name}': closed-loop wrench control (contact_wrench_stiffness_task set) needs a contact sensor "
+                                  "on the end effector; only the open-loop wrench is on the fused path")
+    if sum(t.startswith("pose") for t in targets) > 1 or targets.count("wrench_abs") > 1:
+        raise NotImplementedError(f"action term '{name}': target_types {targets} holds two motion targets or two wrench targets; the fused "
+                                  "path takes one of each")
+    if not any(t.startswith("pose") for t in targets):
+        raise NotImplementedError(f"action term '{name}': target_types {targets} holds no motion target; the fused path takes 'pose_abs' or "
+                                  "'pose_rel', alone or with 'wrench_abs'")
+    decoupled, partial = bool(ctrl.get("inertial_dynamics_decoupling", False)), bool(ctrl.get("partial_inertial_dynamics_decoupling", False))
+    decoupling = "none" if not decoupled else ("partial" if partial else "full")
+    if null_ctrl == "position" and decoupling != "full":
+        raise NotImplementedError(f"action term '{name}': nullspace_control 'position' without full inertial decoupling takes torch.pinverse of "
+                                  "the Jacobian, an SVD inside the kernel (as ik_method 'pinv'); it is on the fused path with "
+                                  "inertial_dynamics_decoupling=True, partial_inertial_dynamics_decoupling=False only")
+    if n > IK_MAX_JOINTS:
+        raise NotImplementedError(f"action term '{name}': {n} controlled joints; the operational-space kernel takes at most {IK_MAX_JOINTS}")
+    body_idx = body_ids[0]
+    if robot.fixed_base:  # the Jacobian of a fixed base has no row for the root body and no root columns (:266-274)
+        jb, jcols = body_idx - 1, list(joint_ids)
+        if jb < 0:
+            raise ValueError(f"action term '{name}': body '{body_names[0]}' is the root of a fixed-base articulation: it has no Jacobian row")
+    else:
+        jb, jcols = body_idx, [i + 6 for i in joint_ids]
+    # ---- _resolve_command_indexes and _preprocess_actions: per-column scale and clamp
+    idx = {"pose": None, "wrench_abs": None, "stiffness": None, "damping_ratio": None}
+    scale, clip, col = [], [], 0
+    inf = (-math.inf, math.inf)
+    ps, os_, ws = float(tcfg.get("position_scale", 1.0)), float(tcfg.get("orientation_scale", 1.0)), float(tcfg.get("wrench_scale", 1.0))
+    for t in targets:
+        w = _OSC_TARGET_WIDTH[t]
+        idx["pose" if t.startswith("pose") else t] = col
+        scale += [ws] * 6 if t == "wrench_abs" else [ps] * 3 + [os_] * (w - 3)
+        clip += [inf] * w
+        col += w
+    k_lim = tuple(float(v) for v in ctrl.get("motion_stiffness_limits_task", (0, 1000)))
+    d_lim = tuple(float(v) for v in ctrl.get("motion_damping_ratio_limits_task", (0, 100)))
+    if mode in ("variable_kp", "variable"):
+        idx["stiffness"] = col
+        scale += [float(tcfg.get("stiffness_scale", 1.0))] * 6
+        clip += [k_lim] * 6
+        col += 6
+        if mode == "variable":
+            idx["damping_ratio"] = col
+            scale += [float(tcfg.get("damping_ratio_scale", 1.0))] * 6
+            clip += [d_lim] * 6
+            col += 6
+    off = tcfg.get("body_offset")
+    return OscTerm(name=name, target_types=targets, impedance_mode=mode, decoupling=decoupling,
+                   gravity_compensation=bool(ctrl.get("gravity_compensation", False)), nullspace_control=null_ctrl,
+                   nullspace_joint_pos_target=null_target, nullspace_stiffness=float(ctrl.get("nullspace_stiffness", 10.0)),
+                   nullspace_damping_ratio=float(ctrl.get("nullspace_damping_ratio", 1.0)),
+                   motion_control_axes=_six(name, "motion_control_axes_task", ctrl.get("motion_control_axes_task", (1,) * 6), False),
+                   contact_wrench_control_axes=_six(name, "contact_wrench_control_axes_task", ctrl.get("contact_wrench_control_axes_task", (0,) * 6), False),
+                   motion_stiffness=_six(name, "motion_stiffness_task", ctrl.get("motion_stiffness_task", 100.0)),
+                   motion_damping_ratio=_six(name, "motion_damping_ratio_task", ctrl.get("motion_damping_ratio_task", 1.0)),
+                   motion_stiffness_limits=k_lim, motion_damping_ratio_limits=d_lim,
+                   offset_pos=None if off is None else tuple(float(v) for v in off.get("pos", (0.0, 0.0, 0.0))),
+                   offset_rot=None if off is None else tuple(float(v) for v in off.get("rot", (1.0, 0.0, 0.0, 0.0))),
+                   body_name=body_names[0], body_idx=int(body_idx), jacobi_body_idx=int(jb), joint_ids=[int(i) for i in joint_ids],
+                   jacobi_joint_ids=[int(i) for i in jcols], action_col=action_col, processed_col=processed_col, width=col,
+                   pose_idx=idx["pose"], wrench_idx=idx["wrench_abs"], stiffness_idx=idx["stiffness"], damping_ratio_idx=idx["damping_ratio"],
+                   scale=scale, clip=clip)
+
+
 @dataclasses.dataclass
 class Plan:
     blob: np.ndarray  # int32 words
@@ -229,6 +385,7 @@ class Plan:
     term_slots: int = 0  # rows of per-env reward-term state (imx_buffers.term_state): one per progress_reward term
     processed_action_dim: int = 0  # width of the processed action (= action_dim unless a term writes more joints than it takes columns)
     ik_terms: list = dataclasses.field(default_factory=list)  # IkTerm of the env's DifferentialInverseKinematicsAction (at most one)
+    osc_terms: list = dataclasses.field(default_factory=list)  # OscTerm of the env's OperationalSpaceControllerAction (at most one, and no IkTerm beside it)
 
 
 @dataclasses.dataclass
@@ -707,6 +864,7 @@ _JOINT_ACTIONS = ("JointPositionAction", "JointVelocityAction", "JointEffortActi
                   "JointPositionToLimitsAction", "EMAJointPositionToLimitsAction")
 _BINARY_ACTIONS = ("BinaryJointPositionAction", "BinaryJointVelocityAction")
 _IK_ACTION = "isaaclab.envs.mdp.actions.task_space_actions:DifferentialInverseKinematicsAction"
+_OSC_ACTION = "isaaclab.envs.mdp.actions.task_space_actions:OperationalSpaceControllerAction"
 _NOISE_OPS = {"add": F_NOISE_ADD, "scale": F_NOISE_SCALE, "abs": F_NOISE_ABS}
 # noise function -> the scalar parameters in NOISE_LO / NOISE_HI, flag.  constant_noise: u * (b - b) + b == b for every u: the uniform
 # path, bit-identical
@@ -773,6 +931,7 @@ class PlanCompiler:
         self.action_dim = 0
         self.processed_dim = 0  # columns of the processed action so far (a binary term writes more joints than it takes columns)
         self.ik_terms: list[IkTerm] = []
+        self.osc_terms: list[OscTerm] = []
         for name, tcfg in (self.cfg.get("actions") or {}).items():
             if tcfg is None or not isinstance(tcfg, dict) or "class_type" not in tcfg:
                 continue
@@ -783,6 +942,9 @@ class PlanCompiler:
                 continue
             if cls == _IK_ACTION:
                 self._ik_action(name, cls, tcfg)
+                continue
+            if cls == _OSC_ACTION:
+                self._osc_action(name, cls, tcfg)
                 continue
             if cname not in _JOINT_ACTIONS:
                 raise NotImplementedError(f"action term '{name}': class {cls} is not on the fused path")
@@ -855,6 +1017,9 @@ class PlanCompiler:
         clip, which the A_JOINT_AFFINE record already does (offset 0, no flag but the clip's); the controller's parameters go to
         ``ik_terms``.  The record's id list only has to pass the blob validation: without the default-offset, to-limits or EMA flag
         ``action_process_element`` loads the id and never indexes a joint array with it, so it is joint 0 for every column."""
+        if self.osc_terms:
+            raise NotImplementedError(f"action term '{name}': a DifferentialInverseKinematicsAction beside the OperationalSpaceControllerAction "
+                                      f"'{self.osc_terms[0].name}'; the fused path runs one task-space term per env")
         if self.ik_terms:
             raise NotImplementedError(f"action term '{name}': a second DifferentialInverseKinematicsAction (after '{self.ik_terms[0].name}'); "
                                       "the fused path runs one per env")
@@ -877,6 +1042,39 @@ class PlanCompiler:
         self.act_recs.append(_rec(**rec))
         self.action_terms.append(Term(name, cls, A_JOINT_AFFINE, dict(tcfg), dim=dim, processed_col=self.processed_dim, processed_dim=dim))
         self.ik_terms.append(ik)
+        self.action_dim += dim
+        self.processed_dim += dim
+
+    def _osc_action(self, name: str, cls: str, tcfg: dict) -> None:
+        """``OperationalSpaceControllerAction`` (task_space_actions.py:248-378, 664-700): raw -> processed is a per-column scale and a
+        clamp on the stiffness and damping-ratio columns, which the A_JOINT_AFFINE record already does with a scale table and a clip
+        table (offset 0, +-inf on the unclamped columns); the controller's parameters go to ``osc_terms``.  The record's id list is
+        joint 0 for every column, as for the differential-IK term."""
+        if self.osc_terms:
+            raise NotImplementedError(f"action term '{name}': a second OperationalSpaceControllerAction (after '{self.osc_terms[0].name}'); "
+                                      "the fused path runs one per env")
+        if self.ik_terms:
+            raise NotImplementedError(f"action term '{name}': an OperationalSpaceControllerAction beside the DifferentialInverseKinematicsAction "
+                                      f"'{self.ik_terms[0].name}'; the fused path runs one task-space term per env")
+        blob = self.blob
+        osc = resolve_osc_term(name, tcfg, self.robot, action_col=self.action_dim, processed_col=self.processed_dim, joint_names=self.entities.joint_names)
+        dim = osc.width
+        rec = dict(op=A_JOINT_AFFINE, ids_off=blob.ints([0] * dim), nids=dim, out=self.action_dim, dim=dim, p1=0.0)
+        if self.processed_dim != self.action_dim:
+            rec["p2"] = int(self.processed_dim)
+        if len(set(osc.scale)) == 1:
+            rec["p0"] = osc.scale[0]
+        else:
+            rec["aux0"] = blob.floats(osc.scale)
+        flags = 0
+        if any(lo_hi != (-math.inf, math.inf) for lo_hi in osc.clip):
+            rec["ids2_off"] = blob.floats([x for lo_hi in osc.clip for x in lo_hi])
+            rec["nids2"] = 2 * dim
+            flags |= F_ACT_CLIP
+        rec["flags"] = flags
+        self.act_recs.append(_rec(**rec))
+        self.action_terms.append(Term(name, cls, A_JOINT_AFFINE, dict(tcfg), dim=dim, processed_col=self.processed_dim, processed_dim=dim))
+        self.osc_terms.append(osc)
         self.action_dim += dim
         self.processed_dim += dim
 
@@ -1118,7 +1316,7 @@ class PlanCompiler:
                     enable_corruption=any(g_.enable_corruption for g_ in groups), ray_starts_local=ray_local, ray_direction=ray_dir,
                     ray_max_distance=self.ray_max, scanner_cfg=scanner, n_ext_rew=self.n_ext_rew, n_ext_term=self.n_ext_term,
                     n_ext_obs=self.n_ext_obs, gravity_dir=tuple(float(x) for x in gdir), mod_state_dim=self.mod_state,
-                    term_slots=len(self.term_slots), processed_action_dim=self.processed_dim, ik_terms=self.ik_terms)
+                    term_slots=len(self.term_slots), processed_action_dim=self.processed_dim, ik_terms=self.ik_terms, osc_terms=self.osc_terms)
 
 
 def compile_plan(env_cfg: Any, robot: RobotSpec) -> Plan:

@@ -189,6 +189,23 @@ def generate_jacobians(robot: RobotSpec, num_envs: int, gen: torch.Generator) ->
     return torch.cat([lin, ang], dim=2).contiguous()
 
 
+DYNAMICS = ("mass_matrices", "gravity_compensation_forces", "body_ang_vel_w")
+
+
+def generate_dynamics(robot: RobotSpec, num_envs: int, gen: torch.Generator) -> dict[str, torch.Tensor]:
+    """What an OperationalSpaceControllerAction reads beside the Jacobians (task_space_actions.py:568-574, 617-634):
+    ``root_physx_view.get_generalized_mass_matrices()`` (N, NM, NM), NM = the joints, symmetric positive definite with an arm-like
+    spectrum -- sym(B B^T / NM + diag(U(0.05, 1.5))), B ~ N(0, 1): condition numbers of a few to a few tens;
+    ``get_gravity_compensation_forces()`` (N, NM) ~ N(0, 5) N m; ``ArticulationData.body_ang_vel_w`` (N, B, 3) ~ N(0, 0.5) rad/s like
+    ``body_lin_vel_w``."""
+    N, NM, B = num_envs, robot.num_joints, robot.num_bodies
+    b = torch.randn(N, NM, NM, generator=gen)
+    m = b @ b.transpose(1, 2) / NM + torch.diag_embed(torch.rand(N, NM, generator=gen) * 1.45 + 0.05)
+    return {"mass_matrices": ((m + m.transpose(1, 2)) * 0.5).contiguous(),
+            "gravity_compensation_forces": torch.randn(N, NM, generator=gen) * 5.0,
+            "body_ang_vel_w": torch.randn(N, B, 3, generator=gen) * 0.5}
+
+
 # UniformPoseCommand ranges of the Reach tasks (manipulation/reach/reach_env_cfg.py): the position of the end-effector target in the base
 # frame; the orientation is any unit quaternion (the cfgs' roll 0, pitch pi or pi / 2, yaw +-3.14 Euler draws are a subset of it)
 POSE_COMMAND_POS_RANGE = ((0.35, 0.65), (-0.2, 0.2), (0.15, 0.5))
@@ -265,6 +282,21 @@ class StateFeed:
         self._stack["jacobians"] = torch.stack([generate_jacobians(self.robot, self.num_envs, gen) for _ in range(self.num_snapshots)],
                                                dim=0).to(self.device).contiguous()
 
+    def ensure_dynamics(self) -> None:
+        """Serve ``feed["mass_matrices"]``, ``feed["gravity_compensation_forces"]`` and ``feed["body_ang_vel_w"]``
+        (:func:`generate_dynamics`): built on the first request from a generator of their own seeded off the feed's seed, like the
+        Jacobians: no other tensor changes by a bit and a feed that never asks allocates nothing.  A recorded feed (``from_tensors``) has
+        them only when its snapshots carried them."""
+        if all(n in self._stack for n in DYNAMICS):
+            return
+        seed = getattr(self, "seed", None)
+        if seed is None:
+            raise KeyError(f"this recorded feed carries no {[n for n in DYNAMICS if n not in self._stack]}")
+        gen = torch.Generator().manual_seed(seed + 0xD1A5)
+        snaps = [generate_dynamics(self.robot, self.num_envs, gen) for _ in range(self.num_snapshots)]
+        for n in DYNAMICS:
+            self._stack[n] = torch.stack([sn[n] for sn in snaps], dim=0).to(self.device).contiguous()
+
     @classmethod
     def from_tensors(cls, robot: RobotSpec, snapshots: list[dict[str, torch.Tensor]], device="cpu",
                      gravity_dir=(0.0, 0.0, -1.0)) -> "StateFeed":
@@ -277,7 +309,7 @@ class StateFeed:
         self.history = snapshots[0]["net_forces_w_history"].shape[1]
         self._stack = {
             n: torch.stack([torch.as_tensor(s[n]) for s in snapshots], 0).to(self.device).contiguous()
-            for n in DYNAMIC + EXTRA + ("jacobians",) if n in snapshots[0]
+            for n in DYNAMIC + EXTRA + ("jacobians",) + DYNAMICS if n in snapshots[0]
         }
         self._static = {n: torch.as_tensor(snapshots[0][n]).to(self.device).contiguous() for n in STATIC}
         self.gravity_dir = [float(x) for x in gravity_dir]

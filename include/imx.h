@@ -337,8 +337,11 @@ enum imx_event_op {
     IMX_E_RESET_JOINTS_BY_OFFSET,       /* :1020-1049 */
     IMX_E_PUSH_BY_SETTING_VELOCITY,     /* :795-820;   ranges: lo/hi x 6 */
     IMX_E_APPLY_EXTERNAL_FORCE_TORQUE,  /* :764-791;   ranges: force lo, hi, torque lo, hi; body ids */
-    IMX_E_RESET_JOINTS_AROUND_DEFAULT   /* isaaclab_tasks .../velocity/config/spot/mdp/events.py:26-60; ranges as the joint resets: the
+    IMX_E_RESET_JOINTS_AROUND_DEFAULT,  /* isaaclab_tasks .../velocity/config/spot/mdp/events.py:26-60; ranges as the joint resets: the
                                            default +- range is clamped to the soft limits BEFORE sampling */
+    IMX_E_RESET_SCENE_TO_DEFAULT        /* envs/mdp/events.py:1096-1118; no ranges, no draws: default root state (+ env origin) and default
+                                           joint state of the robot, default root state of the scene's rigid object (imx_orch_manip_t);
+                                           imx_reset_orchestrate_manip only */
 };
 typedef struct imx_event_term {
     int32_t op;                            /* enum imx_event_op */
@@ -348,7 +351,9 @@ typedef struct imx_event_term {
     float interval_lo, interval_hi;        /* interval_range_s */
     float ranges[24];
     int32_t num_body_ids;
-    int32_t reserved;
+    int32_t asset;                         /* IMX_E_RESET_ROOT_STATE_UNIFORM: whose root state -- 0 the robot (imx_orch_t's default_root_state_d,
+                                              root_pose_out_d, root_vel_out_d), 1 the scene's rigid object (imx_orch_manip_t's;
+                                              imx_reset_orchestrate_manip only).  0 for every other op */
     const int32_t* body_ids_d;             /* IMX_E_APPLY_EXTERNAL_FORCE_TORQUE: resolved body ids (NULL = all bodies) */
     int32_t* last_triggered_step_d;        /* (N) reset terms: _reset_term_last_triggered_step_id */
     uint8_t* triggered_once_d;             /* (N) reset terms: _reset_term_last_triggered_once */
@@ -438,10 +443,25 @@ typedef struct imx_orch {
 size_t imx_orch_part_floats(int64_t num_envs);
 int imx_reset_orchestrate(const imx_orch_t* orch, imx_stream_t stream);
 
+/* ---- the manipulation tasks' part of _reset_idx (Isaac-Lift-Cube-Franka-v0, Isaac-Reach-*): imx_reset_orchestrate_manip -------
+ * imx_orch_t does not grow for it: what these tasks add travels in imx_orch_manip_t (imx_orch_manip.h, which this header includes).
+ *   - reset_scene_to_default (envs/mdp/events.py:1096-1118) and reset_root_state_uniform (:823-868) on the scene's one RigidObject
+ *     (imx_event_term_t.asset = 1) write the object's own "to simulator" buffers;
+ *   - modify_reward_weight (envs/mdp/curriculums.py:21-36: `if env.common_step_counter > num_steps: set_term_cfg(weight)`), evaluated
+ *     where the reference evaluates it -- CurriculumManager.compute inside _reset_idx (envs/manager_based_rl_env.py:347-392), that is
+ *     only in a launch that resets at least one env -- by a plain store of the new weight into the term's IMX_R_WEIGHT word of the
+ *     device-resident reward table (imx_plan_reward_weight_ptr).  *step_counter_d is common_step_counter at that point (the step
+ *     kernel has published this step's count; after ManagerBasedEnv.reset it is the last step's).  The next imx_terminations_rewards
+ *     launch reads the new weight (stream order).  Every workgroup with a reset env stores the same value: idempotent.
+ * The same launch otherwise does what imx_reset_orchestrate does; has_command is 0 or 2 (a pose command), no terrain curriculum. */
+typedef struct imx_orch_manip imx_orch_manip_t;
+#include "imx_orch_manip.h" /* IMX_ORCH_MAX_WEIGHT_TERMS, imx_weight_term_t and the definition of imx_orch_manip_t */
+int imx_reset_orchestrate_manip(const imx_orch_t* orch, const imx_orch_manip_t* manip, imx_stream_t stream);
+
 /* ---- library ---------------------------------------------------------------------------------------------------- */
 const char* imx_version(void);
 /* sizeof of an ABI struct as this library was compiled (which: 0 imx_state_t, 1 imx_buffers_t, 2 imx_head_loss_t, 3 imx_rollout_slot_t, 4 imx_policy_act_t, 5 imx_orch_t, 6 imx_event_term_t,
- * 7 imx_diff_ik_t, 8 imx_osc_t), 0 for an unknown index:
+ * 7 imx_diff_ik_t, 8 imx_osc_t, 10 imx_orch_manip_t, 11 imx_weight_term_t), 0 for an unknown index (9 is one):
  * a binding checks its own layout against it at load time. */
 size_t imx_struct_size(int which);
 const char* imx_last_error(void);
@@ -455,6 +475,14 @@ void imx_plan_destroy(imx_plan_t* plan);
  * `plan` IN PLACE by a recompiled blob of the same shape (same term counts, widths and table sizes -- a changed weight, threshold,
  * id list of equal length ...).  The copy is enqueued on `stream`; graphs that captured launches on `plan` stay valid. */
 int imx_plan_update(imx_plan_t* plan, const int32_t* blob, size_t nwords, imx_stream_t stream);
+/* Device address of reward term `reward_term_index`'s IMX_R_WEIGHT word (an f32; cfg order, as RewardManager.active_terms,
+ * managers/reward_manager.py:163-176) in the plan's device tables: what imx_orch_manip_t.weight_terms[].weight_d points at, and what a
+ * host reads back before it recompiles the tables (imx_plan_update would otherwise restore the weight of its blob).  The address is
+ * stable for the plan's lifetime (imx_plan_update copies in place). */
+int imx_plan_reward_weight_ptr(const imx_plan_t* plan, int reward_term_index, float** out);
+/* The f32 that word holds now, after everything enqueued on `stream` so far: waits for the stream (a host sync -- for set_term_cfg /
+ * get_term_cfg, never for the step or rollout path). */
+int imx_plan_reward_weight_get(const imx_plan_t* plan, int reward_term_index, imx_stream_t stream, float* out);
 size_t imx_plan_scratch_bytes(const imx_plan_t* plan, int64_t num_envs);
 int imx_plan_obs_dim(const imx_plan_t* plan);
 

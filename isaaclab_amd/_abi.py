@@ -155,5 +155,10 @@ try:
     OSC_HEADER = os.path.join(os.path.dirname(HEADER), "imx_osc_struct.h")
     with open(OSC_HEADER) as _f:
         _, _, OSC_STRUCTS, _ = parse(_f.read(), OSC_HEADER, DEFINES)
+    # imx_orch_manip.h, likewise: imx_orch_manip_t and the imx_weight_term_t it holds (imx_reset_orchestrate_manip)
+    MANIP_HEADER = os.path.join(os.path.dirname(HEADER), "imx_orch_manip.h")
+    with open(MANIP_HEADER) as _f:
+        _manip_defines, _, MANIP_STRUCTS, _ = parse(_f.read(), MANIP_HEADER, DEFINES)
+    DEFINES.update(_manip_defines)  # IMX_ORCH_MAX_WEIGHT_TERMS
 except OSError as e:
     raise AbiError(f"the ABI header {HEADER} cannot be read ({e}): the whole binding is derived from it") from e

@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libimx.so")
 
 ORCH_MAX_TERMS = _abi.DEFINES["IMX_ORCH_MAX_TERMS"]
+ORCH_MAX_WEIGHT_TERMS = _abi.DEFINES["IMX_ORCH_MAX_WEIGHT_TERMS"]
 IK_MAX_JOINTS = _abi.DEFINES["IMX_IK_MAX_JOINTS"]
 OSC_CMD_WIDTH = _abi.DEFINES["IMX_OSC_CMD_WIDTH"]
 _STRUCTS = {}  # typedef name -> class
@@ -80,6 +81,10 @@ ImxPolicyAct = _struct("imx_policy_act_t")
 ImxHeadLoss = _struct("imx_head_loss_t")
 _struct("imx_diff_ik_t", ImxDiffIk)
 ImxOsc._fields_ = [(field, _abi.ctype(t, _STRUCTS)) for field, t in _abi.OSC_STRUCTS["imx_osc_t"]]  # (imx_osc_struct.h: imx.h only declares the type)
+# (imx_orch_manip.h, the same way; the holder after the struct it holds by value)
+ImxWeightTerm = type("ImxWeightTerm", (ctypes.Structure,), {"_fields_": [(field, _abi.ctype(t, _STRUCTS)) for field, t in _abi.MANIP_STRUCTS["imx_weight_term_t"]]})
+ImxOrchManip = type("ImxOrchManip", (ctypes.Structure,), {"_fields_": [(field, _abi.ctype(t, {**_STRUCTS, "imx_weight_term_t": ImxWeightTerm}))
+                                                                      for field, t in _abi.MANIP_STRUCTS["imx_orch_manip_t"]]})
 if set(_STRUCTS) != set(_abi.STRUCTS):
     raise _abi.AbiError(f"{_abi.HEADER}: no class for {sorted(set(_abi.STRUCTS) - set(_STRUCTS))}")
 STATE_FIELDS = tuple(field for field, _ in ImxState._fields_)
@@ -118,7 +123,8 @@ def lib():
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
-    for which, cls in enumerate((ImxState, ImxBuffers, ImxHeadLoss, ImxRolloutSlot, ImxPolicyAct, ImxOrch, ImxEventTerm, ImxDiffIk, ImxOsc)):  # the binding's struct layouts against the library's
+    for which, cls in (*enumerate((ImxState, ImxBuffers, ImxHeadLoss, ImxRolloutSlot, ImxPolicyAct, ImxOrch, ImxEventTerm, ImxDiffIk, ImxOsc)),
+                       (10, ImxOrchManip), (11, ImxWeightTerm)):  # the binding's struct layouts against the library's (index 9 is unknown)
         if int(L.imx_struct_size(which)) != ctypes.sizeof(cls):
             raise ImxError(f"{LIB_PATH}: sizeof({cls.__name__}) is {int(L.imx_struct_size(which))} in the library, {ctypes.sizeof(cls)} in the "
                            "binding -- rebuild with `python -m isaaclab_amd.build`")

@@ -33,6 +33,8 @@ extern "C" size_t imx_struct_size(int which) {
         case 6: return sizeof(imx_event_term_t);
         case 7: return sizeof(imx_diff_ik_t);
         case 8: return sizeof(imx_osc_t);
+        case 10: return sizeof(imx_orch_manip_t);
+        case 11: return sizeof(imx_weight_term_t);
         default: return 0;
     }
 }
@@ -416,6 +418,24 @@ extern "C" int imx_plan_update(imx_plan_t* plan, const int32_t* blob, size_t nwo
     plan->dev = dev;
     q.dev = nullptr;
     if (dev && upload_plan(plan, (hipStream_t)stream, true)) return 1;
+    return 0;
+}
+
+extern "C" int imx_plan_reward_weight_ptr(const imx_plan_t* plan, int reward_term_index, float** out) {
+    IMX_REQUIRE(plan && out, "imx_plan_reward_weight_ptr: null argument");
+    IMX_REQUIRE(reward_term_index >= 0 && reward_term_index < plan->nrew, "imx_plan_reward_weight_ptr: reward term %d outside [0, %d)",
+                reward_term_index, plan->nrew);
+    IMX_REQUIRE(plan->dev, "imx_plan_reward_weight_ptr: the plan has no device tables (no GPU visible)");
+    *out = reinterpret_cast<float*>(plan->dev + plan->rew_off + (size_t)reward_term_index * IMX_REC_WORDS + IMX_R_WEIGHT);
+    return 0;
+}
+
+extern "C" int imx_plan_reward_weight_get(const imx_plan_t* plan, int reward_term_index, imx_stream_t stream, float* out) {
+    float* at = nullptr;
+    IMX_REQUIRE(out, "imx_plan_reward_weight_get: null argument");
+    if (imx_plan_reward_weight_ptr(plan, reward_term_index, &at)) return 1;
+    IMX_HIP(hipStreamSynchronize((hipStream_t)stream));
+    IMX_HIP(hipMemcpy(out, at, sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -14,6 +14,7 @@
 // from caller-supplied tables (the reference's torch.rand stream cannot be reproduced in a kernel).  The two means the log needs
 // (metrics over the reset envs, terrain level over all envs) leave as per-workgroup partial sums for the step tail (step.hip).
 #include "imx_internal.h"
+#include "imx_manip_events.h"
 #include "imx_producers.h"
 
 namespace {
@@ -31,9 +32,11 @@ __device__ __forceinline__ float wsum(float v) {
 }
 
 // POSE: the command term is a UniformPoseCommand (has_command == 2) instead of the velocity command; an instantiation of its own so that
-// the velocity cfgs run the register budget they always had, dispatched on the host
-template <bool POSE>
-__global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate(imx_orch_t o) {
+// the velocity cfgs run the register budget they always had, dispatched on the host.  MANIP: the manipulation tasks' launch
+// (imx_reset_orchestrate_manip) -- reset_scene_to_default, events on the scene's rigid object and the modify_reward_weight curriculum,
+// with imx_orch_manip_t as a second kernel argument; again an instantiation of its own (k_reset_orchestrate_manip below)
+template <bool POSE, bool MANIP>
+__device__ __forceinline__ void orch_body(const imx_orch_t& o, const imx_orch_manip_t* mp) {
     const int lane = threadIdx.x;
     const int64_t N = o.num_envs;
     const int64_t e0 = (int64_t)blockIdx.x * ORCH_BLOCK + lane;
@@ -46,7 +49,7 @@ __global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate(imx_orch_t o) 
     // ---- CurriculumManager.compute: terrain_levels_vel (curriculums.py:26-55) + update_env_origins (terrain_importer.py:307-326)
     float ox = o.env_origins_d[e * 3], oy = o.env_origins_d[e * 3 + 1], oz = o.env_origins_d[e * 3 + 2];
     float level_f = 0.0f;
-    if (o.terrain_levels_d) {
+    if (!MANIP && o.terrain_levels_d) {
         int64_t lv = o.terrain_levels_d[e];
         if (reset) {
             const float dx = o.root_pos_w_d[e * 3] - ox, dy = o.root_pos_w_d[e * 3 + 1] - oy;
@@ -73,6 +76,27 @@ __global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate(imx_orch_t o) 
     //      reset envs together (lanes stride over the row: coalesced stores, ~10 instructions per env) -- one lane walking its own env's
     //      272 + 384 floats was 650 store instructions in a divergent branch that 7 of 10 waves enter (25 us for the kernel).
     const uint64_t reset_lanes = __ballot(reset);
+    if (MANIP) {
+        // CurriculumManager.compute -> modify_reward_weight (envs/mdp/curriculums.py:21-36), run by _reset_idx only: a launch that resets
+        // no env stores nothing.  `step` is common_step_counter here.  Every workgroup with a reset env stores the same word: idempotent;
+        // the next imx_terminations_rewards launch reads it (stream order)
+        for (int i = 0; i < mp->num_weight_terms; ++i) {
+            const imx_weight_term_t& W = mp->weight_terms[i];
+            if (W.weight == 0.0f && W.step_reward_d) {
+                // a term this curriculum puts to sleep: the zero-weight skip never writes its step_reward column again, so the column
+                // would keep the values of the last step the term was awake.  The launch that takes the word from non-zero to 0 leaves
+                // 1 + its step count in *switch_step_d; from the NEXT step on every workgroup, with a reset env or without, zeroes the
+                // entries of its own envs.  In the launch of the switch itself a workgroup reads either the old 0 or step + 1 there,
+                // and stores nothing in both cases: that step's column keeps that step's values, whichever workgroup runs first
+                const int32_t sw = *W.switch_step_d;
+                if (sw != 0 && (int32_t)step >= sw && *W.weight_d == 0.0f && live) W.step_reward_d[e * mp->step_reward_stride] = 0.0f;
+            }
+            if (reset_lanes != 0ull && (int32_t)step > W.num_steps && lane == 0) {
+                if (W.switch_step_d && W.weight == 0.0f && *W.weight_d != 0.0f) *W.switch_step_d = (int32_t)step + 1;
+                *W.weight_d = W.weight;
+            }
+        }
+    }
     if (o.cs_timestamp_d || o.lstm_hidden_d) {
         for (uint64_t m = reset_lanes; m != 0ull; m &= m - 1ull) {
             const int64_t er = (int64_t)blockIdx.x * ORCH_BLOCK + (__ffsll((long long)m) - 1);  // wave-uniform
@@ -120,6 +144,23 @@ __global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate(imx_orch_t o) 
             }
         }
         const float* __restrict__ U = T.uniforms_d;
+        if (MANIP && T.op == IMX_E_RESET_SCENE_TO_DEFAULT) {  // events.py:1096-1118: rigid objects, then articulations
+            if (valid) {
+                if (mp->object_default_root_state_d)
+                    root_state_default_env(mp->object_default_root_state_d + e * 13, ox, oy, oz, mp->object_root_pose_out_d + e * 7,
+                                           mp->object_root_vel_out_d + e * 6);
+                root_state_default_env(o.default_root_state_d + e * 13, ox, oy, oz, o.root_pose_out_d + e * 7, o.root_vel_out_d + e * 6);
+            }
+            for (uint64_t m = __ballot(valid); m != 0ull; m &= m - 1ull) {  // the default joint state, unclamped: lane = joint
+                const int64_t er = (int64_t)blockIdx.x * ORCH_BLOCK + (__ffsll((long long)m) - 1);  // wave-uniform
+                for (int j = lane; j < J; j += ORCH_BLOCK) {
+                    const size_t q = (size_t)er * J + j;
+                    o.joint_pos_out_d[q] = o.default_joint_pos_d[q];
+                    o.joint_vel_out_d[q] = o.default_joint_vel_d[q];
+                }
+            }
+            continue;
+        }
         if (T.op == IMX_E_RESET_JOINTS_BY_SCALE || T.op == IMX_E_RESET_JOINTS_BY_OFFSET ||
             T.op == IMX_E_RESET_JOINTS_AROUND_DEFAULT) {  // events.py:987-1049, spot/mdp/events.py:26-60
             // lane = joint of one valid env at a time (the same draws, keyed by (env, column)): 2 J samples + clamps per env spread over
@@ -151,32 +192,17 @@ __global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate(imx_orch_t o) 
         }
         if (!valid) continue;
         switch (T.op) {
-            case IMX_E_RESET_ROOT_STATE_UNIFORM: {  // events.py:823-868
-                const float* d = o.default_root_state_d + e * 13;
+            case IMX_E_RESET_ROOT_STATE_UNIFORM: {  // events.py:823-868, on the robot or (MANIP, asset = 1) the scene's rigid object
+                const bool obj = MANIP && T.asset == 1;
+                const float* d = (obj ? mp->object_default_root_state_d : o.default_root_state_d) + e * 13;
                 float rs[6];
 #pragma unroll
                 for (int k = 0; k < 6; ++k) rs[k] = draw(U, 12, e, k, o.seed, t, step) * (T.ranges[2 * k + 1] - T.ranges[2 * k]) + T.ranges[2 * k];
-                float* pose = o.root_pose_out_d + e * 7;
-                pose[0] = d[0] + ox + rs[0];  // positions = default + env origin + sample (:852)
-                pose[1] = d[1] + oy + rs[1];
-                pose[2] = d[2] + oz + rs[2];
-                // quat_from_euler_xyz(roll, pitch, yaw) (math.py:266-276), then quat_mul(default, delta) (math.py:486-497)
-                const float cy = cosf(rs[5] * 0.5f), sy = sinf(rs[5] * 0.5f), cr = cosf(rs[3] * 0.5f), sr = sinf(rs[3] * 0.5f);
-                const float cp = cosf(rs[4] * 0.5f), sp = sinf(rs[4] * 0.5f);
-                const float w2 = cy * cr * cp + sy * sr * sp, x2 = cy * sr * cp - sy * cr * sp, y2 = cy * cr * sp + sy * sr * cp,
-                            z2 = sy * cr * cp - cy * sr * sp;
-                const float w1 = d[3], x1 = d[4], y1 = d[5], z1 = d[6];
-                const float ww = (z1 + x1) * (x2 + y2), yy = (w1 - y1) * (w2 + z2), zz = (w1 + y1) * (w2 - z2);
-                const float xx = ww + yy + zz;
-                const float qq = 0.5f * (xx + (z1 - x1) * (x2 - y2));
-                pose[3] = qq - ww + (z1 - y1) * (y2 - z2);
-                pose[4] = qq - xx + (x1 + w1) * (x2 + w2);
-                pose[5] = qq - yy + (w1 - x1) * (y2 + z2);
-                pose[6] = qq - zz + (z1 + y1) * (w2 - x2);
+                root_pose_uniform_env(d, ox, oy, oz, rs, (obj ? mp->object_root_pose_out_d : o.root_pose_out_d) + e * 7);
+                float* vel = (obj ? mp->object_root_vel_out_d : o.root_vel_out_d) + e * 6;
 #pragma unroll
                 for (int k = 0; k < 6; ++k)
-                    o.root_vel_out_d[e * 6 + k] =
-                        d[7 + k] + (draw(U, 12, e, 6 + k, o.seed, t, step) * (T.ranges[12 + 2 * k + 1] - T.ranges[12 + 2 * k]) + T.ranges[12 + 2 * k]);
+                    vel[k] = d[7 + k] + (draw(U, 12, e, 6 + k, o.seed, t, step) * (T.ranges[12 + 2 * k + 1] - T.ranges[12 + 2 * k]) + T.ranges[12 + 2 * k]);
             } break;
             case IMX_E_RESET_JOINTS_BY_SCALE:
             case IMX_E_RESET_JOINTS_BY_OFFSET:
@@ -207,7 +233,7 @@ __global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate(imx_orch_t o) 
 
     // ---- CommandTerm.reset for the reset envs (logs + zeroes the metrics, resamples), then CommandManager.compute(dt)
     float mxy0 = 0.0f, myaw0 = 0.0f;
-    if (POSE && live) {  // the same place, the same reset flag and the same two log columns as the velocity command
+    if (POSE && live && (!MANIP || o.has_command == 2)) {  // the same place, the same reset flag and the same two log columns as the velocity command
         PoseCmdCfg c;
         c.resample_lo = o.command_cfg[0]; c.resample_hi = o.command_cfg[1];
         c.pos_x_lo = o.command_cfg[2]; c.pos_x_hi = o.command_cfg[3]; c.pos_y_lo = o.command_cfg[4]; c.pos_y_hi = o.command_cfg[5];
@@ -291,11 +317,21 @@ __global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate(imx_orch_t o) 
     }
 }
 
+template <bool POSE>
+__global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate(imx_orch_t o) {
+    orch_body<POSE, false>(o, nullptr);
+}
+
+__global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate_manip(imx_orch_t o, imx_orch_manip_t m) {
+    orch_body<true, true>(o, &m);
+}
+
 }  // namespace
 
 extern "C" size_t imx_orch_part_floats(int64_t num_envs) { return num_envs > 0 ? (size_t)((num_envs + ORCH_BLOCK - 1) / ORCH_BLOCK) * 4 : 0; }
 
-extern "C" int imx_reset_orchestrate(const imx_orch_t* o, imx_stream_t stream) {
+// the argument checks of both entry points (m = NULL: imx_reset_orchestrate) and the launch
+static int orch_launch(const imx_orch_t* o, const imx_orch_manip_t* m, imx_stream_t stream) {
     IMX_REQUIRE(o, "imx_reset_orchestrate: null descriptor");
     IMX_REQUIRE(o->num_envs > 0 && o->num_envs < (1ll << 31), "imx_reset_orchestrate: num_envs out of range");
     IMX_REQUIRE(o->num_terms >= 0 && o->num_terms <= IMX_ORCH_MAX_TERMS, "imx_reset_orchestrate: %d event terms (at most %d)", o->num_terms,
@@ -311,7 +347,24 @@ extern "C" int imx_reset_orchestrate(const imx_orch_t* o, imx_stream_t stream) {
             IMX_REQUIRE(T.op == IMX_E_PUSH_BY_SETTING_VELOCITY || T.op == IMX_E_APPLY_EXTERNAL_FORCE_TORQUE,
                         "imx_reset_orchestrate: interval term %d: op %d is not an interval event here", t, T.op);
         }
+        IMX_REQUIRE(T.asset == 0 || (T.asset == 1 && T.op == IMX_E_RESET_ROOT_STATE_UNIFORM),
+                    "imx_reset_orchestrate: term %d: asset %d with op %d (0 the robot; 1 the rigid object, reset_root_state_uniform only)", t, T.asset, T.op);
+        if (T.asset == 1) {
+            IMX_REQUIRE(m, "imx_reset_orchestrate: term %d acts on the rigid object: that is imx_reset_orchestrate_manip", t);
+            IMX_REQUIRE(m->object_default_root_state_d && m->object_root_pose_out_d && m->object_root_vel_out_d,
+                        "imx_reset_orchestrate_manip: term %d acts on the rigid object, which lacks its default root state or an out buffer", t);
+            continue;
+        }
         switch (T.op) {
+            case IMX_E_RESET_SCENE_TO_DEFAULT:
+                IMX_REQUIRE(m, "imx_reset_orchestrate: term %d is reset_scene_to_default: that is imx_reset_orchestrate_manip", t);
+                IMX_REQUIRE(T.mode == 0, "imx_reset_orchestrate_manip: reset_scene_to_default is a reset event (term %d has mode %d)", t, T.mode);
+                IMX_REQUIRE(o->default_root_state_d && o->root_pose_out_d && o->root_vel_out_d && o->num_joints > 0 && o->default_joint_pos_d &&
+                            o->default_joint_vel_d && o->joint_pos_out_d && o->joint_vel_out_d,
+                            "imx_reset_orchestrate_manip: reset_scene_to_default needs the robot's default root and joint state and their outputs");
+                IMX_REQUIRE(!m->object_default_root_state_d || (m->object_root_pose_out_d && m->object_root_vel_out_d),
+                            "imx_reset_orchestrate_manip: the rigid object lacks an out buffer");
+                break;
             case IMX_E_RESET_ROOT_STATE_UNIFORM:
                 IMX_REQUIRE(o->default_root_state_d && o->root_pose_out_d && o->root_vel_out_d, "imx_reset_orchestrate: reset_root_state_uniform needs "
                             "default_root_state, root_pose_out and root_vel_out");
@@ -371,10 +424,30 @@ extern "C" int imx_reset_orchestrate(const imx_orch_t* o, imx_stream_t stream) {
     if (o->lstm_hidden_d) IMX_REQUIRE(o->lstm_cell_d && o->lstm_layers > 0 && o->lstm_hidden_dim > 0 && o->num_joints > 0,
                                       "imx_reset_orchestrate: incomplete actuator-net state");
     const unsigned grid = (unsigned)((o->num_envs + ORCH_BLOCK - 1) / ORCH_BLOCK);
-    if (o->has_command == 2)
+    if (m) {
+        IMX_REQUIRE(o->has_command != 1, "imx_reset_orchestrate_manip: the command term is a velocity command (has_command 0 or 2 here)");
+        IMX_REQUIRE(!o->terrain_levels_d, "imx_reset_orchestrate_manip: the terrain curriculum is not part of this launch");
+        IMX_REQUIRE(m->num_weight_terms >= 0 && m->num_weight_terms <= IMX_ORCH_MAX_WEIGHT_TERMS,
+                    "imx_reset_orchestrate_manip: %d weight terms (at most %d)", m->num_weight_terms, IMX_ORCH_MAX_WEIGHT_TERMS);
+        IMX_REQUIRE(m->num_weight_terms == 0 || o->step_counter_d, "imx_reset_orchestrate_manip: the weight curriculum reads step_counter");
+        for (int i = 0; i < m->num_weight_terms; ++i) {
+            IMX_REQUIRE(m->weight_terms[i].weight_d, "imx_reset_orchestrate_manip: weight term %d has no weight address", i);
+            IMX_REQUIRE(!m->weight_terms[i].step_reward_d || (m->step_reward_stride > 0 && m->weight_terms[i].switch_step_d),
+                        "imx_reset_orchestrate_manip: weight term %d has a step_reward column but no switch_step word or no step_reward_stride (%d)",
+                        i, m->step_reward_stride);
+        }
+        hipLaunchKernelGGL(k_reset_orchestrate_manip, dim3(grid), dim3(ORCH_BLOCK), 0, (hipStream_t)stream, *o, *m);
+    } else if (o->has_command == 2)
         hipLaunchKernelGGL(k_reset_orchestrate<true>, dim3(grid), dim3(ORCH_BLOCK), 0, (hipStream_t)stream, *o);
     else
         hipLaunchKernelGGL(k_reset_orchestrate<false>, dim3(grid), dim3(ORCH_BLOCK), 0, (hipStream_t)stream, *o);
     IMX_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" int imx_reset_orchestrate(const imx_orch_t* o, imx_stream_t stream) { return orch_launch(o, nullptr, stream); }
+
+extern "C" int imx_reset_orchestrate_manip(const imx_orch_t* o, const imx_orch_manip_t* m, imx_stream_t stream) {
+    IMX_REQUIRE(m, "imx_reset_orchestrate_manip: null imx_orch_manip_t");
+    return orch_launch(o, m, stream);
 }

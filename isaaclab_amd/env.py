@@ -374,6 +374,7 @@ class RewardManager:
         """reward_manager.py:178-193"""
         if term_name not in self._term_names:
             raise ValueError(f"Reward term '{term_name}' not found.")
+        self._env._sync_curriculum_weights()  # (a weight a curriculum term switched on the device)
         return TermCfgView(self._env._cfg_dict["rewards"][term_name])
 
     def set_term_cfg(self, term_name: str, cfg):
@@ -611,14 +612,17 @@ class ManagerBasedRLEnv:
                  device: str | torch.device | None = None, seed: int | None = None, noise_seed: int = 0,
                  terrain_cell: float = 0.0, use_command_term: bool = False, use_contact_sensor: bool = False,
                  events_cfg: dict | bool | None = None, use_curriculum: bool = False, terrain_importer=None, own_managers: bool = False,
-                 command_term=None, **kwargs):
+                 command_term=None, reward_curriculum: bool = False, **kwargs):
         """``own_managers=True``: the env runs its cfg's EventManager (reset / interval terms), CommandManager (UniformVelocityCommand or
         UniformPoseCommand, by the term's ``class_type``) and CurriculumManager (terrain_levels_vel) itself -- ``_reset_idx`` + the
         command / interval updates of ``step`` as ONE orchestration launch (``imx_reset_orchestrate``) -- instead of taking commands
         from the feed; the single switches (``events_cfg`` = a dict or True for the cfg's own, ``command_term``, ``use_curriculum``)
         select parts of it.  ``command_term``: the name of a command term of the cfg (``"ee_pose"``, ``"base_velocity"``), built by its
         ``class_type``, or a ready ``producers.Uniform*Command``; ``use_command_term=True`` is the older velocity-only switch.
-        ``terrain_importer``: an ``events.TerrainImporterState`` (default: built from the cfg's terrain generator grid)."""
+        ``terrain_importer``: an ``events.TerrainImporterState`` (default: built from the cfg's terrain generator grid).
+        ``reward_curriculum=True``: the CurriculumManager also builds the cfg's ``modify_reward_weight`` terms (the Reach and Lift tasks'
+        curriculum) -- the weight switch happens on the device, inside the orchestration launch, at the reference's step; without the
+        keyword such a term is refused."""
         if own_managers:
             ec = cfg.get("env", cfg) if isinstance(cfg, dict) else None
             ec = ec if ec is not None else (load_task_cfg(cfg)["env"] if isinstance(cfg, str) else cfg.to_dict())
@@ -844,7 +848,8 @@ class ManagerBasedRLEnv:
             from .producers import ArticulationRootState
 
             self.articulation = ArticulationRootState(N, plan.num_joints, self.device)
-        self._orch = None
+        self._orch = self._orch_manip = None
+        self._weight_switch_step = None  # one device word per modify_reward_weight term (imx_weight_term_t.switch_step_d)
         J = plan.num_joints
         if events_cfg:
             from .events import EventManager
@@ -852,12 +857,25 @@ class ManagerBasedRLEnv:
             ev = env_dict.get("events") if events_cfg is True else events_cfg
             if not ev:
                 raise ValueError("events_cfg=True but the env cfg has no events")
-            self.event_manager = EventManager(ev, N, plan.robot, self.device, seed=noise_seed)
+            self.event_manager = EventManager(ev, N, plan.robot, self.device, seed=noise_seed, entities=self._entities, scene=env_dict.get("scene"))
         if use_curriculum:
             from .events import CurriculumManager, TerrainImporterState
 
             # (first: a curriculum term without a kernel -- the Reach tasks' modify_reward_weight -- is refused by name, terrain or not)
-            self.curriculum_manager = CurriculumManager(env_dict.get("curriculum") or {}, self)
+            self.curriculum_manager = CurriculumManager(env_dict.get("curriculum") or {}, self, reward_curriculum=reward_curriculum)
+            cm = self.curriculum_manager
+            if cm.weight_terms:  # these terms run in imx_reset_orchestrate_manip, which has no terrain curriculum and no velocity command
+                first = cm.weight_terms[0]["name"]
+                if cm.terrain_terms:
+                    raise NotImplementedError(f"curriculum term '{first}': modify_reward_weight beside terrain_levels_vel ('{cm.terrain_terms[0]}') "
+                                              "is not built: the launch that switches reward weights has no terrain curriculum")
+                if self.command_term is not None and not self._pose_command:
+                    raise NotImplementedError(f"curriculum term '{first}': modify_reward_weight beside the velocity command term "
+                                              f"'{self.command_term_name}' is not built: the launch that switches reward weights runs a "
+                                              "UniformPoseCommand or no command term")
+                # allocated once for the env's lifetime: a rebuilt descriptor (attach_actuator) keeps an earlier switch
+                self._weight_switch_step = torch.zeros(len(cm.weight_terms), dtype=torch.int32, device=self.device)
+        if use_curriculum and (self.curriculum_manager.terrain_terms or not self.curriculum_manager.weight_terms):
             if terrain_importer is None:
                 tg = ((env_dict.get("scene") or {}).get("terrain") or {}).get("terrain_generator")
                 if not tg:
@@ -866,7 +884,7 @@ class ManagerBasedRLEnv:
             self.terrain_importer = terrain_importer
             if self.command_term is None:
                 raise ValueError("the terrain curriculum reads the env's own velocity command: use_command_term=True")
-            if self._pose_command and self.curriculum_manager.active_terms:
+            if self._pose_command and self.curriculum_manager.terrain_terms:
                 raise ValueError("the terrain curriculum (terrain_levels_vel) reads a velocity command; this env's command term "
                                  f"'{self.command_term_name}' is a UniformPoseCommand")
         if self.event_manager is not None or self.command_term is not None or self.curriculum_manager is not None:
@@ -881,6 +899,18 @@ class ManagerBasedRLEnv:
             self.sim_writes = {"root_pose": torch.zeros(N, 7, device=self.device), "root_vel": torch.zeros(N, 6, device=self.device),
                                "joint_pos": torch.zeros(N, J, device=self.device), "joint_vel": torch.zeros(N, J, device=self.device),
                                "ext_force": torch.zeros(N, NB, 3, device=self.device), "ext_torque": torch.zeros(N, NB, 3, device=self.device)}
+            # the scene's rigid object (Lift's cube): its default root state from scene.<object>.init_state, and what its
+            # write_root_pose_to_sim / write_root_velocity_to_sim receive
+            self.default_object_root_state = None
+            if len(self._entities.rigid_objects) == 1:
+                oinit = ((env_dict.get("scene") or {}).get(next(iter(self._entities.rigid_objects))) or {}).get("init_state") or {}
+                ors = torch.zeros(N, 13, device=self.device)
+                ors[:, 0:3] = torch.tensor(oinit.get("pos", (0.0, 0.0, 0.0)), dtype=torch.float32, device=self.device)
+                ors[:, 3:7] = torch.tensor(oinit.get("rot", (1.0, 0.0, 0.0, 0.0)), dtype=torch.float32, device=self.device)
+                ors[:, 7:10] = torch.tensor(oinit.get("lin_vel", (0.0, 0.0, 0.0)), dtype=torch.float32, device=self.device)
+                ors[:, 10:13] = torch.tensor(oinit.get("ang_vel", (0.0, 0.0, 0.0)), dtype=torch.float32, device=self.device)
+                self.default_object_root_state = ors
+                self.sim_writes.update(object_root_pose=torch.zeros(N, 7, device=self.device), object_root_vel=torch.zeros(N, 6, device=self.device))
             self._ev_part = torch.zeros(int(self._lib.imx_orch_part_floats(N)), device=self.device)
             self._orch_draws = {}  # parity runs: "command" -> (2,N,7) uniforms, "rand_levels" -> (N) int64
             self.defer_step_tail = True
@@ -903,8 +933,8 @@ class ManagerBasedRLEnv:
             for i, m in enumerate(self.command_term.metrics):  # (error_vel_xy, error_vel_yaw) or (position_error, orientation_error)
                 self._log_index[f"Metrics/{self.command_term_name}/{m}"] = base + i
             ev_flags |= 1
-        if self.curriculum_manager is not None:
-            for n in self.curriculum_manager.active_terms:  # curriculum_manager.py:95-118
+        if self.curriculum_manager is not None and (self.curriculum_manager.terrain_terms or not self.curriculum_manager.weight_terms):
+            for n in self.curriculum_manager.terrain_terms:  # curriculum_manager.py:95-118 (a modify_reward_weight term logs nothing)
                 self._log_index[f"Curriculum/{n}"] = base + 2
             ev_flags |= 2
         self._log_views = {k: self._log_out[i] for k, i in self._log_index.items()}
@@ -992,7 +1022,32 @@ class ManagerBasedRLEnv:
             pass
 
     # ---- internals -------------------------------------------------------------------------------------------------
+    def _weight_ptr(self, index: int) -> int:
+        out = ctypes.c_void_p()
+        check(self._lib.imx_plan_reward_weight_ptr(self._plan_h, int(index), ctypes.byref(out)))
+        return out.value
+
+    def _sync_curriculum_weights(self):
+        """The reward weights a ``modify_reward_weight`` curriculum term owns are switched on the device (imx_reset_orchestrate_manip):
+        read them back into the cfg dict and the plan's Python mirror.  A host sync, so only off the hot path: before the tables are
+        recompiled (which would otherwise restore the old weight) and in ``reward_manager.get_term_cfg``; nothing on the step or
+        rollout path calls it."""
+        cm = self.curriculum_manager
+        if cm is None or not cm.weight_terms:
+            return
+        for w in cm.weight_terms:
+            host = ctypes.c_float()
+            check(self._lib.imx_plan_reward_weight_get(self._plan_h, w["index"], _lib.current_stream(self.device), ctypes.byref(host)))
+            entry = self._cfg_dict["rewards"][w["term_name"]]
+            if ctypes.c_float(entry["weight"]).value == host.value:
+                continue  # not switched (yet): the cfg keeps the value it was written with
+            # the switched weight as the curriculum term's cfg spells it (the table holds its fp32 rounding)
+            new = w["weight"] if ctypes.c_float(w["weight"]).value == host.value else float(host.value)
+            entry["weight"] = new
+            self.plan.reward_terms[w["index"]].weight = new
+
     def _install_term_cfg(self, section: str, term_name: str, entry: dict):
+        self._sync_curriculum_weights()
         old = self._cfg_dict[section][term_name]
         new = dict(old)
         new.update({k: v for k, v in entry.items() if k in old or k in ("weight", "params", "func", "time_out")})
@@ -1014,6 +1069,10 @@ class ManagerBasedRLEnv:
         for cur, fresh in zip(self.plan.termination_terms, plan.termination_terms):
             cur.params, cur.time_out = fresh.params, fresh.time_out
         self.plan.blob = plan.blob
+        if self._weight_switch_step is not None and section == "rewards":
+            for i, w in enumerate(self.curriculum_manager.weight_terms):
+                if w["term_name"] == term_name and new["weight"] != 0.0:
+                    self._weight_switch_step[i] = 0  # woken by hand: should its curriculum put it to sleep again, that is a new switch
         for kind in ("rew", "term"):
             for t, _ in self._ext_funcs[kind]:
                 self._resolve_ext(t)  # call-time parameters of Python-evaluated terms follow the new cfg
@@ -1198,7 +1257,7 @@ class ManagerBasedRLEnv:
                     ev_part_d=p(self._ev_part))
         if self.event_manager is not None:
             self.event_manager.fill(o)
-        if self.curriculum_manager is not None and self.curriculum_manager.active_terms:
+        if self.curriculum_manager is not None and self.curriculum_manager.terrain_terms:
             ti = self.terrain_importer
             o.terrain_origins_d, o.terrain_types_d, o.terrain_levels_d = p(ti.terrain_origins), p(ti.terrain_types), p(ti.terrain_levels)
             o.terrain_rows, o.terrain_cols = int(ti.terrain_origins.shape[0]), int(ti.terrain_origins.shape[1])
@@ -1236,6 +1295,24 @@ class ManagerBasedRLEnv:
         if an is not None:
             o.lstm_hidden_d, o.lstm_cell_d = p(an.sea_hidden_state), p(an.sea_cell_state)
             o.lstm_layers, o.lstm_hidden_dim = an.num_layers, an.hidden_dim
+        # the manipulation tasks' launch (imx_reset_orchestrate_manip): an event on the rigid object, reset_scene_to_default or a
+        # modify_reward_weight curriculum; every other env keeps the entry point it always had
+        self._orch_manip = None
+        cm = self.curriculum_manager
+        weights = cm.weight_terms if cm is not None else []
+        if weights or (self.event_manager is not None and self.event_manager.needs_manip):
+            m = _lib.ImxOrchManip(num_weight_terms=len(weights), step_reward_stride=self._step_reward.shape[1])
+            if self.default_object_root_state is not None:
+                m.object_default_root_state_d = p(self.default_object_root_state)
+                m.object_root_pose_out_d, m.object_root_vel_out_d = p(self.sim_writes["object_root_pose"]), p(self.sim_writes["object_root_vel"])
+            for i, w in enumerate(weights):
+                W = m.weight_terms[i]
+                W.weight_d, W.weight, W.num_steps = self._weight_ptr(w["index"]), w["weight"], w["num_steps"]
+                # the term's _step_reward column, zeroed from the step after a switch to weight 0 (the zero-weight skip alone would
+                # keep its last values), and the device word that holds when that switch happened
+                W.step_reward_d = self._step_reward.data_ptr() + 4 * w["index"]
+                W.switch_step_d = self._weight_switch_step.data_ptr() + 4 * i
+            self._orch_manip = m
         return o
 
     def _orchestrate(self, reset_mask, do_step: bool):
@@ -1257,7 +1334,10 @@ class ManagerBasedRLEnv:
                 o.terms[i].uniforms_d, o.terms[i].interval_uniforms_d = _lib.ptr(t.uniforms), _lib.ptr(t.interval_uniforms)
         o.command_uniforms_d = _lib.ptr(self._orch_draws.get("command"))
         o.rand_levels_d = _lib.ptr(self._orch_draws.get("rand_levels"))
-        check(self._lib.imx_reset_orchestrate(ctypes.byref(o), _lib.current_stream(self.device)))
+        if self._orch_manip is not None:
+            check(self._lib.imx_reset_orchestrate_manip(ctypes.byref(o), ctypes.byref(self._orch_manip), _lib.current_stream(self.device)))
+        else:
+            check(self._lib.imx_reset_orchestrate(ctypes.byref(o), _lib.current_stream(self.device)))
 
     # ---- MDP operations ------------------------------------------------------------------------------------------
     def reset(self, seed: int | None = None, env_ids: Sequence[int] | None = None, options: dict | None = None):

@@ -148,7 +148,8 @@ class EventTermState:
     """One reset- or interval-mode term of the reference's ``EventCfg``: its compiled ranges and the state ``EventManager`` keeps for it
     (managers/event_manager.py: ``_reset_term_last_triggered_step_id`` / ``_reset_term_last_triggered_once``, ``_interval_term_time_left``)."""
 
-    def __init__(self, name: str, term: dict, num_envs: int, robot, device):
+    def __init__(self, name: str, term: dict, num_envs: int, robot, device, entities=None):
+        """``entities``: the env's ``robots.SceneEntityResolver`` (None: the robot is the scene's only asset)."""
         from .robots import resolve_matching_names
 
         self.name, self.cfg = name, term
@@ -165,7 +166,22 @@ class EventTermState:
         r = [0.0] * 24
         self.width = 0
         self.body_ids = None
-        if self.func == "reset_root_state_uniform":
+        # params["asset_cfg"].name -> the asset selector of imx_event_term_t: 0 the robot, 1 the scene's rigid object
+        ent = p.get("asset_cfg") or {}
+        ent_name = (ent.get("name") if isinstance(ent, dict) else getattr(ent, "name", None)) or "robot"
+        objects = list(entities.rigid_objects) if entities is not None else []
+        if ent_name != "robot" and ent_name not in objects:
+            raise ValueError(f"event term '{name}': asset_cfg names the scene entity '{ent_name}'; the scene has {['robot'] + objects}")
+        self.asset = 0 if ent_name == "robot" else 1
+        if self.asset == 1 and len(objects) > 1:
+            raise NotImplementedError(f"event term '{name}': the scene has {len(objects)} rigid objects {objects}; the orchestration "
+                                      "launch carries one object's root state")
+        if self.asset == 1 and self.func != "reset_root_state_uniform":
+            raise NotImplementedError(f"event term '{name}': '{self.func}' on the rigid object '{ent_name}' has no kernel "
+                                      "(reset_root_state_uniform has)")
+        if self.func == "reset_scene_to_default":
+            pass  # events.py:1096-1118: no ranges, no draws
+        elif self.func == "reset_root_state_uniform":
             r[:24] = _axis_ranges(p.get("pose_range")) + _axis_ranges(p.get("velocity_range"))
             self.width = 12
         elif self.func.startswith("reset_joints"):
@@ -209,7 +225,9 @@ class EventManager:
     (``imx_reset_orchestrate``), which takes the step's reset mask and the timers and never reads anything back.  Startup-mode terms
     (PhysX materials, masses: simulator side) are listed in ``skipped_terms``, not run."""
 
-    def __init__(self, events_cfg: dict, num_envs: int, robot, device, seed: int = 0):
+    def __init__(self, events_cfg: dict, num_envs: int, robot, device, seed: int = 0, entities=None, scene: dict | None = None):
+        """``entities`` / ``scene``: the env's ``SceneEntityResolver`` and its cfg's ``scene`` dict, for terms that name or walk the
+        scene's assets (an event on the rigid object, ``reset_scene_to_default``)."""
         self.terms: list[EventTermState] = []
         self.skipped_terms: list[str] = []
         self.seed = int(seed)
@@ -220,7 +238,16 @@ class EventManager:
             if term.get("mode") not in ("reset", "interval"):
                 self.skipped_terms.append(name)
                 continue
-            self.terms.append(EventTermState(name, term, num_envs, robot, device))
+            self.terms.append(EventTermState(name, term, num_envs, robot, device, entities))
+            if self.terms[-1].func == "reset_scene_to_default":  # it walks every asset of the scene: those without a kernel are refused
+                objects = list(entities.rigid_objects) if entities is not None else []
+                soft = [k for k, v in (scene or {}).items() if isinstance(v, dict) and str(v.get("class_type") or "").endswith(":DeformableObject")]
+                if soft:
+                    raise NotImplementedError(f"event term '{name}': reset_scene_to_default on a scene with deformable objects {soft} "
+                                              "has no kernel")
+                if len(objects) > 1:
+                    raise NotImplementedError(f"event term '{name}': the scene has {len(objects)} rigid objects {objects}; the "
+                                              "orchestration launch carries one object's root state")
         if len(self.terms) > _lib.ORCH_MAX_TERMS:
             raise NotImplementedError(f"{len(self.terms)} reset / interval event terms (at most {_lib.ORCH_MAX_TERMS})")
 
@@ -230,6 +257,11 @@ class EventManager:
         for t in self.terms:
             out.setdefault(t.mode, []).append(t.name)
         return out
+
+    @property
+    def needs_manip(self) -> bool:
+        """A term that only ``imx_reset_orchestrate_manip`` runs: ``reset_scene_to_default`` or an event on the rigid object."""
+        return any(t.asset == 1 or t.func == "reset_scene_to_default" for t in self.terms)
 
     @property
     def available_modes(self) -> list:
@@ -255,7 +287,7 @@ class EventManager:
             T.interval_lo, T.interval_hi = float(t.interval_range_s[0]), float(t.interval_range_s[1])
             for k, v in enumerate(t.ranges):
                 T.ranges[k] = v
-            T.num_body_ids = 0 if t.body_ids is None else int(t.body_ids.numel())
+            T.num_body_ids, T.asset = (0 if t.body_ids is None else int(t.body_ids.numel())), t.asset
             T.body_ids_d = _lib.ptr(t.body_ids)
             T.last_triggered_step_d, T.triggered_once_d = _lib.ptr(t.last_triggered_step), _lib.ptr(t.triggered_once)
             T.time_left_d = _lib.ptr(t.time_left)
@@ -289,19 +321,42 @@ class TerrainImporterState:
 
 
 class CurriculumManager:
-    """``isaaclab.managers.CurriculumManager`` surface for the one curriculum term with a kernel, ``terrain_levels_vel``; ``compute`` is
-    part of the orchestration launch, ``reset`` reports the state the reference logs (curriculum_manager.py:95-118)."""
+    """``isaaclab.managers.CurriculumManager`` surface for the curriculum terms with a kernel: ``terrain_levels_vel`` and, with
+    ``reward_curriculum=True``, ``modify_reward_weight`` (envs/mdp/curriculums.py:21-36).  ``compute`` is part of the orchestration
+    launch -- the weight switch is a device-side store into the reward table, gated like the reference's by "this launch resets an env"
+    and ``common_step_counter > num_steps`` -- ``reset`` reports the state the reference logs (curriculum_manager.py:95-118)."""
 
-    def __init__(self, curriculum_cfg: dict, env):
+    def __init__(self, curriculum_cfg: dict, env, reward_curriculum: bool = False):
         self._env = env
         self._term_names = []
+        self.terrain_terms: list = []
+        self.weight_terms: list = []  # {name, term_name, index (reward term), weight, num_steps}, cfg order
+        rewards = [t.name for t in env.plan.reward_terms]
         for name, term in (curriculum_cfg or {}).items():
             if term is None:
                 continue
-            fn = _func_name(term if isinstance(term, dict) else term.to_dict())
-            if fn != "terrain_levels_vel":
+            term = term if isinstance(term, dict) else term.to_dict()
+            fn = _func_name(term)
+            if fn == "modify_reward_weight" and reward_curriculum:
+                p = term.get("params") or {}
+                missing = [k for k in ("term_name", "weight", "num_steps") if k not in p]
+                if missing:
+                    raise ValueError(f"curriculum term '{name}': modify_reward_weight lacks {missing}")
+                if p["term_name"] not in rewards:
+                    raise ValueError(f"Reward term '{p['term_name']}' not found.")  # (reward_manager.get_term_cfg, through curriculum term '{name}')
+                target = env.plan.reward_terms[rewards.index(p["term_name"])]
+                if target.external is not None:
+                    raise NotImplementedError(f"curriculum term '{name}': reward term '{target.name}' is evaluated in Python, which reads its "
+                                              "weight on the host; the device-side weight switch would not reach it")
+                if len(self.weight_terms) == _lib.ORCH_MAX_WEIGHT_TERMS:
+                    raise NotImplementedError(f"curriculum term '{name}': more than {_lib.ORCH_MAX_WEIGHT_TERMS} modify_reward_weight terms")
+                self.weight_terms.append(dict(name=name, term_name=target.name, index=rewards.index(target.name), weight=float(p["weight"]),
+                                              num_steps=int(p["num_steps"])))
+            elif fn == "terrain_levels_vel":
+                self.terrain_terms.append(name)
+            else:
                 raise NotImplementedError(f"curriculum term '{name}': '{fn}' has no kernel (terrain_levels_vel has; modify_reward_weight is "
-                                          "RewardManager.set_term_cfg on the host)")
+                                          "RewardManager.set_term_cfg on the host, or runs on the device with reward_curriculum=True)")
             self._term_names.append(name)
 
     @property
@@ -309,5 +364,7 @@ class CurriculumManager:
         return list(self._term_names)
 
     def reset(self, env_ids=None) -> dict:
+        """``Curriculum/<term>`` of the terrain terms; modify_reward_weight returns None, and None states are not logged
+        (curriculum_manager.py:105)."""
         ti = self._env.terrain_importer
-        return {f"Curriculum/{n}": torch.mean(ti.terrain_levels.float()) for n in self._term_names}
+        return {f"Curriculum/{n}": torch.mean(ti.terrain_levels.float()) for n in self.terrain_terms}

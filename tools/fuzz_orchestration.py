@@ -3,7 +3,9 @@ CommandManager / CurriculumManager) against oracle/orchestration_oracle.py (pinn
 and state snapshots, but RANDOM draw tables, actions, episode lengths and step counts -- other reset patterns, timer phases, curriculum
 moves and resampling sequences than the 48 recorded steps.  Simulator writes, trigger state, timers, levels / origins exact or 1e-5.
 ``one_case_pose`` is the same sweep over the Franka Reach cfg with the env's own UniformPoseCommand (``has_command = 2``).
-Test infrastructure, run on the GPU box:  python tools/fuzz_orchestration.py [cases] [seed] [pose]"""
+``one_case_manip`` sweeps the manipulation launch (imx_reset_orchestrate_manip) on the Lift cfg against tests/_manip_orch_oracle.py:
+random ranges, object defaults, thresholds and reset masks.
+Test infrastructure, run on the GPU box:  python tools/fuzz_orchestration.py [cases] [seed] [pose|manip]"""
 import os
 import sys
 
@@ -195,11 +197,86 @@ def one_case_pose(seed: int) -> str:
     return f"steps={steps} resets={resets} resampled twice in a step={twice} unique={bool(ccfg.get('make_quat_unique'))} resample={ccfg['resampling_time_range']}"
 
 
+_MG = None
+
+
+def one_case_manip(seed: int) -> str:
+    """``imx_reset_orchestrate_manip`` alone (``env._orchestrate`` on a mask of the case's own) on the Lift cfg of
+    tests/golden/lift_manip_orchestration.json: reset_scene_to_default, reset_root_state_uniform on the object and two modify_reward_weight
+    terms with RANDOM pose / velocity ranges on all six axes, object defaults (rotated), env origins, thresholds, step counts and reset
+    masks (all false and all true among them), N not a multiple of 64.  Rows that did not reset must keep their bits (NaN-filled)."""
+    global _MG
+    import copy
+
+    import _manip_orch_oracle as mo
+    from isaaclab_amd.robots import FRANKA_PANDA
+    from isaaclab_amd.state_feed import StateFeed
+
+    g = _MG = _MG or mo.ManipOrchGolden("lift")
+    rng = np.random.default_rng(seed)
+    N = int(rng.choice([1, 63, 64, 65, 100, 257]))
+    fx = copy.deepcopy(g.fixture)
+    e = fx["env"]
+    pr = {a: tuple(sorted(rng.uniform(-1.5, 1.5, 2).tolist())) for a in mo.AXES}
+    vr = {a: tuple(sorted(rng.uniform(-1.0, 1.0, 2).tolist())) for a in mo.AXES}
+    e["events"]["reset_object_position"]["params"].update(pose_range=pr, velocity_range=vr)
+    q = rng.normal(size=4)
+    e["scene"]["object"]["init_state"].update(pos=rng.normal(size=3).tolist(), rot=(q / np.linalg.norm(q)).tolist(),
+                                              lin_vel=rng.normal(size=3).tolist(), ang_vel=rng.normal(size=3).tolist())
+    thr = [int(x) for x in rng.integers(0, 30, 2)]
+    new_w = [float(x) for x in rng.uniform(-2, 2, 2)]
+    for (name, c), t_, w_ in zip(e["curriculum"].items(), thr, new_w):
+        c["params"].update(num_steps=t_, weight=w_)
+    feed = StateFeed(FRANKA_PANDA, N, "cuda:0", seed=int(rng.integers(0, 1 << 30)), num_snapshots=2)
+    env = ManagerBasedRLEnv(fx, state_feed=feed, own_managers=True, reward_curriculum=True, num_envs=N)
+    st = {k: feed[k].cpu().numpy() for k in ("default_joint_pos", "default_joint_vel", "soft_joint_pos_limits", "soft_joint_vel_limits", "env_origins")}
+    st["default_root_state"], st["default_object_root_state"] = env.default_root_state.cpu().numpy(), env.default_object_root_state.cpu().numpy()
+    events = {k: v for k, v in e["events"].items() if v is not None and v.get("mode") == "reset"}
+    cur = [(c["params"]["term_name"], np.float32(c["params"]["weight"]).item(), c["params"]["num_steps"]) for c in e["curriculum"].values()]
+    weights = {n: np.float32(t["weight"]).item() for n, t in e["rewards"].items() if t is not None}
+    nan = torch.tensor(0x7FC0BEEF, dtype=torch.int32).view(torch.float32).item()
+    keys = ("root_pose", "root_vel", "joint_pos", "joint_vel", "object_root_pose", "object_root_vel")
+    sw = {}
+    for k in keys:
+        env.sim_writes[k].fill_(nan)
+        sw[k] = env.sim_writes[k].cpu().numpy().copy()
+    trig = {"last": np.zeros((2, N), np.int64), "once": np.zeros((2, N), bool)}
+    kinds = ["none", "all", "some", "last", "some", "none", "some"]
+    switched = 0
+    for it, kind in enumerate(kinds):
+        step = int(rng.integers(0, 40))
+        mask = {"none": np.zeros(N, bool), "all": np.ones(N, bool), "last": np.arange(N) == N - 1}.get(kind)
+        mask = rng.random(N) < 0.3 if mask is None else mask
+        u = rng.random((N, 12), np.float32)
+        env._counters[2] = step
+        env.event_manager.get_term("reset_object_position").uniforms = torch.from_numpy(u).cuda()
+        env._orchestrate(torch.from_numpy(mask).cuda(), do_step=False)
+        ids = np.nonzero(mask)[0]
+        before = dict(weights)
+        weights = mo.modify_reward_weight(weights, step, len(ids) > 0, cur)
+        switched += sum(weights[n] != before[n] for n in weights)
+        if len(ids):
+            mo.apply_reset_events(events, ids, step, sw, trig, st, {"reset_object_position": u}, "object")
+        torch.cuda.synchronize()
+        for k in keys:
+            got = env.sim_writes[k].cpu().numpy()
+            assert np.array_equal(got[~mask].view(np.int32), sw[k][~mask].view(np.int32)), f"{it} {kind}: sim_writes[{k}] changed a row that did not reset"
+            assert_close(got[mask], sw[k][mask], FLOAT_TOL, f"{it} {kind} sim_writes[{k}]")
+            sw[k][mask] = got[mask]  # (the kernel's own bits from here on: the next comparison of untouched rows is exact)
+        for k_, t in enumerate(env.event_manager.terms):
+            assert np.array_equal(t.last_triggered_step.cpu().numpy(), trig["last"][k_]) and np.array_equal(t.triggered_once.cpu().numpy(), trig["once"][k_]), (it, t.name)
+        for n, w in weights.items():
+            got = float(env.reward_manager.get_term_cfg(n).weight)
+            assert np.float32(got) == np.float32(w), (it, kind, step, n, got, w)
+    env.close()
+    return f"N={N} thresholds={thr} weight switches={switched}"
+
+
 if __name__ == "__main__":
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     first = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     pose = "pose" in sys.argv[3:]
-    one_case = one_case_pose if pose else one_case
+    one_case = one_case_manip if "manip" in sys.argv[3:] else one_case_pose if pose else one_case
     bad = 0
     for c in range(first, first + cases):
         try:

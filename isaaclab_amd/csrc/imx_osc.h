@@ -10,7 +10,7 @@
 // zero quaternion or a singular mass matrix give NaN / inf in the env's own outputs.
 #pragma once
 #include "../../include/imx.h"
-#include "imx_quat.h"
+#include "imx_task_space.h"
 
 struct OscIO {
     const float* processed_action;  // (N, PA)
@@ -41,28 +41,6 @@ struct OscIO {
 
 #define IMX_OSC_NJ IMX_IK_MAX_JOINTS
 
-// A = L L^T in place (lower triangle), for a symmetric positive definite M x M matrix held in registers.  A matrix that is not positive
-// definite gives NaN / inf.
-template <int M>
-IMX_HD void osc_chol(float (&A)[M][M]) {
-IMX_UNROLL
-    for (int j = 0; j < M; ++j) {
-        float d = A[j][j];
-IMX_UNROLL
-        for (int k = 0; k < j; ++k) d -= A[j][k] * A[j][k];
-        d = sqrtf(d);
-        A[j][j] = d;
-        const float inv = 1.0f / d;
-IMX_UNROLL
-        for (int i = j + 1; i < M; ++i) {
-            float s = A[i][j];
-IMX_UNROLL
-            for (int k = 0; k < j; ++k) s -= A[i][k] * A[j][k];
-            A[i][j] = s * inv;
-        }
-    }
-}
-
 // R^T R z = b for an upper-triangular 6 x 6 factor.  PARTIAL: R is block diagonal (two 3 x 3 blocks); the zero entries are skipped.
 template <bool PARTIAL>
 IMX_HD void osc_rtr_solve(const float (&R)[6][6], float (&b)[6]) {
@@ -84,33 +62,15 @@ IMX_UNROLL
     }
 }
 
-IMX_HD void osc_matrix_from_quat(float r, float i, float j, float k, float (&R)[3][3]) {  // utils/math.py:144-174
-    const float two_s = 2.0f / ((r * r + i * i) + (j * j + k * k));
-    R[0][0] = 1.0f - two_s * (j * j + k * k); R[0][1] = two_s * (i * j - k * r); R[0][2] = two_s * (i * k + j * r);
-    R[1][0] = two_s * (i * j + k * r); R[1][1] = 1.0f - two_s * (i * i + k * k); R[1][2] = two_s * (j * k - i * r);
-    R[2][0] = two_s * (i * k - j * r); R[2][1] = two_s * (j * k + i * r); R[2][2] = 1.0f - two_s * (i * i + j * j);
-}
-
-// quat_rotate (sign +1) / quat_rotate_inverse (sign -1) (utils/math.py:583-625): a +- b + c
-IMX_HD void osc_quat_rotate(float4 q, float sign, float vx, float vy, float vz, float& ox, float& oy, float& oz) {
-    const float w = q.x, x = q.y, y = q.z, z = q.w;
-    const float f = 2.0f * (w * w) - 1.0f;
-    const float bx = (y * vz - z * vy) * w * 2.0f, by = (z * vx - x * vz) * w * 2.0f, bz = (x * vy - y * vx) * w * 2.0f;
-    const float d = (x * vx + y * vy) + z * vz;
-    ox = (vx * f + sign * bx) + x * d * 2.0f;
-    oy = (vy * f + sign * by) + y * d * 2.0f;
-    oz = (vz * f + sign * bz) + z * d * 2.0f;
-}
-
 // DEC: imx_osc_decoupling of the cfg; NULLSP: cfg.nullspace_position (with DEC == full only).  Compile-time, so that an instantiation
 // holds only the matrices its cfg needs.
 template <int DEC, bool NULLSP>
 IMX_HD void osc_env(const imx_osc_t& c, int64_t e, int mode, const OscIO& io) {
-    // ---- _compute_ee_pose (task_space_actions.py:597-615)
+    // ---- _compute_ee_pose (task_space_actions.py:597-615).  task_frame, apply_delta_pose and frame_jacobian of imx_task_space.h are
+    // written out in this function: through the helpers the same arithmetic is scheduled and allocated differently (225 / 180 / 169 /
+    // 114 VGPRs against 233 / 173 / 174 / 116), and the shipped cfg's mode 2 replayed from a graph measured 0.02 to 0.05 us slower (NOTES.md)
     const float4 rq = make_float4(io.root_quat[e * 4], io.root_quat[e * 4 + 1], io.root_quat[e * 4 + 2], io.root_quat[e * 4 + 3]);
-    // quat_inv = normalize(conjugate) (utils/math.py:239-248, 82-92: x / norm.clamp(min=1e-9))
-    const float rn = fmaxf(sqrtf((rq.x * rq.x + rq.y * rq.y) + (rq.z * rq.z + rq.w * rq.w)), 1.0e-9f);
-    const float4 q10 = make_float4(rq.x / rn, -rq.y / rn, -rq.z / rn, -rq.w / rn);
+    const float4 q10 = quat_inv(rq);
     const int64_t b = e * io.num_bodies + c.body_idx;
     const float4 bq = make_float4(io.body_quat[b * 4], io.body_quat[b * 4 + 1], io.body_quat[b * 4 + 2], io.body_quat[b * 4 + 3]);
     // subtract_frame_transforms (utils/math.py:785-816)
@@ -194,11 +154,11 @@ IMX_UNROLL
                     lz = io.body_lin_vel[b * 3 + 2] - io.root_lin_vel[e * 3 + 2];
         const float wx = io.body_ang_vel[b * 3] - io.root_ang_vel[e * 3], wy = io.body_ang_vel[b * 3 + 1] - io.root_ang_vel[e * 3 + 1],
                     wz = io.body_ang_vel[b * 3 + 2] - io.root_ang_vel[e * 3 + 2];
-        osc_quat_rotate(rq, -1.0f, lx, ly, lz, vel[0], vel[1], vel[2]);
-        osc_quat_rotate(rq, -1.0f, wx, wy, wz, vel[3], vel[4], vel[5]);
+        quat_rotate_ref(rq, -1.0f, lx, ly, lz, vel[0], vel[1], vel[2]);
+        quat_rotate_ref(rq, -1.0f, wx, wy, wz, vel[3], vel[4], vel[5]);
         if (c.has_offset) {  // v += w x r, r = quat_rotate(ee_quat_b_no_offset, offset_pos)
             float r0, r1, r2;
-            osc_quat_rotate(eq0, 1.0f, c.offset_pos[0], c.offset_pos[1], c.offset_pos[2], r0, r1, r2);
+            quat_rotate_ref(eq0, 1.0f, c.offset_pos[0], c.offset_pos[1], c.offset_pos[2], r0, r1, r2);
             vel[0] += vel[4] * r2 - vel[5] * r1;
             vel[1] += vel[5] * r0 - vel[3] * r2;
             vel[2] += vel[3] * r1 - vel[4] * r0;
@@ -207,11 +167,8 @@ IMX_UNROLL
     // compute_pose_error (utils/math.py:820-867, "axis_angle"), des_ee_acc_b = Kp e + Kd (-v) (operational_space.py:408-423)
     float acc[6];
     {
-        float er[6] = {px - ex, py - ey, pz - ez, 0.0f, 0.0f, 0.0f};
-        const float4 conj = make_float4(eq.x, -eq.y, -eq.z, -eq.w);
-        const float nrm = quat_mul_ref(eq, conj).x;
-        const float4 inv = make_float4(conj.x / nrm, conj.y / nrm, conj.z / nrm, conj.w / nrm);
-        axis_angle_from_quat_ref(quat_mul_ref(qd, inv), er[3], er[4], er[5]);
+        float er[6];
+        pose_error(ex, ey, ez, eq, px, py, pz, qd, true, er);
 IMX_UNROLL
         for (int i = 0; i < 6; ++i) acc[i] = kp[i] * er[i] + kd[i] * (-vel[i]);
     }
@@ -220,8 +177,8 @@ IMX_UNROLL
     float Jm[6][IMX_OSC_NJ];
     {
         float R[3][3], Ro[3][3];
-        osc_matrix_from_quat(q10.x, q10.y, q10.z, q10.w, R);
-        osc_matrix_from_quat(c.offset_rot[0], c.offset_rot[1], c.offset_rot[2], c.offset_rot[3], Ro);
+        matrix_from_quat(q10.x, q10.y, q10.z, q10.w, R);
+        matrix_from_quat(c.offset_rot[0], c.offset_rot[1], c.offset_rot[2], c.offset_rot[3], Ro);
         const float ox = c.offset_pos[0], oy = c.offset_pos[1], oz = c.offset_pos[2];
         const float* jrow = io.jacobians + (e * io.NB + c.jacobi_body_idx) * 6 * io.ND;
 IMX_UNROLL
@@ -301,7 +258,7 @@ IMX_UNROLL
                 u[r] = s;
             }
         }
-        osc_chol<IMX_OSC_NJ>(L);
+        chol<IMX_OSC_NJ>(L);
         // Y = L^-1 J^T (n x 6): J M^-1 J^T = Y^T Y.  Its Cholesky factor R (Y^T Y = R^T R) is taken from Y by a Gram-Schmidt sweep, column
         // by column, instead of from the product: the product squares Y's condition number, and on a near-singular task space a pivot of
         // the squared matrix drowns in its rounding (a negative square root); R[i][i] = ||column|| cannot.  Partial decoupling factors
@@ -405,24 +362,20 @@ static inline const char* imx_osc_check(const imx_osc_t* c, int64_t N, int mode,
     if (c->pose_type != IMX_OSC_POSE_ABS && c->pose_type != IMX_OSC_POSE_REL) return "unknown pose type";
     if (c->impedance_mode < IMX_OSC_FIXED || c->impedance_mode > IMX_OSC_VARIABLE) return "unknown impedance mode";
     if (c->decoupling < IMX_OSC_DECOUPLING_NONE || c->decoupling > IMX_OSC_DECOUPLING_PARTIAL) return "unknown decoupling";
-    if (c->num_joints < 1 || c->num_joints > IMX_IK_MAX_JOINTS) return "num_joints outside [1, 8]";
+    if (const char* why = task_space_check(*c, mode, io.num_bodies, io.NB, io.ND, c->nullspace_position ? io.J : 0)) return why;
     if (c->nullspace_position && c->decoupling != IMX_OSC_DECOUPLING_FULL) return "null-space control without full decoupling (it needs an SVD)";
     if (c->nullspace_position && c->num_joints <= 6) return "null-space control on six joints or fewer";
     if (!io.root_pos || !io.root_quat || !io.body_pos || !io.body_quat || !io.command_state) return "null argument";
-    if (io.num_bodies <= 0 || io.num_bodies >= lim || c->body_idx < 0 || c->body_idx >= io.num_bodies) return "body_idx outside [0, num_bodies)";
     if (io.ld_cmd < IMX_OSC_CMD_WIDTH || io.ld_cmd >= lim) return "ld_cmd smaller than 25";
     if (mode & 1) {
         if (!io.processed_action) return "null processed action";
-        if (io.PA <= 0 || io.PA >= lim) return "processed columns outside [0, PA)";
-        const int pw = c->pose_type == IMX_OSC_POSE_ABS ? 7 : 6;
-        if (c->pose_col < 0 || c->pose_col + pw > io.PA) return "processed columns outside [0, PA)";
-        if (c->has_wrench && (c->wrench_col < 0 || c->wrench_col + 6 > io.PA)) return "processed columns outside [0, PA)";
-        if (c->impedance_mode != IMX_OSC_FIXED && (c->stiffness_col < 0 || c->stiffness_col + 6 > io.PA)) return "processed columns outside [0, PA)";
-        if (c->impedance_mode == IMX_OSC_VARIABLE && (c->damping_ratio_col < 0 || c->damping_ratio_col + 6 > io.PA)) return "processed columns outside [0, PA)";
+        if (!processed_cols_ok(io.PA, c->pose_col, c->pose_type == IMX_OSC_POSE_ABS ? 7 : 6) || (c->has_wrench && !processed_cols_ok(io.PA, c->wrench_col, 6)) ||
+            (c->impedance_mode != IMX_OSC_FIXED && !processed_cols_ok(io.PA, c->stiffness_col, 6)) ||
+            (c->impedance_mode == IMX_OSC_VARIABLE && !processed_cols_ok(io.PA, c->damping_ratio_col, 6)))
+            return "processed columns outside [0, PA)";
     }
     if (mode & 2) {
         if (!io.jacobians || !io.joint_efforts || !io.root_lin_vel || !io.root_ang_vel || !io.body_lin_vel || !io.body_ang_vel) return "null argument";
-        if (io.NB <= 0 || io.NB >= lim || c->jacobi_body_idx < 0 || c->jacobi_body_idx >= io.NB) return "jacobi_body_idx outside [0, NB)";
         if (io.ND <= 0 || io.ND >= lim) return "bad ND";
         if (io.ld_eff < c->num_joints || io.ld_eff >= lim) return "ld_eff smaller than num_joints";
         const bool dyn = c->decoupling != IMX_OSC_DECOUPLING_NONE, jnt = c->nullspace_position != 0;
@@ -431,12 +384,8 @@ static inline const char* imx_osc_check(const imx_osc_t* c, int64_t N, int mode,
         if ((dyn || c->gravity_compensation) && (io.NM <= 0 || io.NM >= 32768)) return "bad NM";
         if (jnt && (!io.joint_pos || !io.joint_vel || !io.nullspace_target)) return "null joint state or null-space target";
         if (jnt && (io.J <= 0 || io.J >= lim)) return "bad J";
-        for (int j = 0; j < c->num_joints; ++j) {
-            if (c->joint_ids[j] < 0) return "joint id outside [0, J)";
-            if (jnt && c->joint_ids[j] >= io.J) return "joint id outside [0, J)";
+        for (int j = 0; j < c->num_joints; ++j)
             if ((dyn || c->gravity_compensation) && c->joint_ids[j] >= io.NM) return "mass-matrix row outside [0, NM)";
-            if (c->jacobi_joint_ids[j] < 0 || c->jacobi_joint_ids[j] >= io.ND) return "Jacobian column outside [0, ND)";
-        }
     }
     return nullptr;
 }

@@ -163,12 +163,8 @@ IMX_DEV void pose_command_env(int64_t N, int64_t e, const PoseCmdCfg& c, float d
             cw[0] = wx; cw[1] = wy; cw[2] = wz; cw[3] = wq.x; cw[4] = wq.y; cw[5] = wq.z; cw[6] = wq.w;
             const size_t b = (size_t)e * c.num_bodies + c.body_idx;
             mpos = norm3(body_pos[b * 3] - wx, body_pos[b * 3 + 1] - wy, body_pos[b * 3 + 2] - wz);
-            // source_quat_norm = quat_mul(q, conj q)[:, 0]; source_quat_inv = conj q / norm; quat_error = quat_mul(body quat, inv)
-            const float4 conj = make_float4(wq.x, -wq.y, -wq.z, -wq.w);
-            const float nrm = quat_mul_ref(wq, conj).x;
-            const float4 inv = make_float4(conj.x / nrm, conj.y / nrm, conj.z / nrm, conj.w / nrm);
             const float4 bq = make_float4(body_quat[b * 4], body_quat[b * 4 + 1], body_quat[b * 4 + 2], body_quat[b * 4 + 3]);
-            mrot = axis_angle_magnitude(quat_mul_ref(bq, inv));
+            mrot = axis_angle_magnitude(quat_error_ref(bq, wq));
             tl -= dt;
             resample = tl <= 0.0f;
         }

@@ -26,6 +26,17 @@ IMX_HD void quat_apply(float w, float x, float y, float z, float vx, float vy, f
     oz = vz + w * tz + (x * ty - y * tx);
 }
 
+// quat_rotate (sign +1) / quat_rotate_inverse (sign -1) (utils/math.py:583-625): a +- b + c.  Not quat_apply: the two round differently.
+IMX_HD void quat_rotate_ref(float4 q, float sign, float vx, float vy, float vz, float& ox, float& oy, float& oz) {
+    const float w = q.x, x = q.y, y = q.z, z = q.w;
+    const float f = 2.0f * (w * w) - 1.0f;
+    const float bx = (y * vz - z * vy) * w * 2.0f, by = (z * vx - x * vz) * w * 2.0f, bz = (x * vy - y * vx) * w * 2.0f;
+    const float d = (x * vx + y * vy) + z * vz;
+    ox = (vx * f + sign * bx) + x * d * 2.0f;
+    oy = (vy * f + sign * by) + y * d * 2.0f;
+    oz = (vz * f + sign * bz) + z * d * 2.0f;
+}
+
 // quat_mul (utils/math.py:464-500): the reference's eight-product form with its association, quaternions w, x, y, z in .x .. .w
 IMX_HD float4 quat_mul_ref(float4 a, float4 b) {
     const float w1 = a.x, x1 = a.y, y1 = a.z, z1 = a.w, w2 = b.x, x2 = b.y, y2 = b.z, z2 = b.w;
@@ -36,6 +47,13 @@ IMX_HD float4 quat_mul_ref(float4 a, float4 b) {
     const float qq = 0.5f * (xx + (z1 - x1) * (x2 - y2));
     return make_float4(qq - ww + (z1 - y1) * (y2 - z2), qq - xx + (x1 + w1) * (x2 + w2), qq - yy + (w1 - x1) * (y2 + z2),
                        qq - zz + (z1 + y1) * (w2 - x2));
+}
+
+// quat_error of compute_pose_error (utils/math.py:820-867): target * conj(source) / (source * conj(source)).w
+IMX_HD float4 quat_error_ref(float4 target, float4 source) {
+    const float4 conj = make_float4(source.x, -source.y, -source.z, -source.w);
+    const float nrm = quat_mul_ref(source, conj).x;
+    return quat_mul_ref(target, make_float4(conj.x / nrm, conj.y / nrm, conj.z / nrm, conj.w / nrm));
 }
 
 // axis_angle_from_quat (utils/math.py:646-675) step by step: the w < 0 flip (q * (1 - 2 (w < 0))), half = atan2(||xyz||, w),

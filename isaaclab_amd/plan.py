@@ -106,28 +106,65 @@ _IK_WIDTH = {("position", False): 3, ("position", True): 3, ("pose", True): 6, (
 
 
 @dataclasses.dataclass
-class IkTerm:
-    """One ``DifferentialInverseKinematicsAction`` as resolved by its ``__init__`` (task_space_actions.py:53-121): the parameters of
-    ``imx_diff_ik_t``.  They travel beside the plan, not in its blob."""
+class TaskSpaceTerm:
+    """What the task-space action terms share: the controlled frame, its Jacobian block and the term's columns."""
 
     name: str
-    command_type: str  # "position" | "pose"
-    use_relative_mode: bool
-    ik_method: str  # "dls" | "trans"
-    lambda_val: float
-    k_val: float
     offset_pos: tuple | None  # cfg.body_offset, or None
     offset_rot: tuple | None
     body_name: str
     body_idx: int
     jacobi_body_idx: int
-    joint_ids: list
+    joint_ids: list  # columns of joint_pos / joint_vel (OSC: also rows and columns of the mass matrix, task_space_actions.py:571-574)
     jacobi_joint_ids: list
     action_col: int  # first raw column
     processed_col: int  # first processed column
-    width: int  # raw = processed columns: 3, 6 or 7
+    width: int  # action_dim: raw = processed columns
     scale: list  # per column
-    clip: list | None  # per column (lo, hi), or None
+    clip: list | None  # per column (lo, hi); IK: None without a cfg.clip; OSC: +-inf on the columns the reference does not clamp
+
+
+def _match_frame(tcfg: dict, robot: RobotSpec, joint_names, body_label: str):
+    """The joint and body matching of both ``__init__``: ``(joint_ids, joint names, body_idx, body name)``."""
+    joint_ids, jn = resolve_matching_names(tcfg["joint_names"], list(joint_names if joint_names is not None else robot.joint_names))
+    body_ids, body_names = resolve_matching_names(tcfg["body_name"], list(robot.body_names))
+    if len(body_ids) != 1:
+        raise ValueError(f"Expected one match for the {body_label}: {tcfg['body_name']}. Found {len(body_ids)}: {body_names}.")
+    return joint_ids, jn, body_ids[0], body_names[0]
+
+
+def _frame_fields(name: str, robot: RobotSpec, kernel: str, joint_ids, body_idx, body_name) -> dict:
+    """The joint-count limit and the Jacobian's row and columns (task_space_actions.py:72-77, 266-274): the index fields of a
+    ``TaskSpaceTerm``."""
+    n = len(joint_ids)
+    if n > IK_MAX_JOINTS:
+        raise NotImplementedError(f"action term '{name}': {n} controlled joints; the {kernel} kernel takes at most {IK_MAX_JOINTS}")
+    if robot.fixed_base:  # the Jacobian of a fixed base has no row for the root body and no root columns
+        jb, jcols = body_idx - 1, list(joint_ids)
+        if jb < 0:
+            raise ValueError(f"action term '{name}': body '{body_name}' is the root of a fixed-base articulation: it has no Jacobian row")
+    else:
+        jb, jcols = body_idx, [i + 6 for i in joint_ids]
+    return dict(body_name=body_name, body_idx=int(body_idx), jacobi_body_idx=int(jb), joint_ids=[int(i) for i in joint_ids],
+                jacobi_joint_ids=[int(i) for i in jcols])
+
+
+def _body_offset(tcfg: dict) -> dict:
+    off = tcfg.get("body_offset")
+    return dict(offset_pos=None if off is None else tuple(float(v) for v in off.get("pos", (0.0, 0.0, 0.0))),
+                offset_rot=None if off is None else tuple(float(v) for v in off.get("rot", (1.0, 0.0, 0.0, 0.0))))
+
+
+@dataclasses.dataclass
+class IkTerm(TaskSpaceTerm):
+    """One ``DifferentialInverseKinematicsAction`` as resolved by its ``__init__`` (task_space_actions.py:53-121): the parameters of
+    ``imx_diff_ik_t``.  They travel beside the plan, not in its blob."""
+
+    command_type: str  # "position" | "pose"
+    use_relative_mode: bool
+    ik_method: str  # "dls" | "trans"
+    lambda_val: float
+    k_val: float
 
 
 def resolve_ik_term(name: str, tcfg: dict, robot: RobotSpec, action_col: int = 0, processed_col: int = 0, joint_names=None) -> IkTerm:
@@ -150,20 +187,8 @@ def resolve_ik_term(name: str, tcfg: dict, robot: RobotSpec, action_col: int = 0
                                   "'dls' and 'trans' are")
     params = {"trans": {"k_val": 1.0}, "dls": {"lambda_val": 0.01}}[method]
     params.update(ctrl.get("ik_params") or {})
-    joint_ids, jn = resolve_matching_names(tcfg["joint_names"], list(joint_names if joint_names is not None else robot.joint_names))
-    body_ids, body_names = resolve_matching_names(tcfg["body_name"], list(robot.body_names))
-    if len(body_ids) != 1:
-        raise ValueError(f"Expected one match for the body name: {tcfg['body_name']}. Found {len(body_ids)}: {body_names}.")
-    n = len(joint_ids)
-    if n > IK_MAX_JOINTS:
-        raise NotImplementedError(f"action term '{name}': {n} controlled joints; the differential-IK kernel takes at most {IK_MAX_JOINTS}")
-    body_idx = body_ids[0]
-    if robot.fixed_base:  # the Jacobian of a fixed base has no row for the root body and no root columns (:72-77)
-        jb, jcols = body_idx - 1, list(joint_ids)
-        if jb < 0:
-            raise ValueError(f"action term '{name}': body '{body_names[0]}' is the root of a fixed-base articulation: it has no Jacobian row")
-    else:
-        jb, jcols = body_idx, [i + 6 for i in joint_ids]
+    joint_ids, jn, body_idx, body_name = _match_frame(tcfg, robot, joint_names, "body name")
+    frame = _frame_fields(name, robot, "differential-IK", joint_ids, body_idx, body_name)
     width = _IK_WIDTH[(command_type, relative)]
     scale = tcfg.get("scale", 1.0)
     if isinstance(scale, (int, float)):
@@ -183,20 +208,16 @@ def resolve_ik_term(name: str, tcfg: dict, robot: RobotSpec, action_col: int = 0
             if i >= width:
                 raise IndexError(f"action term '{name}': clip key matches joint {i} of the term, past its {width} action columns")
             clip[i] = (float(v[0]), float(v[1]))
-    off = tcfg.get("body_offset")
     return IkTerm(name=name, command_type=command_type, use_relative_mode=relative, ik_method=method,
-                  lambda_val=float(params.get("lambda_val", 0.01)), k_val=float(params.get("k_val", 1.0)),
-                  offset_pos=None if off is None else tuple(float(v) for v in off.get("pos", (0.0, 0.0, 0.0))),
-                  offset_rot=None if off is None else tuple(float(v) for v in off.get("rot", (1.0, 0.0, 0.0, 0.0))),
-                  body_name=body_names[0], body_idx=int(body_idx), jacobi_body_idx=int(jb), joint_ids=[int(i) for i in joint_ids],
-                  jacobi_joint_ids=[int(i) for i in jcols], action_col=action_col, processed_col=processed_col, width=width, scale=scale, clip=clip)
+                  lambda_val=float(params.get("lambda_val", 0.01)), k_val=float(params.get("k_val", 1.0)), **frame, **_body_offset(tcfg),
+                  action_col=action_col, processed_col=processed_col, width=width, scale=scale, clip=clip)
 
 
 _OSC_TARGET_WIDTH = {"pose_abs": 7, "pose_rel": 6, "wrench_abs": 6}  # OperationalSpaceController.__init__ (operational_space.py:50-61)
 
 
 @dataclasses.dataclass
-class OscTerm:
+class OscTerm(TaskSpaceTerm):
     """One ``OperationalSpaceControllerAction`` as resolved by its ``__init__`` (task_space_actions.py:248-378) and its controller's
     (operational_space.py:34-140): the parameters of ``imx_osc_t``.  They travel beside the plan, not in its blob."""
 
@@ -215,22 +236,10 @@ class OscTerm:
     motion_damping_ratio: list  # 6
     motion_stiffness_limits: tuple
     motion_damping_ratio_limits: tuple
-    offset_pos: tuple | None  # cfg.body_offset, or None
-    offset_rot: tuple | None
-    body_name: str
-    body_idx: int
-    jacobi_body_idx: int
-    joint_ids: list  # columns of joint_pos / joint_vel, rows and columns of the mass matrix (:571-574)
-    jacobi_joint_ids: list
-    action_col: int  # first raw column
-    processed_col: int  # first processed column
-    width: int  # action_dim: raw = processed columns
     pose_idx: int  # first column of each part inside the term (_resolve_command_indexes :504-537); None = absent
     wrench_idx: int | None
     stiffness_idx: int | None
     damping_ratio_idx: int | None
-    scale: list  # per column (_preprocess_actions :664-700)
-    clip: list  # per column (lo, hi); +-inf on the columns the reference does not clamp
 
     @property
     def pose_type(self) -> str:
@@ -272,10 +281,7 @@ def resolve_osc_term(name: str, tcfg: dict, robot: RobotSpec, action_col: int = 
         raise ValueError("Invalid value for nullspace joint pos targets.")
     if null_ctrl not in ("none", "position"):
         raise ValueError(f"Invalid null-space control method: {null_ctrl}.")
-    joint_ids, _ = resolve_matching_names(tcfg["joint_names"], list(joint_names if joint_names is not None else robot.joint_names))
-    body_ids, body_names = resolve_matching_names(tcfg["body_name"], list(robot.body_names))
-    if len(body_ids) != 1:
-        raise ValueError(f"Expected one match for the ee body name: {tcfg['body_name']}. Found {len(body_ids)}: {body_names}.")
+    joint_ids, _, body_idx, body_name = _match_frame(tcfg, robot, joint_names, "ee body name")
     n = len(joint_ids)
     if null_ctrl != "none" and n <= 6:  # (operational_space.py:491-493, raised by the first compute())
         raise ValueError("Null-space control is only applicable for redundant manipulators.")
@@ -298,15 +304,7 @@ def resolve_osc_term(name: str, tcfg: dict, robot: RobotSpec, action_col: int = 
         raise NotImplementedError(f"action term '{name}': nullspace_control 'position' without full inertial decoupling takes torch.pinverse of "
                                   "the Jacobian, an SVD inside the kernel (as ik_method 'pinv'); it is on the fused path with "
                                   "inertial_dynamics_decoupling=True, partial_inertial_dynamics_decoupling=False only")
-    if n > IK_MAX_JOINTS:
-        raise NotImplementedError(f"action term '{name}': {n} controlled joints; the operational-space kernel takes at most {IK_MAX_JOINTS}")
-    body_idx = body_ids[0]
-    if robot.fixed_base:  # the Jacobian of a fixed base has no row for the root body and no root columns (:266-274)
-        jb, jcols = body_idx - 1, list(joint_ids)
-        if jb < 0:
-            raise ValueError(f"action term '{name}': body '{body_names[0]}' is the root of a fixed-base articulation: it has no Jacobian row")
-    else:
-        jb, jcols = body_idx, [i + 6 for i in joint_ids]
+    frame = _frame_fields(name, robot, "operational-space", joint_ids, body_idx, body_name)
     # ---- _resolve_command_indexes and _preprocess_actions: per-column scale and clamp
     idx = {"pose": None, "wrench_abs": None, "stiffness": None, "damping_ratio": None}
     scale, clip, col = [], [], 0
@@ -330,7 +328,6 @@ def resolve_osc_term(name: str, tcfg: dict, robot: RobotSpec, action_col: int = 
             scale += [float(tcfg.get("damping_ratio_scale", 1.0))] * 6
             clip += [d_lim] * 6
             col += 6
-    off = tcfg.get("body_offset")
     return OscTerm(name=name, target_types=targets, impedance_mode=mode, decoupling=decoupling,
                    gravity_compensation=bool(ctrl.get("gravity_compensation", False)), nullspace_control=null_ctrl,
                    nullspace_joint_pos_target=null_target, nullspace_stiffness=float(ctrl.get("nullspace_stiffness", 10.0)),
@@ -339,11 +336,8 @@ def resolve_osc_term(name: str, tcfg: dict, robot: RobotSpec, action_col: int = 
                    contact_wrench_control_axes=_six(name, "contact_wrench_control_axes_task", ctrl.get("contact_wrench_control_axes_task", (0,) * 6), False),
                    motion_stiffness=_six(name, "motion_stiffness_task", ctrl.get("motion_stiffness_task", 100.0)),
                    motion_damping_ratio=_six(name, "motion_damping_ratio_task", ctrl.get("motion_damping_ratio_task", 1.0)),
-                   motion_stiffness_limits=k_lim, motion_damping_ratio_limits=d_lim,
-                   offset_pos=None if off is None else tuple(float(v) for v in off.get("pos", (0.0, 0.0, 0.0))),
-                   offset_rot=None if off is None else tuple(float(v) for v in off.get("rot", (1.0, 0.0, 0.0, 0.0))),
-                   body_name=body_names[0], body_idx=int(body_idx), jacobi_body_idx=int(jb), joint_ids=[int(i) for i in joint_ids],
-                   jacobi_joint_ids=[int(i) for i in jcols], action_col=action_col, processed_col=processed_col, width=col,
+                   motion_stiffness_limits=k_lim, motion_damping_ratio_limits=d_lim, **frame, **_body_offset(tcfg),
+                   action_col=action_col, processed_col=processed_col, width=col,
                    pose_idx=idx["pose"], wrench_idx=idx["wrench_abs"], stiffness_idx=idx["stiffness"], damping_ratio_idx=idx["damping_ratio"],
                    scale=scale, clip=clip)
 
@@ -940,11 +934,8 @@ class PlanCompiler:
             if cname in _BINARY_ACTIONS:
                 self._binary_action(name, cls, tcfg)
                 continue
-            if cls == _IK_ACTION:
-                self._ik_action(name, cls, tcfg)
-                continue
-            if cls == _OSC_ACTION:
-                self._osc_action(name, cls, tcfg)
+            if cls in (_IK_ACTION, _OSC_ACTION):
+                self._task_space_action(name, cls, tcfg)
                 continue
             if cname not in _JOINT_ACTIONS:
                 raise NotImplementedError(f"action term '{name}': class {cls} is not on the fused path")
@@ -1012,69 +1003,42 @@ class PlanCompiler:
             self.action_dim += dim
             self.processed_dim += dim
 
-    def _ik_action(self, name: str, cls: str, tcfg: dict) -> None:
-        """``DifferentialInverseKinematicsAction`` (task_space_actions.py:53-166): raw -> processed is ``raw * scale`` and an optional
-        clip, which the A_JOINT_AFFINE record already does (offset 0, no flag but the clip's); the controller's parameters go to
-        ``ik_terms``.  The record's id list only has to pass the blob validation: without the default-offset, to-limits or EMA flag
-        ``action_process_element`` loads the id and never indexes a joint array with it, so it is joint 0 for every column."""
-        if self.osc_terms:
-            raise NotImplementedError(f"action term '{name}': a DifferentialInverseKinematicsAction beside the OperationalSpaceControllerAction "
-                                      f"'{self.osc_terms[0].name}'; the fused path runs one task-space term per env")
-        if self.ik_terms:
-            raise NotImplementedError(f"action term '{name}': a second DifferentialInverseKinematicsAction (after '{self.ik_terms[0].name}'); "
-                                      "the fused path runs one per env")
+    def _task_space_action(self, name: str, cls: str, tcfg: dict) -> None:
+        """``DifferentialInverseKinematicsAction`` (task_space_actions.py:53-166) and ``OperationalSpaceControllerAction`` (:248-378,
+        664-700): raw -> processed is a per-column scale and an optional clip (IK: cfg.clip; OSC: the clamp of the stiffness and
+        damping-ratio columns, +-inf on the others), which the A_JOINT_AFFINE record already does (offset 0, no flag but the clip's);
+        the controller's parameters go to ``ik_terms`` / ``osc_terms``.  The record's id list only has to pass the blob validation:
+        without the default-offset, to-limits or EMA flag ``action_process_element`` loads the id and never indexes a joint array
+        with it, so it is joint 0 for every column."""
+        ik = cls == _IK_ACTION
+        a, mine, other = ("a", "DifferentialInverseKinematicsAction", "OperationalSpaceControllerAction") if ik else \
+            ("an", "OperationalSpaceControllerAction", "DifferentialInverseKinematicsAction")
+        terms, others = (self.ik_terms, self.osc_terms) if ik else (self.osc_terms, self.ik_terms)
+        if others:
+            raise NotImplementedError(f"action term '{name}': {a} {mine} beside the {other} '{others[0].name}'; the fused path runs one "
+                                      "task-space term per env")
+        if terms:
+            raise NotImplementedError(f"action term '{name}': a second {mine} (after '{terms[0].name}'); the fused path runs one per env")
         blob = self.blob
-        ik = resolve_ik_term(name, tcfg, self.robot, action_col=self.action_dim, processed_col=self.processed_dim, joint_names=self.entities.joint_names)
-        dim = ik.width
+        term = (resolve_ik_term if ik else resolve_osc_term)(name, tcfg, self.robot, action_col=self.action_dim, processed_col=self.processed_dim,
+                                                             joint_names=self.entities.joint_names)
+        dim = term.width
         rec = dict(op=A_JOINT_AFFINE, ids_off=blob.ints([0] * dim), nids=dim, out=self.action_dim, dim=dim, p1=0.0)
         if self.processed_dim != self.action_dim:
             rec["p2"] = int(self.processed_dim)
-        if len(set(ik.scale)) == 1:
-            rec["p0"] = ik.scale[0]
+        if len(set(term.scale)) == 1:
+            rec["p0"] = term.scale[0]
         else:
-            rec["aux0"] = blob.floats(ik.scale)
+            rec["aux0"] = blob.floats(term.scale)
         flags = 0
-        if ik.clip is not None:
-            rec["ids2_off"] = blob.floats([x for lo_hi in ik.clip for x in lo_hi])
+        if term.clip is not None and (ik or any(lo_hi != (-math.inf, math.inf) for lo_hi in term.clip)):
+            rec["ids2_off"] = blob.floats([x for lo_hi in term.clip for x in lo_hi])
             rec["nids2"] = 2 * dim
             flags |= F_ACT_CLIP
         rec["flags"] = flags
         self.act_recs.append(_rec(**rec))
         self.action_terms.append(Term(name, cls, A_JOINT_AFFINE, dict(tcfg), dim=dim, processed_col=self.processed_dim, processed_dim=dim))
-        self.ik_terms.append(ik)
-        self.action_dim += dim
-        self.processed_dim += dim
-
-    def _osc_action(self, name: str, cls: str, tcfg: dict) -> None:
-        """``OperationalSpaceControllerAction`` (task_space_actions.py:248-378, 664-700): raw -> processed is a per-column scale and a
-        clamp on the stiffness and damping-ratio columns, which the A_JOINT_AFFINE record already does with a scale table and a clip
-        table (offset 0, +-inf on the unclamped columns); the controller's parameters go to ``osc_terms``.  The record's id list is
-        joint 0 for every column, as for the differential-IK term."""
-        if self.osc_terms:
-            raise NotImplementedError(f"action term '{name}': a second OperationalSpaceControllerAction (after '{self.osc_terms[0].name}'); "
-                                      "the fused path runs one per env")
-        if self.ik_terms:
-            raise NotImplementedError(f"action term '{name}': an OperationalSpaceControllerAction beside the DifferentialInverseKinematicsAction "
-                                      f"'{self.ik_terms[0].name}'; the fused path runs one task-space term per env")
-        blob = self.blob
-        osc = resolve_osc_term(name, tcfg, self.robot, action_col=self.action_dim, processed_col=self.processed_dim, joint_names=self.entities.joint_names)
-        dim = osc.width
-        rec = dict(op=A_JOINT_AFFINE, ids_off=blob.ints([0] * dim), nids=dim, out=self.action_dim, dim=dim, p1=0.0)
-        if self.processed_dim != self.action_dim:
-            rec["p2"] = int(self.processed_dim)
-        if len(set(osc.scale)) == 1:
-            rec["p0"] = osc.scale[0]
-        else:
-            rec["aux0"] = blob.floats(osc.scale)
-        flags = 0
-        if any(lo_hi != (-math.inf, math.inf) for lo_hi in osc.clip):
-            rec["ids2_off"] = blob.floats([x for lo_hi in osc.clip for x in lo_hi])
-            rec["nids2"] = 2 * dim
-            flags |= F_ACT_CLIP
-        rec["flags"] = flags
-        self.act_recs.append(_rec(**rec))
-        self.action_terms.append(Term(name, cls, A_JOINT_AFFINE, dict(tcfg), dim=dim, processed_col=self.processed_dim, processed_dim=dim))
-        self.osc_terms.append(osc)
+        terms.append(term)
         self.action_dim += dim
         self.processed_dim += dim
 

@@ -18,6 +18,9 @@ import struct
 import numpy as np
 import torch
 
+import _task_space_cases as tsc
+from _task_space_cases import SENTINEL, calls, host_compiler, schedule, sentinels_intact  # noqa: F401 (the tests use ikc.*)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
 ROOT = os.path.dirname(HERE)
@@ -138,38 +141,12 @@ def run_oracle(g: IkGolden) -> float:
 
 
 # ---------------------------------------------------------------------------------------------------- the host program
-def host_compiler():
-    import shutil
-
-    for c in (os.environ.get("CXX"), "c++", "g++", "clang++"):
-        if c and shutil.which(c):
-            return shutil.which(c)
-    return None
-
-
 def build_host_program(out_dir: str) -> str:
-    import subprocess
-
-    exe = os.path.join(out_dir, "diff_ik_host")
-    subprocess.check_call([host_compiler(), "-O2", "-std=c++17", "-ffp-contract=off", os.path.join(ROOT, "tools", "diff_ik_host.cpp"), "-o", exe])
-    return exe
+    return tsc.build_host_program("diff_ik_host", out_dir)
 
 
 def processed_full(g: IkGolden, t: int, PA: int | None = None):
-    """(N, PA) processed action with the recorded fp32 columns of the term at its processed column."""
-    ik = g.ik
-    PA = ik.processed_col + ik.width if PA is None else PA
-    p = torch.zeros(g.N, PA)
-    p[:, ik.processed_col:ik.processed_col + ik.width] = torch.from_numpy(np.ascontiguousarray(g.ref(f"step{t}/processed_actions", "f32")))
-    return p.contiguous()
-
-
-def schedule(g: IkGolden):
-    """The env's schedule: per step mode 1 on substep 0's state, then mode 2 on every substep's."""
-    for t in range(g.steps):
-        yield t, 0, 1
-        for s in range(g.substeps):
-            yield t, s, 2
+    return tsc.processed_full(g, g.ik, t, PA)
 
 
 def run_host_program(exe: str, g: IkGolden, tmp_dir: str) -> float:
@@ -206,17 +183,15 @@ class KernelTerm:
     """``imx_diff_ik`` over device tensors of its own.  The output tensors carry a sentinel row after N and ``joint_pos_des`` a sentinel
     column after the term's joints."""
 
-    SENTINEL = -77.25
-
     def __init__(self, ik, N: int, device="cuda:0"):
         from isaaclab_amd._lib import ImxDiffIk
 
         self.ik, self.N, self.dev = ik, N, torch.device(device)
         self.cfg = ImxDiffIk.from_term(ik)
         self.n = len(ik.joint_ids)
-        self.ee_pos_des = torch.full((N + 1, 3), self.SENTINEL, device=self.dev)
-        self.ee_quat_des = torch.full((N + 1, 4), self.SENTINEL, device=self.dev)
-        self.joint_pos_des = torch.full((N + 1, self.n + 1), self.SENTINEL, device=self.dev)
+        self.ee_pos_des = torch.full((N + 1, 3), SENTINEL, device=self.dev)
+        self.ee_quat_des = torch.full((N + 1, 4), SENTINEL, device=self.dev)
+        self.joint_pos_des = torch.full((N + 1, self.n + 1), SENTINEL, device=self.dev)
 
     def call(self, mode: int, proc, st: dict, cfg=None, **over) -> int:
         """Returns the status; 0 = launched."""
@@ -238,8 +213,7 @@ class KernelTerm:
 
     def outputs(self):
         pos, quat, des = self.ee_pos_des.cpu(), self.ee_quat_des.cpu(), self.joint_pos_des.cpu()
-        s = self.SENTINEL
-        assert (pos[self.N] == s).all() and (quat[self.N] == s).all() and (des[self.N] == s).all() and (des[:, self.n] == s).all(), "a sentinel was overwritten"
+        sentinels_intact(self.N, (pos, 3), (quat, 4), (des, self.n))
         return pos[: self.N], quat[: self.N], des[: self.N, : self.n]
 
 
@@ -248,11 +222,7 @@ def run_kernel(g: IkGolden, fill: float = 0.0, merged_first: bool = False):
     call's outputs (for the bit-for-bit comparisons) and the largest rho."""
     k = KernelTerm(g.ik, g.N)
     outs, worst = [], 0.0
-    for t, s, mode in schedule(g):
-        if merged_first and mode == 2 and s == 0:
-            continue
-        if merged_first and mode == 1:
-            mode = 3
+    for t, s, mode in calls(g, merged_first):
         assert k.call(mode, processed_full(g, t), g.state(t, s, fill)) == 0
         pos, quat, des = k.outputs()
         outs.append((pos.clone(), quat.clone(), des.clone()))

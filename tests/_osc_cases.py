@@ -18,6 +18,9 @@ import struct
 import numpy as np
 import torch
 
+import _task_space_cases as tsc
+from _task_space_cases import SENTINEL, calls as host_calls, host_compiler, schedule, sentinels_intact  # noqa: F401 (the tests use oc.*)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
 ROOT = os.path.dirname(HERE)
@@ -153,50 +156,16 @@ def run_oracle(g: OscGolden) -> float:
 
 
 # ---------------------------------------------------------------------------------------------------- the host program
-def host_compiler():
-    import shutil
-
-    for c in (os.environ.get("CXX"), "c++", "g++", "clang++"):
-        if c and shutil.which(c):
-            return shutil.which(c)
-    return None
-
-
 def build_host_program(out_dir: str, extra=()) -> str:
-    import subprocess
-
-    exe = os.path.join(out_dir, "osc_host")
-    subprocess.check_call([host_compiler(), "-O2", "-std=c++17", "-ffp-contract=off", *extra, os.path.join(ROOT, "tools", "osc_host.cpp"), "-o", exe])
-    return exe
+    return tsc.build_host_program("osc_host", out_dir, extra)
 
 
 def processed_full(g: OscGolden, t: int, PA: int | None = None):
-    """(N, PA) processed action with the recorded fp32 columns of the term at its processed column."""
-    o = g.osc
-    PA = o.processed_col + o.width if PA is None else PA
-    p = torch.zeros(g.N, PA)
-    p[:, o.processed_col:o.processed_col + o.width] = torch.from_numpy(np.ascontiguousarray(g.ref(f"step{t}/processed_actions", "f32")))
-    return p.contiguous()
-
-
-def schedule(g: OscGolden):
-    """The env's schedule: per step mode 1 on substep 0's state, then mode 2 on every substep's."""
-    for t in range(g.steps):
-        yield t, 0, 1
-        for s in range(g.substeps):
-            yield t, s, 2
+    return tsc.processed_full(g, g.osc, t, PA)
 
 
 def target_or_zeros(g: OscGolden):
     return g.target if g.target is not None else torch.zeros(g.N, len(g.osc.joint_ids))
-
-
-def host_calls(g: OscGolden, merged_first: bool = False):
-    """``schedule``; ``merged_first``: mode 3 for (mode 1, first mode 2), as the fused rollout launches."""
-    for t, s, mode in schedule(g):
-        if merged_first and mode == 2 and s == 0:
-            continue
-        yield t, s, 3 if merged_first and mode == 1 else mode
 
 
 def host_outputs(exe: str, g: OscGolden, tmp_dir: str, merged_first: bool = False):
@@ -239,8 +208,6 @@ class KernelTerm:
     """``imx_osc`` over device tensors of its own.  The output tensors carry a sentinel row after N and a sentinel column after their
     last column."""
 
-    SENTINEL = -77.25
-
     def __init__(self, osc, N: int, target=None, device="cuda:0"):
         from isaaclab_amd._lib import ImxOsc
 
@@ -248,8 +215,8 @@ class KernelTerm:
         self.cfg = ImxOsc.from_term(osc)
         self.n = len(osc.joint_ids)
         self.target = (target if target is not None else torch.zeros(N, self.n)).to(self.dev).contiguous()
-        self.command_state = torch.full((N + 1, 26), self.SENTINEL, device=self.dev)
-        self.joint_efforts = torch.full((N + 1, self.n + 1), self.SENTINEL, device=self.dev)
+        self.command_state = torch.full((N + 1, 26), SENTINEL, device=self.dev)
+        self.joint_efforts = torch.full((N + 1, self.n + 1), SENTINEL, device=self.dev)
 
     def call(self, mode: int, proc, st: dict, cfg=None, **over) -> int:
         """Returns the status; 0 = launched."""
@@ -272,8 +239,7 @@ class KernelTerm:
 
     def outputs(self):
         cmd, eff = self.command_state.cpu(), self.joint_efforts.cpu()
-        s = self.SENTINEL
-        assert (cmd[self.N] == s).all() and (cmd[:, 25] == s).all() and (eff[self.N] == s).all() and (eff[:, self.n] == s).all(), "a sentinel was overwritten"
+        sentinels_intact(self.N, (cmd, 25), (eff, self.n))
         return cmd[: self.N, :25], eff[: self.N, : self.n]
 
 
@@ -282,11 +248,7 @@ def run_kernel(g: OscGolden, fill: float = 0.0, merged_first: bool = False):
     call's outputs (for the bit-for-bit comparisons) and the largest rho."""
     k = KernelTerm(g.osc, g.N, g.target)
     outs, worst = [], 0.0
-    for t, s, mode in schedule(g):
-        if merged_first and mode == 2 and s == 0:
-            continue
-        if merged_first and mode == 1:
-            mode = 3
+    for t, s, mode in host_calls(g, merged_first):
         assert k.call(mode, processed_full(g, t), g.state(t, s, fill)) == 0
         cmd, eff = k.outputs()
         outs.append((cmd.clone(), eff.clone()))

@@ -106,6 +106,22 @@ def test_joint_position_fixtures_compile_to_the_same_blob(task):
     assert FRANKA_PANDA.fixed_base and UR10.fixed_base and not ROBOTS["anymal_c"].fixed_base
 
 
+# sha256 of bytes(ImxDiffIk.from_term(...)) of the variants' cfgs, as the commit before diff-IK and OSC came to share their resolver code
+# filled them (little-endian ints and floats: platform-independent)
+IK_STRUCTS = {
+    "V1": "5b3d6e91f1fd0189c8a8fa21c1610095c1e694c1f666b716ef8c0eebe99e25b8",
+    "V2": "a7ba6c6f1eb7ce160dac9433f607ec0a3269e0ad1c0d1d7c1444e002d495bc6f",
+    "V3": "4ad4a1957f8d0aa00b746da4c1799c887fdcbbdb8f8edd21b7038b0c14093603",
+    "V4": "12840d1e1d4967b8949e7a7ee1ae3b182208f1e0af2e85f8463d81a5d4a6d65d",
+    "V5": "2b34ff591d0516d452c5b0ad29f6fc911458c235cdde9e6ced189e2a424fa955",
+}
+
+
+@pytest.mark.parametrize("variant", ikc.VARIANTS)
+def test_variant_cfgs_fill_the_same_struct(variant):
+    assert hashlib.sha256(bytes(_lib.ImxDiffIk.from_term(ikc.IkGolden(variant, 1).ik))).hexdigest() == IK_STRUCTS[variant]
+
+
 # ------------------------------------------------------------------------------------------------ refusals
 def _reach_rel_env():
     return copy.deepcopy(load_task_cfg(ikc.task_path("Isaac-Reach-Franka-IK-Rel-v0"))["env"])

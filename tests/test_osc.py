@@ -119,6 +119,16 @@ PARENT_BLOBS = {
     "golden/Isaac-Reach-Franka-IK-Rel-v0.json": "1f8aece61aee726e7b721f1b2227d80468cac327a67c4b416400f00f3548dac9",
     "golden/Isaac-Lift-Cube-Franka-IK-Abs-v0.json": "0dfd7743daf5a430bf410996feb28b895d68c3b0fddff103000fa35d5469beb4",
     "golden/Isaac-Lift-Cube-Franka-IK-Rel-v0.json": "2edfa4cea341ce704a4e04080f5b252c733726c26b971ade0234adc9af5a4e9c",
+    # (the term's own task, as compiled before diff-IK and OSC came to share their resolver code)
+    "golden/Isaac-Reach-Franka-OSC-v0.json": "e6838b6a3c1f8134ce3ca6cf3ccf16e907c75a6c01c5d072bd8fb40dc952a901",
+}
+# sha256 of bytes(ImxOsc.from_term(...)) of the variants' cfgs, from the same commit (little-endian ints and floats: platform-independent)
+OSC_STRUCTS = {
+    "O1": "090c39dd5493aa88dd3226e02aa5ea6079f3f5745d92d487340cc1ba2b310bac",
+    "O2": "2f39d0f41d57aaf4e0354fa101343d3e9f208a9910ced962087698aae90db9d4",
+    "O3": "d122e7b3c0be0d981d7e11976d83d7e86124d822f5166786a4f6441bf65ebfae",
+    "O4": "920d3790d7d2a44b11bacdc250a04799364106b86af972f043b0049b905770f7",
+    "O5": "119201c85db5506b5f25795a2ee1d6bfc0db498e1df9cf9e4b06c9aeed0bb9b9",
 }
 
 
@@ -127,7 +137,12 @@ def test_existing_fixtures_compile_to_the_same_blob(task):
     fx = load_task_cfg(os.path.join(oc.HERE, task) if task.startswith("golden/") else task)
     p = compile_plan(fx["env"], ROBOTS[fx["robot"]])
     assert hashlib.sha256(p.blob.astype("<i4").tobytes()).hexdigest() == PARENT_BLOBS[task]
-    assert p.osc_terms == [] and len(p.ik_terms) == (1 if "-IK-" in task else 0)
+    assert len(p.osc_terms) == (1 if "-OSC-" in task else 0) and len(p.ik_terms) == (1 if "-IK-" in task else 0)
+
+
+@pytest.mark.parametrize("variant", oc.VARIANTS)
+def test_variant_cfgs_fill_the_same_struct(variant):
+    assert hashlib.sha256(bytes(_lib.ImxOsc.from_term(oc.OscGolden(variant, 1).osc))).hexdigest() == OSC_STRUCTS[variant]
 
 
 # ------------------------------------------------------------------------------------------------ errors and refusals

@@ -1,7 +1,7 @@
 """MEASUREMENT (MI355X): ``imx_osc`` under HIP events at 4096 envs, modes 1, 2 and 3, next to ``imx_diff_ik`` (the IK-Abs Reach
 fixture) and ``imx_action_process`` (the OSC fixture's 13-column action record).
 
-    python tools/time_osc.py [--num-envs 4096] [--launches 200] [--repeats 7]
+    python tools/time_osc.py [--num-envs 4096] [--launches 200] [--repeats 7] [--lib another/libimx.so]
 
 Each figure is the median over ``--repeats`` of (event time of ``--launches`` back-to-back launches) / launches, after a warm-up batch:
 the launch-to-launch period of a small kernel on one stream as the eager env pays it (host call included); the ``_graph`` figures replay
@@ -69,8 +69,11 @@ def main():
     ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--lib", help="time this build of the library instead of the tree's (for one build against another)")
     a = ap.parse_args()
-    res = {"num_envs": a.num_envs, "unit": "us per launch", "device": torch.cuda.get_device_name(0)}
+    if a.lib:
+        _lib.LIB_PATH = os.path.abspath(a.lib)
+    res = {"lib": os.path.relpath(_lib.LIB_PATH, ROOT), "num_envs": a.num_envs, "unit": "us per launch", "device": torch.cuda.get_device_name(0)}
     env = make_env("Isaac-Reach-Franka-OSC-v0", a.num_envs)
     for mode in (1, 2, 3):
         res[f"k_osc_mode{mode}"] = round(timed(lambda: env._osc_launch(mode), a.launches, a.repeats), 3)

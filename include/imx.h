@@ -181,8 +181,13 @@ enum imx_rew_op {
     IMX_W_OBJECT_EE_DISTANCE,         /* :28-45  1 - tanh(||object - ee_w|| / p0), p0 = std; ee_w = the FrameTransformer's first target frame =
                                                   body_pos_w[:, id] + quat_apply(body_quat_w[:, id], (p1, p2, p3)): ids = the ONE robot body the frame
                                                   sits on, p1..p3 = its offset position (frame_transformer.py:358; identity offset rotation) */
-    IMX_W_OBJECT_GOAL_DISTANCE        /* :48-67  (object z > p1) * (1 - tanh(||des_pos_w - object|| / p0)), p0 = std, p1 = minimal_height;
+    IMX_W_OBJECT_GOAL_DISTANCE,       /* :48-67  (object z > p1) * (1 - tanh(||des_pos_w - object|| / p0)), p0 = std, p1 = minimal_height;
                                                   des_pos_w as for the reach rewards, CMD == 7 */
+    /* isaaclab_tasks .../navigation/mdp/rewards.py (Isaac-Navigation-Flat-Anymal-C-v0); command = (N, 4) pose-2d command in the base
+       frame (CMD == 4): pos_command_b 3, heading_command_b 1.  A plan with these ops runs k_term_rew_nav and holds no classic, reach or
+       lift op */
+    IMX_W_NAV_POSITION_COMMAND_ERROR_TANH, /* :17-22  1 - tanh(||cmd[:3]|| / p0), p0 = std */
+    IMX_W_NAV_HEADING_COMMAND_ERROR_ABS    /* :25-29  |cmd[3]| */
 };
 
 /* observation ops -- envs/mdp/observations.py */
@@ -461,7 +466,7 @@ int imx_reset_orchestrate_manip(const imx_orch_t* orch, const imx_orch_manip_t* 
 /* ---- library ---------------------------------------------------------------------------------------------------- */
 const char* imx_version(void);
 /* sizeof of an ABI struct as this library was compiled (which: 0 imx_state_t, 1 imx_buffers_t, 2 imx_head_loss_t, 3 imx_rollout_slot_t, 4 imx_policy_act_t, 5 imx_orch_t, 6 imx_event_term_t,
- * 7 imx_diff_ik_t, 8 imx_osc_t, 10 imx_orch_manip_t, 11 imx_weight_term_t), 0 for an unknown index (9 is one):
+ * 7 imx_diff_ik_t, 8 imx_osc_t, 10 imx_orch_manip_t, 11 imx_weight_term_t, 12 imx_pretrained_policy_t), 0 for an unknown index (9 is one):
  * a binding checks its own layout against it at load time. */
 size_t imx_struct_size(int which);
 const char* imx_last_error(void);
@@ -1003,6 +1008,39 @@ int imx_osc(const imx_osc_t* cfg, int64_t N, int mode, const float* processed_ac
             int64_t num_bodies, const float* jacobians_d, int64_t NB, int64_t ND, const float* mass_matrices_d, const float* gravity_d,
             int64_t NM, const float* joint_pos_d, const float* joint_vel_d, int64_t J, const float* nullspace_target_d,
             float* command_state_d, int64_t ld_cmd, float* joint_efforts_d, int64_t ld_eff, imx_stream_t stream);
+
+/* ---- PreTrainedPolicyAction -------------------------------------------------------------------------------------------
+ * One low-level locomotion step of the term (isaaclab_tasks .../navigation/mdp/pre_trained_policy_action.py:93-100) for all envs in
+ * ONE launch: the masked zero of the last_action() closure (:53-57), the low-level observation group, the policy MLP and the
+ * low-level JointPositionAction.process_actions.
+ * ll_plan: the low-level observation group and the low-level action term compiled as a plan of their own (isaaclab_amd/plan.py,
+ *   plan.policy_terms): one observation group without history, modifiers, height scan or Python-evaluated term; its D = dims[0] of
+ *   the policy, its A = dims[nlayers].  Its generated_commands op reads st->command (the env points it at the term's raw action, CMD
+ *   columns), its last_action op reads bf->action = low_level_actions (N, A).
+ * Per workgroup of tile_rows (16 or 32; 0 = the choice imx_mlp_infer makes for one network at this N) envs: the root-frame vectors of
+ * the rows; every observation column through the device functions of imx_observations (value, noise, clip, scale; a last_action column
+ * of an env with bf->episode_length_buf == 0 reads 0) straight into the LDS tile; the Linear + ELU layers on the MFMA; then
+ * bf->action <- the policy output, bf->prev_action <- the old bf->action, bf->processed_action <- the action records (N, PA): the joint
+ * position targets.  Every element equals what the chain imx_observations(ll_plan) -> imx_mlp_infer -> imx_action_process(ll_plan)
+ * gives after the masked zero, bit for bit, when the chain's imx_mlp_infer runs the same tile height.
+ * noise_u_d: (N, D) uniforms replacing the in-kernel draws (parity runs), or NULL: draws keyed by (seed, step, env * D + column) with
+ *   step = (step_counter_d ? step_counter_d[0] : 0) * step_stride + step_offset.  enable_corruption: bit 0, as in imx_observations.
+ * obs_out_d: optional (N, D) copy of the observation rows (debug / tests), or NULL.
+ * Refused without a launch: a null plan / state / buffers / policy, N < 1, a plan outside the description above, nlayers outside
+ * [1, IMX_PP_MAX_LAYERS], a width outside [1, 512], dims that do not match the plan, a null or misaligned weight, a pitch that is
+ * no multiple of 32 or below the layer's inputs, packed weights for some layers only, tile_rows other than 0, 16, 32, a state tensor
+ * an observation or action record needs, a null action / prev_action / processed_action / episode_length_buf. */
+typedef struct imx_pretrained_policy imx_pretrained_policy_t;
+#include "imx_pretrained_policy_struct.h"
+int imx_pretrained_policy(const imx_plan_t* ll_plan, int64_t N, const imx_state_t* st, const imx_buffers_t* bf,
+                          const imx_pretrained_policy_t* policy, const float* noise_u_d, uint64_t seed, const int32_t* step_counter_d,
+                          int32_t step_stride, int32_t step_offset, int enable_corruption, int tile_rows, float* obs_out_d,
+                          imx_stream_t stream);
+/* The refusals of imx_pretrained_policy alone, without a device: 0 = the launch would be made. */
+int imx_pretrained_policy_check(const imx_plan_t* ll_plan, int64_t N, const imx_state_t* st, const imx_buffers_t* bf,
+                                const imx_pretrained_policy_t* policy, int tile_rows);
+/* The tile height imx_pretrained_policy(tile_rows = 0) and imx_mlp_infer (one network) run at N rows: 16 or 32. */
+int imx_pretrained_policy_tile_rows(int64_t N);
 
 #ifdef __cplusplus
 }

@@ -160,5 +160,10 @@ try:
     with open(MANIP_HEADER) as _f:
         _manip_defines, _, MANIP_STRUCTS, _ = parse(_f.read(), MANIP_HEADER, DEFINES)
     DEFINES.update(_manip_defines)  # IMX_ORCH_MAX_WEIGHT_TERMS
+    # imx_pretrained_policy_struct.h, likewise: imx_pretrained_policy_t (imx_pretrained_policy)
+    POLICY_HEADER = os.path.join(os.path.dirname(HEADER), "imx_pretrained_policy_struct.h")
+    with open(POLICY_HEADER) as _f:
+        _policy_defines, _, POLICY_STRUCTS, _ = parse(_f.read(), POLICY_HEADER, DEFINES)
+    DEFINES.update(_policy_defines)  # IMX_PP_MAX_LAYERS
 except OSError as e:
     raise AbiError(f"the ABI header {HEADER} cannot be read ({e}): the whole binding is derived from it") from e

@@ -18,6 +18,7 @@ ORCH_MAX_TERMS = _abi.DEFINES["IMX_ORCH_MAX_TERMS"]
 ORCH_MAX_WEIGHT_TERMS = _abi.DEFINES["IMX_ORCH_MAX_WEIGHT_TERMS"]
 IK_MAX_JOINTS = _abi.DEFINES["IMX_IK_MAX_JOINTS"]
 OSC_CMD_WIDTH = _abi.DEFINES["IMX_OSC_CMD_WIDTH"]
+PP_MAX_LAYERS = _abi.DEFINES["IMX_PP_MAX_LAYERS"]
 _STRUCTS = {}  # typedef name -> class
 
 
@@ -85,6 +86,9 @@ ImxOsc._fields_ = [(field, _abi.ctype(t, _STRUCTS)) for field, t in _abi.OSC_STR
 ImxWeightTerm = type("ImxWeightTerm", (ctypes.Structure,), {"_fields_": [(field, _abi.ctype(t, _STRUCTS)) for field, t in _abi.MANIP_STRUCTS["imx_weight_term_t"]]})
 ImxOrchManip = type("ImxOrchManip", (ctypes.Structure,), {"_fields_": [(field, _abi.ctype(t, {**_STRUCTS, "imx_weight_term_t": ImxWeightTerm}))
                                                                       for field, t in _abi.MANIP_STRUCTS["imx_orch_manip_t"]]})
+# (imx_pretrained_policy_struct.h, the same way)
+ImxPretrainedPolicy = type("ImxPretrainedPolicy", (ctypes.Structure,), {"_fields_": [(field, _abi.ctype(t, _STRUCTS))
+                                                                                    for field, t in _abi.POLICY_STRUCTS["imx_pretrained_policy_t"]]})
 if set(_STRUCTS) != set(_abi.STRUCTS):
     raise _abi.AbiError(f"{_abi.HEADER}: no class for {sorted(set(_abi.STRUCTS) - set(_STRUCTS))}")
 STATE_FIELDS = tuple(field for field, _ in ImxState._fields_)
@@ -97,7 +101,8 @@ class ImxError(RuntimeError):
 
 _lib = None
 
-_SIGNATURES = {name: (_abi.ctype(res, _STRUCTS, ret=True), [_abi.ctype(t, _STRUCTS) for t in args])
+_BY_POINTER = {**_STRUCTS, "imx_pretrained_policy_t": ImxPretrainedPolicy}  # (a struct of an included header travels as POINTER(class) too)
+_SIGNATURES = {name: (_abi.ctype(res, _BY_POINTER, ret=True), [_abi.ctype(t, _BY_POINTER) for t in args])
                for name, (res, args, _) in _abi.FUNCTIONS.items()}
 EXPORTS = tuple(_SIGNATURES)
 
@@ -124,7 +129,7 @@ def lib():
         fn.restype = res
         fn.argtypes = args
     for which, cls in (*enumerate((ImxState, ImxBuffers, ImxHeadLoss, ImxRolloutSlot, ImxPolicyAct, ImxOrch, ImxEventTerm, ImxDiffIk, ImxOsc)),
-                       (10, ImxOrchManip), (11, ImxWeightTerm)):  # the binding's struct layouts against the library's (index 9 is unknown)
+                       (10, ImxOrchManip), (11, ImxWeightTerm), (12, ImxPretrainedPolicy)):  # the binding's struct layouts against the library's (index 9 is unknown)
         if int(L.imx_struct_size(which)) != ctypes.sizeof(cls):
             raise ImxError(f"{LIB_PATH}: sizeof({cls.__name__}) is {int(L.imx_struct_size(which))} in the library, {ctypes.sizeof(cls)} in the "
                            "binding -- rebuild with `python -m isaaclab_amd.build`")

@@ -35,6 +35,7 @@ extern "C" size_t imx_struct_size(int which) {
         case 8: return sizeof(imx_osc_t);
         case 10: return sizeof(imx_orch_manip_t);
         case 11: return sizeof(imx_weight_term_t);
+        case 12: return sizeof(imx_pretrained_policy_t);
         default: return 0;
     }
 }
@@ -121,7 +122,7 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
     for (int k = 0; k < p->nrew; ++k) {
         const int32_t* r = &w[p->rew_off + k * IMX_REC_WORDS];
         const int op = r[IMX_R_OP];
-        IMX_REQUIRE(op >= IMX_W_IS_ALIVE && op <= IMX_W_OBJECT_GOAL_DISTANCE, "plan: unknown reward op %d", op);
+        IMX_REQUIRE(op >= IMX_W_IS_ALIVE && op <= IMX_W_NAV_HEADING_COMMAND_ERROR_ABS, "plan: unknown reward op %d", op);
         IMX_REQUIRE(r[IMX_R_OUT] == k, "plan: reward record %d has index %d", k, r[IMX_R_OUT]);
         int limit = p->J;
         const char* what = "joint";
@@ -148,6 +149,8 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
         if (op == IMX_W_OBJECT_EE_DISTANCE) IMX_REQUIRE(r[IMX_R_NIDS] == 1, "plan: reward record %d (object_ee_distance) needs the one body of its frame", k);
         if (op == IMX_W_OBJECT_GOAL_DISTANCE)
             IMX_REQUIRE(p->CMD == 7, "plan: reward record %d (object_goal_distance) needs a 7-wide pose command (CMD=%d)", k, p->CMD);
+        if (op == IMX_W_NAV_POSITION_COMMAND_ERROR_TANH || op == IMX_W_NAV_HEADING_COMMAND_ERROR_ABS)
+            IMX_REQUIRE(p->CMD == 4, "plan: reward record %d (op %d) needs a 4-wide pose-2d command (CMD=%d)", k, op, p->CMD);
         if (op == IMX_W_PROGRESS_REWARD)
             IMX_REQUIRE(r[IMX_R_AUX0] >= 0 && r[IMX_R_AUX0] < p->term_slots, "plan: reward record %d: state slot %d outside [0, %d)", k,
                         r[IMX_R_AUX0], p->term_slots);

@@ -7,6 +7,7 @@
 // association order (compile with -ffp-contract=off).
 #include "imx_internal.h"
 #include "imx_raycast.h"
+#include "imx_obs_device.h"
 // Scalar-register budget of the lean observation kernel.  On gfx950 a SIMD has 800 SGPRs, allocated in blocks of 16: the 106 the compiler
 // takes by default (100 + VCC / FLAT_SCRATCH / XNACK) round to 112 = SEVEN waves per SIMD although the 57 VGPRs allow eight.  Capped,
 // the compiler parks ~30 rarely used scalars in VGPR lanes; measured at 65 536 envs: 102 -> 142 us, 96 -> 132, 88 -> 132, 80 -> 126,
@@ -89,9 +90,6 @@ IMX_DEV bool any_ids(const int32_t* __restrict__ ids, int n, F f) {
 
 // max over history of the force norm on body b (rewards.py:266, terminations.py:157): max_h sqrt(s_h) with s_h = (x^2 + y^2) + z^2.
 // sqrtf is correctly rounded and monotone, so max_h sqrt(s_h) == sqrt(max_h s_h) bit for bit: ONE square root per body.
-// torch.clamp / Tensor.clip of an observation: NaN stays NaN (fminf / fmaxf alone return the bound).  A height-scan ray that misses
-// (+inf hit) through a DigitalFilter gives -inf - -inf = NaN, and the reference's observation is NaN, not the clip bound.
-IMX_DEV float clip_keep_nan(float v, float lo, float hi) { return v != v ? v : fminf(fmaxf(v, lo), hi); }
 
 IMX_DEV float max_hist_force(const float* __restrict__ F, int64_t e, int H, int B, int b) {
     const float* f = F + ((size_t)e * H * B + b) * 3;
@@ -128,34 +126,6 @@ IMX_DEV bool spot_active(float cx, float cy, float cz, float vx, float vy, float
 IMX_DEV float progress_potential(float tx, float ty, float tz, float px, float py, float pz, float dt, bool z_on) {
     const float dx = tx - px, dy = ty - py, dz = z_on ? tz - pz : 0.0f;
     return -sqrtf((dx * dx + dy * dy) + dz * dz) / dt;
-}
-// one angle of euler_xyz_from_quat (utils/math.py:414-444) `% (2 pi)`: atan2 lies in [-pi, pi], where torch.remainder by fp32(2 pi) is
-// x + 2 pi for x < 0 and x itself otherwise (-0 included)
-IMX_DEV float euler_mod_2pi(float s, float c) {
-    const float a = atan2f(s, c);
-    return a < 0.0f ? a + 6.28318530717958647692f : a;
-}
-// atan2(sin(a), cos(a)) of observations.py:26-28,75 for a in (-3 pi, 2 pi): a wrapped into (-pi, pi] without sinf / cosf (exact math;
-// within a few ulps of pi the reference's rounding can land on the other side -- a known deviation, compared modulo 2 pi)
-IMX_DEV float wrap_atan2(float a) {
-    const float PI = 3.14159265358979323846f, TWO_PI = 6.28318530717958647692f;
-    return a > PI ? a - TWO_PI : (a <= -PI ? a + TWO_PI : a);
-}
-// base_heading_proj (observations.py:43-58): quat_rotate(q, FORWARD_VEC_B = (1, 0, 0)) (utils/math.py:583-602, a + b + c; with v = x the
-// cross and dot products reduce to single factors exactly) . normalize(target - pos, z = 0) (math.py:82-92: x / max(||x||, 1e-9))
-IMX_DEV float heading_proj(float qw, float qx, float qy, float qz, float tx, float ty, float px, float py) {
-    const float dx = tx - px, dy = ty - py;
-    const float n = fmaxf(sqrtf(dx * dx + dy * dy), 1.0e-9f);
-    const float ux = dx / n, uy = dy / n;
-    const float hx = (2.0f * (qw * qw) - 1.0f) + (qx * qx) * 2.0f;
-    const float hy = (qz * qw) * 2.0f + (qy * qx) * 2.0f;
-    return hx * ux + hy * uy;  // + hz * 0
-}
-// base_angle_to_target (observations.py:61-77): atan2(to_target y, x) - yaw, wrapped
-IMX_DEV float angle_to_target(float qw, float qx, float qy, float qz, float tx, float ty, float px, float py) {
-    const float walk = atan2f(ty - py, tx - px);
-    const float yaw = euler_mod_2pi(2.0f * (qw * qz + qx * qy), 1.0f - 2.0f * (qy * qy + qz * qz));
-    return wrap_atan2(walk - yaw);
 }
 
 // The reward functions of classic/humanoid/mdp/rewards.py for env ec -- the raw value f.  Evaluated in phase 2 of
@@ -277,6 +247,16 @@ IMX_DEV float lift_reward(const PlanView& P, const imx_state_t& S, const int32_t
     const float dy = S.object_root_pos_w[ec * 3 + 1] - (S.body_pos_w[b * 3 + 1] + oy);
     const float dz = oz - (S.body_pos_w[b * 3 + 2] + oz2);
     return 1.0f - tanhf(sqrtf((dx * dx + dy * dy) + dz * dz) / p0);
+}
+
+// ---- navigation/mdp/rewards.py (Isaac-Navigation-Flat-Anymal-C-v0): the (N, 4) pose-2d command in the base frame; in phase 2 of
+// k_term_rew_nav.  position_command_error_tanh :17-22: torch.norm(cmd[:, :3], dim=1) = sqrt of the sequential sum of squares;
+// heading_command_error_abs :25-29
+IMX_DEV float nav_reward(const PlanView& P, const imx_state_t& S, const int32_t* __restrict__ r, int op, int64_t ec) {
+    const float* __restrict__ cmd = S.command + ec * P.CMD;
+    if (op == IMX_W_NAV_HEADING_COMMAND_ERROR_ABS) return fabsf(cmd[3]);
+    const float d = sqrtf((cmd[0] * cmd[0] + cmd[1] * cmd[1]) + cmd[2] * cmd[2]);
+    return 1.0f - tanhf(d / f_of(r[IMX_R_P0]));
 }
 
 // scratch layout for k_term_rew (4-byte words, nw = number of env groups; sized for the smallest group: ceil(N/16) groups)
@@ -546,6 +526,16 @@ k_term_rew_lift(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, StepScra
 #undef IMX_TR_LIFT
 }
 
+// NAV: the navigation task's two reward ops, in a kernel of their own like the lift ops (the shared instantiations stay as they were).
+__global__ void __launch_bounds__(64 * IMX_TR_MAX_WAVES)
+k_term_rew_nav(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, StepScratch sc, float* __restrict__ frame, int G, int defer_tail,
+               imx_rollout_slot_t ro) {
+    constexpr bool CLASSIC = false, REACH = false;
+#define IMX_TR_NAV
+#include "term_rew_body.inc"
+#undef IMX_TR_NAV
+}
+
 // ------------------------------------------------------------------------------------------------- observations
 // One WAVE = one environment (4 envs per 256-thread block).  Every lane first derives the env's root-frame vectors
 // and scanner yaw from the same 13 root-state floats (wave-uniform loads: one transaction, no LDS, no barrier);
@@ -557,57 +547,6 @@ k_term_rew_lift(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, StepScra
 // Height-scanner rays (yaw-only frame, vertical direction) take a fast path that keeps up to four rays of a lane
 // in flight: cell-table loads of all four, then the 48-byte triangle records of all four, then the Woop tests.
 #define IMX_OBS_ENVS_PER_BLOCK 4
-#define IMX_XCOL_WORDS 16
-enum { XC_COL = 0, XC_OP, XC_J, XC_FLAGS, XC_P0, XC_NLO, XC_NHI, XC_CLO, XC_CHI, XC_SCALE, XC_AUX, XC_RX, XC_RY, XC_RZ, XC_HIST, XC_HSTRIDE };
-
-struct XCol {
-    int4 a, b, c, d;
-};
-IMX_DEV XCol load_xcol(const int32_t* __restrict__ W, int off, int i) {
-    const int4* p = reinterpret_cast<const int4*>(W + off) + (size_t)i * 4;
-    XCol x;
-    x.a = p[0]; x.b = p[1]; x.c = p[2]; x.d = p[3];
-    return x;
-}
-
-// The noise term of one element: uniform_noise u * (n_max - n_min) + n_min (noise_model.py:62-66; constant_noise is the case n_min == n_max)
-// or gaussian_noise mean + std * z (:87-92).  The sample is the fed one (the reference's recorded rand_like / randn_like draw) or comes
-// from the counter-based generator (Box-Muller on two of its uniforms for z).
-// GAUSS = false: plans without a gaussian term (the LEAN kernels: logf / cosf / sqrtf in their instruction stream cost 2 % at 4096 envs
-// and 7 % at 65 536, taken or not; a plan with gaussian noise runs the general kernels).
-template <bool GAUSS>
-IMX_DEV float noise_sample(int flags, float lo, float hi, const float* __restrict__ noise_u, uint64_t seed, uint32_t step, int64_t e, int D, int c) {
-    if (GAUSS && (flags & IMX_F_NOISE_GAUSS)) {
-        float z;
-        if (noise_u) {
-            z = noise_u[e * D + c];
-        } else {
-            const float u1 = uniform01(seed, step, (uint64_t)e * D + c), u2 = uniform01(seed ^ 0x6A09E667F3BCC909ull, step, (uint64_t)e * D + c);
-            z = sqrtf(-2.0f * logf(1.0f - u1)) * cosf(6.28318530717958647692f * u2);  // 1 - u1 in (0, 1]: no log(0)
-        }
-        return lo + hi * z;
-    }
-    const float u = noise_u ? noise_u[e * D + c] : uniform01(seed, step, (uint64_t)e * D + c);
-    return u * (hi - lo) + lo;
-}
-
-// D = width of the whole column space (all groups side by side), gbase = first column of this entry's group in it: the parity-mode
-// uniforms are one (N, D) array, group after group
-template <bool GAUSS>
-IMX_DEV float obs_post(const XCol& x, float v, int corrupt, const float* __restrict__ noise_u, uint64_t seed, uint32_t step,
-                       int64_t e, int D, int gbase) {
-    const int flags = x.a.w;
-    if (corrupt && (flags & (IMX_F_NOISE_ADD | IMX_F_NOISE_SCALE | IMX_F_NOISE_ABS))) {
-        // a term with a history window draws for its first (oldest-slot) columns, like rand_like on the (N, d) term value
-        const int c = gbase + x.a.x - (x.d.z - 1) * x.d.w;
-        const float lo = f_of(x.b.y), hi = f_of(x.b.z);
-        const float nz = noise_sample<GAUSS>(flags, lo, hi, noise_u, seed, step, e, D, c);
-        v = (flags & IMX_F_NOISE_ADD) ? v + nz : ((flags & IMX_F_NOISE_SCALE) ? v * nz : nz);
-    }
-    if (flags & IMX_F_CLIP) v = clip_keep_nan(v, f_of(x.b.w), f_of(x.c.x));
-    if (flags & IMX_F_SCALE) v = v * f_of(x.c.y);
-    return v;
-}
 
 // ObservationTermCfg.modifiers (observation_manager.py:310-312; utils/modifiers/modifier.py): the term's modifier program,
 // run on the raw value of ONE element; filter / integrator state of that element lives in the env's mod_state row at
@@ -687,64 +626,12 @@ k_frame(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, float* __restric
         dst[5] = scanner_step(P, Bf, e, (uint32_t)Bf.counters[2], fill_all || (Bf.reset_buf && Bf.reset_buf[e]), o[2].y, o[2].z, o[2].w);
 }
 
-// object_position_in_robot_root_frame (manipulation/lift/mdp/observations.py:19-31), component j: subtract_frame_transforms (utils/math.py:
-// 785-816) = quat_apply(quat_inv(q), object - root), the subtraction inside the rotation; quat_inv = normalize(conjugate(q)) (:239-248,
-// normalize :82-92 = x / max(||x||, 1e-9)).  es = the env's frame row: root position 9..11, root quaternion 12..15
-IMX_DEV float object_pos_in_root_frame(const float* __restrict__ es, const float* __restrict__ obj, int j) {
-    const float w = es[12], x = es[13], y = es[14], z = es[15];
-    const float n = fmaxf(sqrtf(((w * w + x * x) + y * y) + z * z), 1.0e-9f);
-    float ox, oy, oz;
-    quat_apply(w / n, -x / n, -y / n, -z / n, obj[0] - es[9], obj[1] - es[10], obj[2] - es[11], ox, oy, oz);
-    return j == 0 ? ox : (j == 1 ? oy : oz);
-}
 
 // k_obs: one BLOCK = one environment, one lane = one output column (ray columns first in xcol).  No prologue, no
 // barrier: the env's 20-float frame is read with wave-uniform loads (scalar cache), then every lane is an independent,
 // register-light stream: xcol (four 16-byte loads) -> value -> noise/clip/scale -> obs[e*D + c]; consecutive lanes
 // write consecutive floats of one obs row.  The ray path is cast_ray_vertical (imx_raycast.h): cell descriptor and
 // the four shared lattice corners are loaded together -- one dependent memory level per ray on height-field terrain.
-// value of one non-ray observation column (every op but HEIGHT_SCAN); es = the env's frame (k_frame).  OBJECT: with the op that reads the
-// scene's rigid object -- k_obs only; k_obs_lean, tuned to its SGPR budget, is not chosen for a plan that has it (choose_obs_kernel)
-template <bool OBJECT>
-IMX_DEV float obs_plain_value(const PlanView& P, const imx_state_t& S, const imx_buffers_t& Bf, const float* __restrict__ es,
-                              int64_t e, const XCol& x) {
-    const int32_t* __restrict__ W = P.w;
-    const int op = x.a.y, j = x.a.z, flags = x.a.w, aux = x.c.z, J = P.J;
-    switch (op) {
-        case IMX_O_BASE_POS_Z: return es[11];
-        case IMX_O_BASE_LIN_VEL: return es[0 + j];
-        case IMX_O_BASE_ANG_VEL: return es[3 + j];
-        case IMX_O_PROJECTED_GRAVITY: return es[6 + j];
-        case IMX_O_ROOT_POS_W: return es[9 + j] - S.env_origins[e * 3 + j];
-        case IMX_O_ROOT_QUAT_W: return ((flags & IMX_F_QUAT_UNIQUE) && es[12] < 0.0f) ? -es[12 + j] : es[12 + j];
-        case IMX_O_ROOT_LIN_VEL_W: return S.root_lin_vel_w[e * 3 + j];
-        case IMX_O_ROOT_ANG_VEL_W: return S.root_ang_vel_w[e * 3 + j];
-        case IMX_O_JOINT_POS: return S.joint_pos[e * J + aux];
-        case IMX_O_JOINT_POS_REL: return S.joint_pos[e * J + aux] - S.default_joint_pos[e * J + aux];
-        case IMX_O_JOINT_POS_LIMIT_NORMALIZED: {  // scale_transform (utils/math.py:22-40)
-            const float2 lim = reinterpret_cast<const float2*>(S.soft_joint_pos_limits)[e * J + aux];
-            const float offset = (lim.x + lim.y) * 0.5f;
-            return 2.0f * (S.joint_pos[e * J + aux] - offset) / (lim.y - lim.x);
-        }
-        case IMX_O_JOINT_VEL: return S.joint_vel[e * J + aux];
-        case IMX_O_JOINT_VEL_REL: return S.joint_vel[e * J + aux] - S.default_joint_vel[e * J + aux];
-        case IMX_O_LAST_ACTION: return Bf.action[e * P.A + j];
-        case IMX_O_GENERATED_COMMANDS: return S.command[e * P.CMD + j];
-        case IMX_O_EXTERNAL: return S.ext_obs[e * (int64_t)W[IMX_H_NEXT_OBS] + aux + j];
-        // classic/humanoid/mdp/observations.py; target_pos x, y in XC_P0, XC_RX
-        case IMX_O_BASE_YAW_ROLL: {  // :19-30: yaw, roll
-            const float qw = es[12], qx = es[13], qy = es[14], qz = es[15];
-            return wrap_atan2(j == 0 ? euler_mod_2pi(2.0f * (qw * qz + qx * qy), 1.0f - 2.0f * (qy * qy + qz * qz))
-                                     : euler_mod_2pi(2.0f * (qw * qx + qy * qz), 1.0f - 2.0f * (qx * qx + qy * qy)));
-        }
-        case IMX_O_BASE_UP_PROJ: return -es[8];  // :33-40
-        case IMX_O_BASE_HEADING_PROJ: return heading_proj(es[12], es[13], es[14], es[15], f_of(x.b.x), f_of(x.c.w), es[9], es[10]);
-        case IMX_O_BASE_ANGLE_TO_TARGET: return angle_to_target(es[12], es[13], es[14], es[15], f_of(x.b.x), f_of(x.c.w), es[9], es[10]);
-        case IMX_O_BODY_INCOMING_WRENCH: return S.link_incoming_joint_force[e * (int64_t)P.NB * 6 + aux];  // envs/mdp/observations.py:176-185
-        case IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME: return OBJECT ? object_pos_in_root_frame(es, S.object_root_pos_w + e * 3, j) : 0.0f;
-        default: return 0.0f;
-    }
-}
 
 // modifiers -> noise -> clip -> scale -> history window -> obs[e][c] for computed column i (observation_manager.py:305-335)
 // LEAN: the plan has one observation group, no modifiers and no history windows (every task config of BASELINE.json) -- the code for
@@ -1171,6 +1058,7 @@ extern "C" int imx_terminations_rewards_rollout(const imx_plan_t* plan, int64_t 
             case IMX_W_OBJECT_GOAL_DISTANCE:
                 if (need(st->command, "command") || need(st->root_pos_w, "root_pos_w") || need(st->object_root_pos_w, "object_root_pos_w")) return 1;
                 break;
+            case IMX_W_NAV_POSITION_COMMAND_ERROR_TANH: case IMX_W_NAV_HEADING_COMMAND_ERROR_ABS: if (need(st->command, "command")) return 1; break;
             default: break;
         }
     }
@@ -1189,12 +1077,13 @@ extern "C" int imx_terminations_rewards_rollout(const imx_plan_t* plan, int64_t 
     const size_t lds = ((size_t)(plan->nterm > 0 ? plan->nterm : 1) * 64 + 3 * (size_t)(plan->nrew > 0 ? plan->nrew : 1) * 64) * 4;
     // with the root position at hand the kernel also leaves the frame table imx_observations needs (flag 4 there skips k_frame)
     float* frame = st->root_pos_w ? reinterpret_cast<float*>(reinterpret_cast<char*>(bf->scratch) + frame_offset_bytes(plan, N)) : nullptr;
-    bool classic = false, reach = false, lift = false;
+    bool classic = false, reach = false, lift = false, nav = false;
     for (int k = 0; k < plan->nrew; ++k) {
         const int op = w[plan->rew_off + k * IMX_REC_WORDS + IMX_R_OP];
         classic = classic || (op >= IMX_W_UPRIGHT_POSTURE_BONUS && op <= IMX_W_POWER_CONSUMPTION);
-        reach = reach || op >= IMX_W_POSITION_COMMAND_ERROR;
-        lift = lift || op >= IMX_W_OBJECT_IS_LIFTED;
+        reach = reach || (op >= IMX_W_POSITION_COMMAND_ERROR && op <= IMX_W_OBJECT_GOAL_DISTANCE);
+        lift = lift || (op >= IMX_W_OBJECT_IS_LIFTED && op <= IMX_W_OBJECT_GOAL_DISTANCE);
+        nav = nav || op >= IMX_W_NAV_POSITION_COMMAND_ERROR_TANH;
     }
     for (int k = 0; k < plan->nterm; ++k) {  // the terminations on the object
         const int32_t* r = &w[plan->term_off + k * IMX_REC_WORDS];
@@ -1202,7 +1091,11 @@ extern "C" int imx_terminations_rewards_rollout(const imx_plan_t* plan, int64_t 
     }
     reach = reach || lift;
     IMX_REQUIRE(!(classic && reach), "imx_terminations_rewards: a plan with both classic/humanoid and manipulation/reach or lift ops is not supported");
-    if (lift)
+    IMX_REQUIRE(!(nav && (classic || reach)), "imx_terminations_rewards: a plan with navigation reward ops beside classic/humanoid, reach or lift ops is not supported");
+    if (nav)
+        hipLaunchKernelGGL(k_term_rew_nav, dim3(grid), dim3(64 * NW), lds, (hipStream_t)stream, imx_plan_view(plan), N, *st, *bf, sc, frame, G,
+                           flags & 1, ro);
+    else if (lift)
         hipLaunchKernelGGL(k_term_rew_lift, dim3(grid), dim3(64 * NW), lds, (hipStream_t)stream, imx_plan_view(plan), N, *st, *bf, sc, frame, G,
                            flags & 1, ro);
     else if (classic)

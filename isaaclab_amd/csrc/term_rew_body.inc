@@ -358,6 +358,9 @@
                 f = sum * (truncated ? 0.0f : 1.0f);
             }
             if (CLASSIC && op >= IMX_W_UPRIGHT_POSTURE_BONUS) f = classic_reward(P, S, Bf, r, op, live ? e : min(grp * G, N - 1), N);
+#ifdef IMX_TR_NAV
+            if (op >= IMX_W_NAV_POSITION_COMMAND_ERROR_TANH) f = nav_reward(P, S, r, op, live ? e : min(grp * G, N - 1));
+#endif
 #ifdef IMX_TR_LIFT
             if (op >= IMX_W_POSITION_COMMAND_ERROR && op < IMX_W_OBJECT_IS_LIFTED) f = reach_reward(P, S, r, op, live ? e : min(grp * G, N - 1));
             if (op >= IMX_W_OBJECT_IS_LIFTED) f = lift_reward(P, S, r, op, live ? e : min(grp * G, N - 1));

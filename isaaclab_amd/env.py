@@ -58,6 +58,11 @@ def load_task_cfg(task: str) -> dict:
         env.setdefault("curriculum", extra.get("curriculum"))
         for k, v in (extra.get("scene") or {}).items():
             env["scene"].setdefault(k, v)
+    # a PreTrainedPolicyAction's policy_path given relative to the fixture file (the archive lies beside it)
+    for tcfg in (fx["env"].get("actions") or {}).values():
+        pp = tcfg.get("policy_path") if isinstance(tcfg, dict) else None
+        if isinstance(pp, str) and not os.path.isabs(pp) and os.path.isfile(os.path.join(os.path.dirname(os.path.abspath(path)), pp)):
+            tcfg["policy_path"] = os.path.join(os.path.dirname(os.path.abspath(path)), pp)
     return fx
 
 
@@ -215,6 +220,24 @@ class _OscActionTermView(_ActionTermView):
         return self._env._joint_efforts
 
 
+class _PolicyActionTermView(_ActionTermView):
+    """The PreTrainedPolicyAction term (isaaclab_tasks .../navigation/mdp/pre_trained_policy_action.py:70-84): ``processed_actions`` IS
+    ``raw_actions``, the tensor ``process_actions`` copies the action into -- here the term's columns of the processed action, which
+    no reset touches (the term has no ``reset``); ``low_level_actions`` and the low-level term's joint position targets."""
+
+    @property
+    def raw_actions(self):
+        return self.processed_actions
+
+    @property
+    def low_level_actions(self):
+        return self._env._ll_actions
+
+    @property
+    def joint_pos_target(self):
+        return self._env._ll_joint_pos_target
+
+
 class ActionManager:
     """View with the public surface of isaaclab/managers/action_manager.py:228-359."""
 
@@ -224,8 +247,10 @@ class ActionManager:
         c = 0
         ik_names = {ik.name for ik in env.plan.ik_terms}
         osc_names = {o.name for o in env.plan.osc_terms}
+        pp_names = {p.name for p in env.plan.policy_terms}
         for t in env.plan.action_terms:
-            view = _IkActionTermView if t.name in ik_names else _OscActionTermView if t.name in osc_names else _ActionTermView
+            view = _IkActionTermView if t.name in ik_names else _OscActionTermView if t.name in osc_names else \
+                _PolicyActionTermView if t.name in pp_names else _ActionTermView
             self._terms[t.name] = view(env, t.name, c, t.dim, t.processed_col, t.processed_dim)
             c += t.dim
 
@@ -262,6 +287,8 @@ class ActionManager:
             self._env._diff_ik(2)
         if self._env._osc is not None:  # ... and an OperationalSpaceControllerAction its joint efforts (:440-462)
             self._env._osc_launch(2)
+        if self._env._pp is not None:  # ... and a PreTrainedPolicyAction a low-level step every low_level_decimation calls
+            self._env._apply_low_level()
 
     def reset(self, env_ids=None) -> dict:
         ids = slice(None) if env_ids is None else env_ids
@@ -271,7 +298,8 @@ class ActionManager:
         # (inside env.step() the action kernel does this itself for the envs the step kernel reset).  A binary joint term zeroes its raw
         # action only (binary_joint_actions.py:135), and so does a DifferentialInverseKinematicsAction (task_space_actions.py:181-182: the
         # desired pose survives until the next process_action) and an OperationalSpaceControllerAction (:464-474: the controller's
-        # command is never reset): done above
+        # command is never reset): done above.  A PreTrainedPolicyAction has no reset of its own: its raw actions (the processed
+        # columns), low_level_actions and its counter stay
         for t in self._env.plan.action_terms:
             if t.func.rsplit(":", 1)[-1].rsplit(".", 1)[-1] == "EMAJointPositionToLimitsAction":
                 from .robots import resolve_matching_names
@@ -612,7 +640,8 @@ class ManagerBasedRLEnv:
                  device: str | torch.device | None = None, seed: int | None = None, noise_seed: int = 0,
                  terrain_cell: float = 0.0, use_command_term: bool = False, use_contact_sensor: bool = False,
                  events_cfg: dict | bool | None = None, use_curriculum: bool = False, terrain_importer=None, own_managers: bool = False,
-                 command_term=None, reward_curriculum: bool = False, **kwargs):
+                 command_term=None, reward_curriculum: bool = False, low_level_policy=None, fused_low_level: bool = True,
+                 low_level_tile_rows: int = 0, **kwargs):
         """``own_managers=True``: the env runs its cfg's EventManager (reset / interval terms), CommandManager (UniformVelocityCommand or
         UniformPoseCommand, by the term's ``class_type``) and CurriculumManager (terrain_levels_vel) itself -- ``_reset_idx`` + the
         command / interval updates of ``step`` as ONE orchestration launch (``imx_reset_orchestrate``) -- instead of taking commands
@@ -622,7 +651,11 @@ class ManagerBasedRLEnv:
         ``terrain_importer``: an ``events.TerrainImporterState`` (default: built from the cfg's terrain generator grid).
         ``reward_curriculum=True``: the CurriculumManager also builds the cfg's ``modify_reward_weight`` terms (the Reach and Lift tasks'
         curriculum) -- the weight switch happens on the device, inside the orchestration launch, at the reference's step; without the
-        keyword such a term is refused."""
+        keyword such a term is refused.
+        ``low_level_policy``: the policy of the cfg's PreTrainedPolicyAction -- the path of a TorchScript archive, an ``nn.Module`` or a
+        list of ``(W, b)`` pairs -- instead of the cfg's ``policy_path`` (``policy_loader.load_policy``).  ``fused_low_level=False`` runs
+        the low-level step as the chain of existing launches instead of ``imx_pretrained_policy``; ``low_level_tile_rows`` (0, 16, 32)
+        is the fused kernel's tile height, 0 = chosen by the number of envs."""
         if own_managers:
             ec = cfg.get("env", cfg) if isinstance(cfg, dict) else None
             ec = ec if ec is not None else (load_task_cfg(cfg)["env"] if isinstance(cfg, str) else cfg.to_dict())
@@ -719,6 +752,10 @@ class ManagerBasedRLEnv:
                 self._osc_target = self.feed["default_joint_pos"][:, o.joint_ids].contiguous()
             else:
                 self._osc_target = z(N, len(o.joint_ids))
+        # a PreTrainedPolicyAction's low-level step (imx_pretrained_policy): built below, once the persistent buffers exist
+        self._pp = plan.policy_terms[0] if plan.policy_terms else None
+        if self._pp is None and low_level_policy is not None:
+            raise ValueError("low_level_policy= was given but the cfg has no PreTrainedPolicyAction term")
         self._reward_buf = z(N)
         self._episode_sums = z(K, N)
         self._step_reward = z(N, K)
@@ -772,6 +809,8 @@ class ManagerBasedRLEnv:
         self._state_cache: dict[int, ImxState] = {}
         self._root_cache = None
 
+        if self._pp is not None:
+            self._init_low_level(low_level_policy, fused_low_level, low_level_tile_rows)
         self.action_manager = ActionManager(self)
         self.observation_manager = ObservationManager(self)
         self.reward_manager = RewardManager(self)
@@ -792,6 +831,10 @@ class ManagerBasedRLEnv:
                     raise ValueError(f"command_term='{command_term}': the env cfg has no such command term (it has {list(cmds)})")
                 ccfg = cmds[command_term]
                 cls = func_name_of(ccfg.get("class_type")) or ""
+                if command_width(ccfg) == 4:
+                    raise NotImplementedError(f"command_term='{command_term}': class_type '{cls}' (a pose-2d command: UniformPose2dCommand / "
+                                              "TerrainBasedPose2dCommand) has no fused producer yet; this cfg's (N, 4) command comes from "
+                                              "the state feed (drop command_term= / own_managers=True)")
                 if command_width(ccfg) == 7:
                     term = UniformPoseCommand(ccfg, N, plan.step_dt, self.device, seed=noise_seed, robot=plan.robot)
                 elif cls.endswith(":UniformVelocityCommand"):
@@ -1014,6 +1057,9 @@ class ManagerBasedRLEnv:
         if getattr(self, "_plan_h", None):
             self._lib.imx_plan_destroy(self._plan_h)
             self._plan_h = None
+        if getattr(self, "_ll_plan_h", None):
+            self._lib.imx_plan_destroy(self._ll_plan_h)
+            self._ll_plan_h = None
 
     def __del__(self):
         try:
@@ -1185,6 +1231,102 @@ class ManagerBasedRLEnv:
                                     self._ee_quat_des.data_ptr(), self._joint_pos_des.data_ptr(), self._joint_pos_des.shape[1],
                                     _lib.current_stream(self.device)))
 
+    # ---- PreTrainedPolicyAction: the low-level locomotion step ----------------------------------------------------------------
+    def _init_low_level(self, low_level_policy, fused: bool, tile_rows: int):
+        """The state of the cfg's PreTrainedPolicyAction (pre_trained_policy_action.py:34-68): the policy, ``low_level_actions``, the
+        low-level term's targets, and the low-level plan with buffers of its own -- its ``action`` is ``low_level_actions`` (what the
+        last_action op reads and the action record writes), its ``processed_action`` the joint position targets, and the state's
+        ``command`` the term's raw action (what the generated_commands op reads)."""
+        from .policy_loader import DevicePolicy, load_policy
+
+        pp, ll, N, dev = self._pp, self._pp.low_level_plan, self.num_envs, self.device
+        if tile_rows not in (0, 16, 32):
+            raise ValueError(f"low_level_tile_rows={tile_rows}: 0 (chosen by the number of envs), 16 or 32")
+        layers = load_policy(low_level_policy if low_level_policy is not None else pp.policy_path, pp.name)
+        if layers.dims[0] != ll.obs_dim or layers.dims[-1] != ll.action_dim:
+            raise ValueError(f"action term '{pp.name}': the low-level policy maps {layers.dims[0]} -> {layers.dims[-1]} columns; the "
+                             f"low-level observation group has {ll.obs_dim}, the low-level action term {ll.action_dim}")
+        self._ll_policy = DevicePolicy(layers, dev)
+        self._ll_fused, self._ll_tile_rows = bool(fused), int(tile_rows)
+        A, D = ll.action_dim, ll.obs_dim
+        z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
+        self._ll_actions, self._ll_prev, self._ll_joint_pos_target = z(N, A), z(N, A), z(N, A)
+        self._ll_obs, self._ll_out = z(N, D), z(N, A)  # the chain's intermediate rows (the fused kernel keeps them in LDS)
+        self._ll_counters = z(8, dtype=torch.int32)
+        self._ll_noise_u: torch.Tensor | None = None  # parity mode: (N, D) uniforms replacing the in-kernel draws
+        self._ll_obs_out: torch.Tensor | None = None  # debug: the fused kernel also writes its observation rows here
+        self._ll_counter = 0  # PreTrainedPolicyAction._counter (:94-100), kept across env steps
+        self._ll_in_step = 0  # low-level steps since the env step began: with the env's step counter the key of the noise draws
+        blob = np.ascontiguousarray(ll.blob, np.int32)
+        self._ll_plan_h = ctypes.c_void_p()
+        check(self._lib.imx_plan_create(blob.ctypes.data, blob.size, ctypes.byref(self._ll_plan_h)))
+        self._ll_scratch = torch.zeros(int(self._lib.imx_plan_scratch_bytes(self._ll_plan_h, N)), dtype=torch.uint8, device=dev)
+        self._ll_bufs = ImxBuffers(episode_length_buf=self._episode_length_buf.data_ptr(), action=self._ll_actions.data_ptr(),
+                                   prev_action=self._ll_prev.data_ptr(), processed_action=self._ll_joint_pos_target.data_ptr(),
+                                   counters=self._ll_counters.data_ptr(), obs=self._ll_obs.data_ptr(), scratch=self._ll_scratch.data_ptr())
+        self._ll_state_cache: dict[int, ImxState] = {}
+        dec = int(self._cfg_dict.get("decimation", 1))
+        self._ll_stride = -(-dec // pp.low_level_decimation) + 1  # more than the low-level steps of one env step
+
+    def _ll_state(self) -> ImxState:
+        """The low-level plan's state: this snapshot's tensors (per call, as in ``_diff_ik``), ``command`` = the term's raw action."""
+        idx = self.feed.index
+        st = self._ll_state_cache.get(idx)
+        if st is None:
+            snap = self.feed.snapshot(idx)
+            kw = {n: snap[n].data_ptr() for n in _lib.STATE_FIELDS if n in snap}
+            c0 = self._pp.action_col
+            raw = self._processed_action[:, c0:c0 + self._pp.width]
+            if not raw.is_contiguous():
+                raise _lib.ImxError(f"action term '{self._pp.name}': its raw action must be a contiguous (N, {self._pp.width}) tensor")
+            kw["command"] = raw.data_ptr()
+            st = ImxState(**kw)
+            self._ll_state_cache[idx] = st
+        return st
+
+    LL_SEED_SALT = 0x4C4C504F4C4943  # the low-level group's noise stream, apart from the env's own observation noise
+
+    def _ll_launch(self):
+        """One low-level step (pre_trained_policy_action.py:95-98): ``imx_pretrained_policy``, or with ``fused_low_level=False`` the
+        chain masked zero -> imx_observations -> imx_mlp_infer -> imx_action_process on the low-level plan.  No host sync."""
+        ll, N, st = self._pp.low_level_plan, self.num_envs, self._ll_state()
+        stream = _lib.current_stream(self.device)
+        seed = (self.noise_seed ^ self.LL_SEED_SALT) & 0xFFFFFFFFFFFFFFFF
+        corrupt = 1 if ll.enable_corruption else 0
+        offset = self._ll_in_step
+        self._ll_in_step += 1
+        if self._ll_fused:
+            check(self._lib.imx_pretrained_policy(self._ll_plan_h, N, ctypes.byref(st), ctypes.byref(self._ll_bufs),
+                                                  ctypes.byref(self._ll_policy.struct), _lib.ptr(self._ll_noise_u), seed,
+                                                  self._counters[2:3].data_ptr(), self._ll_stride, offset, corrupt, self._ll_tile_rows,
+                                                  _lib.ptr(self._ll_obs_out), stream))
+            return
+        # low_level_actions[episode_length_buf == 0, :] = 0 (last_action(), :53-57)
+        self._ll_actions.masked_fill_((self._episode_length_buf == 0).unsqueeze(1), 0.0)
+        torch.mul(self._counters[2:3], self._ll_stride, out=self._ll_counters[2:3])  # the fused kernel's noise key, for imx_observations
+        self._ll_counters[2:3].add_(offset)
+        check(self._lib.imx_observations(self._ll_plan_h, N, ctypes.byref(st), ctypes.byref(self._ll_bufs), None, _lib.ptr(self._ll_noise_u),
+                                         seed, corrupt, None, stream))
+        self._ll_policy.infer(self._ll_obs[:N], self._ll_out[:N])
+        check(self._lib.imx_action_process(self._ll_plan_h, N, self._ll_out.data_ptr(), math.inf, ctypes.byref(st),
+                                           ctypes.byref(self._ll_bufs), stream))
+
+    def _ll_check_schedule(self, capturing: bool):
+        """Under graph capture the launches of one env step are replayed for every later one: the counter's pattern must repeat."""
+        dec, lld = int(self.cfg_decimation), self._pp.low_level_decimation
+        if capturing and dec % lld != 0:
+            raise NotImplementedError(f"action term '{self._pp.name}': decimation {dec} is no multiple of low_level_decimation {lld}: the "
+                                      "low-level launches fall on different substeps from one env step to the next, which a captured "
+                                      "rollout cannot replay")
+
+    def _apply_low_level(self):
+        """``PreTrainedPolicyAction.apply_actions`` (:93-100): a low-level step when the counter is a multiple of
+        ``low_level_decimation``; the low-level term's ``apply_actions`` hands the targets to PhysX and leaves nothing to compute."""
+        if self._ll_counter % self._pp.low_level_decimation == 0:
+            self._ll_launch()
+            self._ll_counter = 0
+        self._ll_counter += 1
+
     def _eval_external(self, kind: str):
         for col, (term, fn) in enumerate(self._ext_funcs[kind] if kind != "obs" else ()):  # (each term is called ONCE per step: class terms keep state)
             if kind == "rew" and term.weight == 0.0:
@@ -1235,6 +1377,10 @@ class ManagerBasedRLEnv:
             raise ValueError(f"attach_actuator: the processed action of '{self._osc.name}' (OperationalSpaceControllerAction) is a task-space "
                              "command, not a row of joint targets; the term's output is joint_efforts "
                              f"(action_manager.get_term('{self._osc.name}').joint_efforts), for its {len(self._osc.joint_ids)} joints only")
+        if self._pp is not None:
+            raise ValueError(f"attach_actuator: the processed action of '{self._pp.name}' (PreTrainedPolicyAction) is the command of the "
+                             "low-level policy, not a row of joint targets; the term's targets are joint_pos_target "
+                             f"(action_manager.get_term('{self._pp.name}').joint_pos_target)")
         if self.plan.processed_action_dim != self.plan.num_joints:
             raise ValueError(f"attach_actuator: the action terms write {self.plan.processed_action_dim} joint targets, the robot has "
                              f"{self.plan.num_joints} joints")
@@ -1420,6 +1566,11 @@ class ManagerBasedRLEnv:
         if self._osc is not None:  # the OSC term's joint efforts, likewise once per physics substep
             for k in range(int(self.cfg_decimation)):
                 self._osc_launch(3 if (k == 0 and rollout_slot is not None) else 2)
+        if self._pp is not None:  # the PreTrainedPolicyAction's low-level steps, per its counter (also across env steps)
+            self._ll_check_schedule(torch.cuda.is_current_stream_capturing())
+            self._ll_in_step = 0
+            for _ in range(int(self.cfg_decimation)):
+                self._apply_low_level()
         self._sim_step_counter += int(self.cfg_decimation)
         self.feed.advance()
         if self.articulation is not None:

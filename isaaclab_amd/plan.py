@@ -48,12 +48,16 @@ _CLASSIC = "isaaclab_tasks.manager_based.classic.humanoid.mdp"  # its own module
 _REACH = "isaaclab_tasks.manager_based.manipulation.reach.mdp.rewards"
 _LIFT = "isaaclab_tasks.manager_based.manipulation.lift.mdp"  # .observations, .rewards, .terminations (Isaac-Lift-Cube-Franka-v0)
 _POSE_COMMAND = "isaaclab.envs.mdp.commands.pose_command:UniformPoseCommand"  # command = (N, 7): position + quaternion, base frame
+_NAV = "isaaclab_tasks.manager_based.navigation.mdp"  # .rewards, .pre_trained_policy_action (Isaac-Navigation-Flat-Anymal-C-v0)
+# command = (N, 4): pos_command_b 3 + heading_command_b 1 (pose_2d_command.py: UniformPose2dCommand.command and its terrain-based subclass)
+_POSE_2D_COMMANDS = tuple(f"isaaclab.envs.mdp.commands.pose_2d_command:{c}" for c in ("UniformPose2dCommand", "TerrainBasedPose2dCommand"))
 
 
 def command_width(command_cfg: dict | None) -> int:
-    """Width of a command term's ``command``: 7 for a ``UniformPoseCommand`` (pose_command.py:71-72), 3 for any other (the base velocity
-    command every other task uses)."""
-    return 7 if command_cfg is not None and func_name(command_cfg.get("class_type")) == _POSE_COMMAND else 3
+    """Width of a command term's ``command``: 7 for a ``UniformPoseCommand`` (pose_command.py:71-72), 4 for a ``UniformPose2dCommand`` /
+    ``TerrainBasedPose2dCommand`` (pose_2d_command.py), 3 for any other (the base velocity command every other task uses)."""
+    cls = func_name(command_cfg.get("class_type")) if command_cfg is not None else None
+    return 7 if cls == _POSE_COMMAND else 4 if cls in _POSE_2D_COMMANDS else 3
 
 
 def f32(x: float) -> float:
@@ -343,6 +347,21 @@ def resolve_osc_term(name: str, tcfg: dict, robot: RobotSpec, action_col: int = 
 
 
 @dataclasses.dataclass
+class PolicyTerm:
+    """One ``PreTrainedPolicyAction`` (isaaclab_tasks .../navigation/mdp/pre_trained_policy_action.py:24-100): its low-level observation
+    group and its low-level action term compiled as a plan of their own (``imx_pretrained_policy`` and the unfused chain run on it), the
+    launch period and where the policy comes from.  It travels beside the plan, not in its blob."""
+
+    name: str
+    action_col: int  # first raw (= processed) column; the term's raw action is its processed action (process_actions copies)
+    width: int  # action_dim: 3
+    low_level_decimation: int
+    policy_path: Any  # cfg.policy_path (a local file), or None: the env is given low_level_policy=
+    low_level_plan: "Plan"  # D = the policy's inputs, A = its outputs; generated_commands reads the raw action, last_action low_level_actions
+    low_level_action_name: str
+
+
+@dataclasses.dataclass
 class Plan:
     blob: np.ndarray  # int32 words
     robot: RobotSpec
@@ -380,6 +399,7 @@ class Plan:
     processed_action_dim: int = 0  # width of the processed action (= action_dim unless a term writes more joints than it takes columns)
     ik_terms: list = dataclasses.field(default_factory=list)  # IkTerm of the env's DifferentialInverseKinematicsAction (at most one)
     osc_terms: list = dataclasses.field(default_factory=list)  # OscTerm of the env's OperationalSpaceControllerAction (at most one, and no IkTerm beside it)
+    policy_terms: list = dataclasses.field(default_factory=list)  # PolicyTerm of the env's PreTrainedPolicyAction (at most one, no IK / OSC term beside it)
 
 
 @dataclasses.dataclass
@@ -523,7 +543,8 @@ class _Fused:
 # Closed modules -- Spot's rewards, the classic tasks' observations and rewards, the reach rewards -- have no Python fallback: a function
 # of theirs without a table entry is refused in the managers named here.  Any other unknown function is Python-evaluated (``EXTERNAL``).
 _CLOSED = {_SPOT: ("reward",), _REACH: ("reward",), **{f"{_CLASSIC}.{m}": ("termination", "reward", "observation") for m in ("observations", "rewards")},
-           **{f"{_LIFT}.{m}": ("termination", "reward", "observation") for m in ("observations", "rewards", "terminations")}}
+           **{f"{_LIFT}.{m}": ("termination", "reward", "observation") for m in ("observations", "rewards", "terminations")},
+           f"{_NAV}.rewards": ("reward",)}
 
 
 def _target_pos(kind: str, name: str, p: dict) -> list[float]:
@@ -740,6 +761,17 @@ def _reach_body(fn, c, name, p, rec):
     rec.update(ids_off=c.blob.ints(ids[:1]), nids=1)
 
 
+# -- the navigation task's own terms (isaaclab_tasks .../navigation/mdp/rewards.py: Isaac-Navigation-Flat-Anymal-C-v0)
+def _pose_2d_command(fn, c, name, p, rec):
+    """Each reads the (N, 4) pose-2d command: ``command_name`` must name a command term of the cfg that is 4 wide."""
+    cname = p.get("command_name")
+    ccfg = (c.cfg.get("commands") or {}).get(cname)
+    if ccfg is None:
+        raise ValueError(f"reward term '{name}': command_name '{cname}' is not a command term of the cfg (it has {list(c.cfg.get('commands') or {})})")
+    if command_width(ccfg) != 4 or c.cmd_dim != 4:
+        raise ValueError(f"reward term '{name}': {fn} reads a UniformPose2dCommand (N, 4); command '{cname}' is {command_width(ccfg)} wide")
+
+
 _W, _WV, _WS, _WC = f"{_MDP}.rewards:", f"{_VEL}.rewards:", f"{_SPOT}:", f"{_CLASSIC}.rewards:"
 REWARD_TERMS = {
     **{_W + f: _Fused(f.upper()) for f in ("is_alive", "is_terminated", "lin_vel_z_l2", "ang_vel_xy_l2", "flat_orientation_l2",
@@ -782,6 +814,10 @@ REWARD_TERMS = {
     _WC + "power_consumption": _Fused("POWER_CONSUMPTION", hook=_power_consumption),  # :114-140
     **{f"{_REACH}:{f}": _Fused(f.upper(), params=par, hook=functools.partial(_reach_body, f))
        for f, par in (("position_command_error", ()), ("position_command_error_tanh", ("std",)), ("orientation_command_error", ()))},
+    f"{_NAV}.rewards:position_command_error_tanh": _Fused("NAV_POSITION_COMMAND_ERROR_TANH", params=("std",),
+                                                          hook=functools.partial(_pose_2d_command, "position_command_error_tanh")),  # :17-22
+    f"{_NAV}.rewards:heading_command_error_abs": _Fused("NAV_HEADING_COMMAND_ERROR_ABS",
+                                                        hook=functools.partial(_pose_2d_command, "heading_command_error_abs")),  # :25-29
     f"{_LIFT}.rewards:object_is_lifted": _Fused("OBJECT_IS_LIFTED", params=("minimal_height",), hook=_object_is_lifted),  # :20-25
     f"{_LIFT}.rewards:object_ee_distance": _Fused("OBJECT_EE_DISTANCE", params=("std",), hook=_object_ee_distance),  # :28-45
     f"{_LIFT}.rewards:object_goal_distance": _Fused("OBJECT_GOAL_DISTANCE", params=("std", "minimal_height"), hook=_object_goal_distance),  # :48-67
@@ -859,6 +895,7 @@ _JOINT_ACTIONS = ("JointPositionAction", "JointVelocityAction", "JointEffortActi
 _BINARY_ACTIONS = ("BinaryJointPositionAction", "BinaryJointVelocityAction")
 _IK_ACTION = "isaaclab.envs.mdp.actions.task_space_actions:DifferentialInverseKinematicsAction"
 _OSC_ACTION = "isaaclab.envs.mdp.actions.task_space_actions:OperationalSpaceControllerAction"
+_POLICY_ACTION = f"{_NAV}.pre_trained_policy_action:PreTrainedPolicyAction"
 _NOISE_OPS = {"add": F_NOISE_ADD, "scale": F_NOISE_SCALE, "abs": F_NOISE_ABS}
 # noise function -> the scalar parameters in NOISE_LO / NOISE_HI, flag.  constant_noise: u * (b - b) + b == b for every u: the uniform
 # path, bit-identical
@@ -926,6 +963,7 @@ class PlanCompiler:
         self.processed_dim = 0  # columns of the processed action so far (a binary term writes more joints than it takes columns)
         self.ik_terms: list[IkTerm] = []
         self.osc_terms: list[OscTerm] = []
+        self.policy_terms: list[PolicyTerm] = []
         for name, tcfg in (self.cfg.get("actions") or {}).items():
             if tcfg is None or not isinstance(tcfg, dict) or "class_type" not in tcfg:
                 continue
@@ -935,7 +973,13 @@ class PlanCompiler:
                 self._binary_action(name, cls, tcfg)
                 continue
             if cls in (_IK_ACTION, _OSC_ACTION):
+                if self.policy_terms:
+                    raise NotImplementedError(f"action term '{name}': a {cname} beside the PreTrainedPolicyAction '{self.policy_terms[0].name}' is "
+                                              "not on the fused path")
                 self._task_space_action(name, cls, tcfg)
+                continue
+            if cls == _POLICY_ACTION:
+                self._policy_action(name, tcfg)
                 continue
             if cname not in _JOINT_ACTIONS:
                 raise NotImplementedError(f"action term '{name}': class {cls} is not on the fused path")
@@ -1039,6 +1083,77 @@ class PlanCompiler:
         self.act_recs.append(_rec(**rec))
         self.action_terms.append(Term(name, cls, A_JOINT_AFFINE, dict(tcfg), dim=dim, processed_col=self.processed_dim, processed_dim=dim))
         terms.append(term)
+        self.action_dim += dim
+        self.processed_dim += dim
+
+    def _policy_action(self, name: str, tcfg: dict) -> None:
+        """``PreTrainedPolicyAction`` (isaaclab_tasks .../navigation/mdp/pre_trained_policy_action.py:34-100).  raw -> processed is a copy
+        (``process_actions`` :90-91, ``action_dim`` 3 :73-74): the A_JOINT_AFFINE record with scale 1 and offset 0, as for the task-space
+        terms.  The low-level observation group and the low-level action term are compiled as a plan of their own: the term named
+        ``velocity_commands`` becomes a generated_commands op over a 3-wide command (the env points the state's command at this term's
+        raw action, :64), the term named ``actions`` a last_action op (the env points the buffers' action at low_level_actions, :53-62)."""
+        import copy
+
+        if self.policy_terms:
+            raise NotImplementedError(f"action term '{name}': a second PreTrainedPolicyAction (after '{self.policy_terms[0].name}'); the fused "
+                                      "path runs one per env")
+        task_space = self.ik_terms + self.osc_terms
+        if task_space:
+            raise NotImplementedError(f"action term '{name}': a PreTrainedPolicyAction beside the task-space term '{task_space[0].name}' is not "
+                                      "on the fused path")
+        lla, group = tcfg.get("low_level_actions"), tcfg.get("low_level_observations")
+        if not isinstance(lla, dict) or not isinstance(group, dict) or "class_type" not in lla:
+            raise NotImplementedError(f"action term '{name}': a PreTrainedPolicyAction cfg without low_level_actions / low_level_observations "
+                                      "is not on the fused path")
+        lld = int(tcfg.get("low_level_decimation", 4))
+        if lld < 1:
+            raise ValueError(f"action term '{name}': low_level_decimation {lld}")
+        ll_cls = func_name(lla["class_type"])
+        if _short(ll_cls)[1] not in _JOINT_ACTIONS:
+            raise NotImplementedError(f"action term '{name}': low-level action class {ll_cls} is not on the fused path (the joint classes "
+                                      f"{', '.join(_JOINT_ACTIONS)} are)")
+        for key in ("actions", "velocity_commands"):  # (the reference assigns cfg.low_level_observations.<key>.func, :63-66)
+            if not isinstance(group.get(key), dict):
+                raise ValueError(f"action term '{name}': the low-level observation group has no term '{key}' "
+                                 "(PreTrainedPolicyAction remaps the terms of these two names)")
+        if group.get("history_length"):
+            raise NotImplementedError(f"action term '{name}': a low-level observation group with history (history_length "
+                                      f"{group['history_length']}) is not on the fused path")
+        if not group.get("concatenate_terms", True):
+            raise NotImplementedError(f"action term '{name}': a low-level observation group with concatenate_terms=False feeds no policy")
+        group = copy.deepcopy(group)
+        for tname, ocfg in group.items():
+            if not isinstance(ocfg, dict) or "func" not in ocfg:
+                continue
+            if ocfg.get("history_length"):
+                raise NotImplementedError(f"action term '{name}': low-level observation term '{tname}' has history (history_length "
+                                          f"{ocfg['history_length']}); not on the fused path")
+            if ocfg.get("modifiers"):
+                raise NotImplementedError(f"action term '{name}': low-level observation term '{tname}' has modifiers; not on the fused path")
+        group["actions"].update(func=f"{_MDP}.observations:last_action", params={})
+        group["velocity_commands"].update(func=f"{_MDP}.observations:generated_commands", params={"command_name": None})
+        sub = {"sim": self.cfg["sim"], "decimation": self.cfg["decimation"], "episode_length_s": self.cfg["episode_length_s"],
+               "scene": self.cfg.get("scene") or {}, "actions": {"low_level": lla}, "observations": {"ll_policy": group}, "commands": {}}
+        try:
+            ll = PlanCompiler(sub, self.robot).compile()
+        except NotImplementedError as e:
+            raise NotImplementedError(f"action term '{name}': low-level {e}") from e
+        for t in ll.obs_terms:
+            if t.external is not None:
+                raise NotImplementedError(f"action term '{name}': low-level observation term '{t.name}' ({t.func}) would be evaluated in "
+                                          "Python; not on the fused path")
+            if t.op == O_OPS["HEIGHT_SCAN"]:
+                raise NotImplementedError(f"action term '{name}': low-level observation term '{t.name}' is a height scan (a rough-terrain "
+                                          "low-level policy); not on the fused path")
+        blob = self.blob
+        dim = 3
+        rec = dict(op=A_JOINT_AFFINE, ids_off=blob.ints([0] * dim), nids=dim, out=self.action_dim, dim=dim, p0=1.0, p1=0.0, flags=0)
+        if self.processed_dim != self.action_dim:
+            rec["p2"] = int(self.processed_dim)
+        self.act_recs.append(_rec(**rec))
+        self.action_terms.append(Term(name, _POLICY_ACTION, A_JOINT_AFFINE, dict(tcfg), dim=dim, processed_col=self.processed_dim, processed_dim=dim))
+        self.policy_terms.append(PolicyTerm(name=name, action_col=self.action_dim, width=dim, low_level_decimation=lld,
+                                            policy_path=tcfg.get("policy_path"), low_level_plan=ll, low_level_action_name="low_level"))
         self.action_dim += dim
         self.processed_dim += dim
 
@@ -1230,6 +1345,10 @@ class PlanCompiler:
     # -- header and tables
     def _assemble(self) -> Plan:
         cfg, robot, blob, groups, scene = self.cfg, self.robot, self.blob, self.groups, self.scene
+        if self.policy_terms and len(self.action_terms) > 1:
+            raise NotImplementedError(f"action term '{self.policy_terms[0].name}': a PreTrainedPolicyAction beside other action terms "
+                                      f"({[t.name for t in self.action_terms if t.name != self.policy_terms[0].name]}) is not on the fused "
+                                      "path: the low-level policy reads the term's raw action as the env's whole processed action")
         J, B = robot.num_joints, robot.num_bodies
         Hh, max_len, max_len_s, gdir = self.history, self.max_len, self.max_len_s, self.gravity_dir
         D = sum(g_.dim for g_ in groups)
@@ -1280,7 +1399,8 @@ class PlanCompiler:
                     enable_corruption=any(g_.enable_corruption for g_ in groups), ray_starts_local=ray_local, ray_direction=ray_dir,
                     ray_max_distance=self.ray_max, scanner_cfg=scanner, n_ext_rew=self.n_ext_rew, n_ext_term=self.n_ext_term,
                     n_ext_obs=self.n_ext_obs, gravity_dir=tuple(float(x) for x in gdir), mod_state_dim=self.mod_state,
-                    term_slots=len(self.term_slots), processed_action_dim=self.processed_dim, ik_terms=self.ik_terms, osc_terms=self.osc_terms)
+                    term_slots=len(self.term_slots), processed_action_dim=self.processed_dim, ik_terms=self.ik_terms, osc_terms=self.osc_terms,
+                    policy_terms=self.policy_terms)
 
 
 def compile_plan(env_cfg: Any, robot: RobotSpec) -> Plan:

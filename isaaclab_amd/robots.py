@@ -288,4 +288,7 @@ UR10 = RobotSpec(
     fixed_base=True,
 )
 
-ROBOTS = {r.name: r for r in (ANYMAL_C, G1, CARTPOLE, SPOT, ANT, HUMANOID, FRANKA_PANDA, UR10)}
+# ANYmal-C under the navigation task: the same articulation; the state feed serves the (N, 4) pose-2d command (command_dim = 4)
+ANYMAL_C_NAV = dataclasses.replace(ANYMAL_C, name="anymal_c_nav", command_dim=4)
+
+ROBOTS = {r.name: r for r in (ANYMAL_C, G1, CARTPOLE, SPOT, ANT, HUMANOID, FRANKA_PANDA, UR10, ANYMAL_C_NAV)}

@@ -220,6 +220,16 @@ def generate_pose_command(num_envs: int, gen: torch.Generator) -> torch.Tensor:
     return torch.cat([pos, q], dim=-1).contiguous()
 
 
+def generate_pose_2d_command(num_envs: int, gen: torch.Generator) -> torch.Tensor:
+    """``UniformPose2dCommand.command`` (N, 4) in the base frame (pose_2d_command.py): ``pos_command_b`` -- xy ~ U(-3, 3) as the
+    navigation cfg's ranges, z ~ U(-0.05, 0.05) (the target sits at the robot's default root height) -- and ``heading_command_b`` ~
+    U(-pi, pi)."""
+    u = torch.rand(num_envs, 4, generator=gen)
+    lo = torch.tensor([-3.0, -3.0, -0.05, -math.pi])
+    hi = torch.tensor([3.0, 3.0, 0.05, math.pi])
+    return (u * (hi - lo) + lo).contiguous()
+
+
 class StateFeed:
     """``S`` snapshots of the post-physics state held on ``device``; ``advance()`` moves to the next one.
 
@@ -253,8 +263,10 @@ class StateFeed:
             sn["object_root_pos_w"] = generate_object_offset(num_envs, gen_o)  # (the offset; the root position is added below)
             if robot.command_dim == 7:  # a pose command (the velocity command drawn above is dropped: other tensors keep their draws)
                 sn["command"] = generate_pose_command(num_envs, gen_c)
+            elif robot.command_dim == 4:  # the navigation task's pose-2d command, likewise
+                sn["command"] = generate_pose_2d_command(num_envs, gen_c)
             elif robot.command_dim != 3:
-                raise ValueError(f"robot {robot.name}: the feed serves 3- or 7-wide commands, not {robot.command_dim}")
+                raise ValueError(f"robot {robot.name}: the feed serves 3-, 4- or 7-wide commands, not {robot.command_dim}")
         for name in DYNAMIC + EXTRA:
             self._stack[name] = torch.stack([s[name] for s in snaps], dim=0).to(self.device).contiguous()
         # every snapshot keeps the same origins/defaults; root xy of later snapshots re-uses snapshot-0 origins

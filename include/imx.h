@@ -463,10 +463,30 @@ typedef struct imx_orch_manip imx_orch_manip_t;
 #include "imx_orch_manip.h" /* IMX_ORCH_MAX_WEIGHT_TERMS, imx_weight_term_t and the definition of imx_orch_manip_t */
 int imx_reset_orchestrate_manip(const imx_orch_t* orch, const imx_orch_manip_t* manip, imx_stream_t stream);
 
+/* ---- the pose-2d command term (Isaac-Navigation-Flat-Anymal-C-v0): imx_pose2d_command, imx_reset_orchestrate_pose2d -------------
+ * UniformPose2dCommand (isaaclab/envs/mdp/commands/pose_2d_command.py:26-143) and TerrainBasedPose2dCommand (:146-203) under
+ * CommandTerm.reset / compute (isaaclab/managers/command_manager.py:120-187), one lane per env (pose2d_command_env).  The term travels
+ * in imx_pose2d_command_t (imx_pose2d_struct.h, which this header includes): its cfg, the terrain's valid targets, the optional parity
+ * draws and its state / output buffers.
+ *   imx_pose2d_command: reset(the envs of reset_mask_d; NULL = none) and then, with do_compute, compute(dt), on the root pose given.
+ *     In-kernel draws are keyed by (seed, column, *step_counter_d (NULL = 0), env).
+ *   imx_reset_orchestrate_pose2d: what imx_reset_orchestrate does -- scene.reset, the reset events, the command term's reset and
+ *     compute in their place (envs/manager_based_rl_env.py:347-392, :215-236), the interval events -- with this term as the command
+ *     term.  imx_orch_t does not grow for it and orch->has_command must be 0; the sums of error_pos_2d / error_heading over the reset
+ *     envs leave in ev_part columns 0 / 1.  No terrain curriculum (orch->terrain_levels_d must be NULL).
+ * Every NULL pointer or out-of-range value is refused and named in imx_last_error before any launch. */
+typedef struct imx_pose2d_command imx_pose2d_command_t;
+#include "imx_pose2d_struct.h" /* the definition of imx_pose2d_command_t */
+int imx_pose2d_command(int64_t N, const imx_pose2d_command_t* cmd, float dt, int do_compute, const float* root_pos_w_d,
+                       const float* root_quat_w_d, const uint8_t* reset_mask_d, uint64_t seed, const int32_t* step_counter_d,
+                       imx_stream_t stream);
+int imx_reset_orchestrate_pose2d(const imx_orch_t* orch, const imx_pose2d_command_t* cmd, imx_stream_t stream);
+
 /* ---- library ---------------------------------------------------------------------------------------------------- */
 const char* imx_version(void);
 /* sizeof of an ABI struct as this library was compiled (which: 0 imx_state_t, 1 imx_buffers_t, 2 imx_head_loss_t, 3 imx_rollout_slot_t, 4 imx_policy_act_t, 5 imx_orch_t, 6 imx_event_term_t,
- * 7 imx_diff_ik_t, 8 imx_osc_t, 10 imx_orch_manip_t, 11 imx_weight_term_t, 12 imx_pretrained_policy_t), 0 for an unknown index (9 is one):
+ * 7 imx_diff_ik_t, 8 imx_osc_t, 10 imx_orch_manip_t, 11 imx_weight_term_t, 12 imx_pretrained_policy_t,
+ * 13 imx_pose2d_command_t), 0 for an unknown index (9 is one):
  * a binding checks its own layout against it at load time. */
 size_t imx_struct_size(int which);
 const char* imx_last_error(void);

@@ -165,5 +165,9 @@ try:
     with open(POLICY_HEADER) as _f:
         _policy_defines, _, POLICY_STRUCTS, _ = parse(_f.read(), POLICY_HEADER, DEFINES)
     DEFINES.update(_policy_defines)  # IMX_PP_MAX_LAYERS
+    # imx_pose2d_struct.h, likewise: imx_pose2d_command_t (imx_pose2d_command, imx_reset_orchestrate_pose2d)
+    POSE2D_HEADER = os.path.join(os.path.dirname(HEADER), "imx_pose2d_struct.h")
+    with open(POSE2D_HEADER) as _f:
+        _, _, POSE2D_STRUCTS, _ = parse(_f.read(), POSE2D_HEADER, DEFINES)
 except OSError as e:
     raise AbiError(f"the ABI header {HEADER} cannot be read ({e}): the whole binding is derived from it") from e

@@ -36,6 +36,7 @@ extern "C" size_t imx_struct_size(int which) {
         case 10: return sizeof(imx_orch_manip_t);
         case 11: return sizeof(imx_weight_term_t);
         case 12: return sizeof(imx_pretrained_policy_t);
+        case 13: return sizeof(imx_pose2d_command_t);
         default: return 0;
     }
 }

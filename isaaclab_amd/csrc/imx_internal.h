@@ -129,30 +129,6 @@ static __host__ __device__ __forceinline__ int imx_cell_index(int ix, int iy, in
 
 IMX_DEV float f_of(int32_t w) { return __int_as_float(w); }
 
-// quat_rotate_inverse (isaaclab/utils/math.py:605-625): a - b + c with
-//   a = v*(2 w^2 - 1), b = cross(q_vec, v)*w*2, c = q_vec*dot(q_vec, v)*2   (same association as the reference)
-IMX_DEV void quat_rotate_inverse(float w, float x, float y, float z, float vx, float vy, float vz, float& ox, float& oy,
-                                 float& oz) {
-    const float s = 2.0f * (w * w) - 1.0f;
-    const float ax = vx * s, ay = vy * s, az = vz * s;
-    const float cx = y * vz - z * vy, cy = z * vx - x * vz, cz = x * vy - y * vx;
-    const float bx = cx * w * 2.0f, by = cy * w * 2.0f, bz = cz * w * 2.0f;
-    const float d = (x * vx + y * vy) + z * vz;  // bmm: sequential dot
-    const float ccx = x * d * 2.0f, ccy = y * d * 2.0f, ccz = z * d * 2.0f;
-    ox = ax - bx + ccx;
-    oy = ay - by + ccy;
-    oz = az - bz + ccz;
-}
-
-// yaw_quat (isaaclab/utils/math.py:521-542) -> (qw, qz) of the yaw-only quaternion (x = y = 0)
-IMX_DEV void yaw_quat_wz(float w, float x, float y, float z, float& yw, float& yz) {
-    const float yaw = atan2f(2.0f * (w * z + x * y), 1.0f - 2.0f * (y * y + z * z));
-    const float s = sinf(yaw * 0.5f), c = cosf(yaw * 0.5f);
-    const float n = fmaxf(sqrtf(c * c + s * s), 1.0e-9f);  // normalize(): x / norm.clamp(min=eps)
-    yw = c / n;
-    yz = s / n;
-}
-
 // quat_apply (isaaclab/utils/math.py:545-564) for a yaw-only quaternion (w,0,0,z):
 //   t = 2*cross(xyz, v);  out = v + w*t + cross(xyz, t)
 IMX_DEV void quat_apply_yaw_only(float w, float z, float vx, float vy, float vz, float& ox, float& oy, float& oz) {
@@ -164,7 +140,8 @@ IMX_DEV void quat_apply_yaw_only(float w, float z, float vx, float vy, float vz,
     oz = vz + w * tz + (0.0f * ty - 0.0f * tx);
 }
 
-// quat_apply, quat_mul_ref and axis_angle_from_quat_ref live in imx_quat.h (shared with host C++)
+// quat_apply, quat_rotate_inverse, yaw_quat_wz, wrap_to_pi, uniform01, quat_mul_ref and axis_angle_from_quat_ref live in imx_quat.h
+// (shared with host C++)
 // ||axis_angle_from_quat(d)|| (utils/math.py:646-675) step by step: the w < 0 flip (q * (1 - 2 (w < 0))), half = atan2(||xyz||, w),
 // angle = 2 half, the |angle| <= 1e-6 Taylor branch 0.5 - angle^2 / 48, then xyz / that factor and its norm
 IMX_DEV float axis_angle_magnitude(float4 d) {
@@ -178,19 +155,11 @@ IMX_DEV float axis_angle_magnitude(float4 d) {
     return sqrtf((ax * ax + ay * ay) + az * az);
 }
 
-// wrap_to_pi (isaaclab/utils/math.py:95-117), torch.remainder semantics
 // reset_joints_around_default (isaaclab_tasks/.../velocity/config/spot/mdp/events.py:48-58): lo/hi = clamp(default + range, limits),
 // then sample_uniform (utils/math.py:1313-1331) = u * (hi - lo) + lo
 IMX_DEV float around_default(float d, float r_lo, float r_hi, float lim_lo, float lim_hi, float u) {
     const float lo = fminf(fmaxf(d + r_lo, lim_lo), lim_hi), hi = fminf(fmaxf(d + r_hi, lim_lo), lim_hi);
     return u * (hi - lo) + lo;
-}
-
-IMX_DEV float wrap_to_pi(float a) {
-    const float PI = 3.14159265358979323846f, TWO_PI = 6.28318530717958647692f;
-    float m = fmodf(a + PI, TWO_PI);
-    if (m != 0.0f && m < 0.0f) m += TWO_PI;
-    return (m == 0.0f && a > 0.0f) ? PI : m - PI;
 }
 
 #define IMX_HALF_LOG_2PI 0.91893853320467274178f
@@ -258,14 +227,3 @@ int imx_check_action_inputs(const imx_plan_t* plan, const imx_state_t* st, const
 
 IMX_DEV float norm3(float x, float y, float z) { return sqrtf((x * x + y * y) + z * z); }
 
-// counter-based uniform [0,1): two rounds of a 32-bit multiply-xorshift hash (Wellons' "lowbias32") over
-// (seed, step, element index); 24-bit mantissa like torch.rand.  ~12 VALU ops (a 64-bit splitmix cost ~40).
-IMX_DEV float uniform01(uint64_t seed, uint32_t step, uint64_t idx) {
-    uint32_t x = (uint32_t)idx ^ ((uint32_t)(idx >> 32) * 0x9E3779B9u) ^ (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x85EBCA6Bu);
-    x += step * 0x9E3779B9u + 0x7F4A7C15u;
-    x ^= x >> 16; x *= 0x7FEB352Du;
-    x ^= x >> 15; x *= 0x846CA68Bu;
-    x ^= x >> 16;
-    x += step; x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15;
-    return (float)(x >> 8) * (1.0f / 16777216.0f);
-}

@@ -209,3 +209,8 @@ static inline PoseCmdCfg pose_cmd_cfg_from16(const float* cfg16, int make_quat_u
     c.body_idx = body_idx; c.num_bodies = num_bodies;
     return c;
 }
+
+// ------------------------------------------------------------------------------------------------- pose-2d command
+// pose2d_command_env (UniformPose2dCommand / TerrainBasedPose2dCommand, envs/mdp/commands/pose_2d_command.py) lives in a file of its
+// own that also compiles as host C++ (tools/pose2d_host.cpp)
+#include "imx_pose2d.h"

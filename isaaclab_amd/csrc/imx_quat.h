@@ -26,6 +26,50 @@ IMX_HD void quat_apply(float w, float x, float y, float z, float vx, float vy, f
     oz = vz + w * tz + (x * ty - y * tx);
 }
 
+// quat_rotate_inverse (isaaclab/utils/math.py:605-625): a - b + c with
+//   a = v*(2 w^2 - 1), b = cross(q_vec, v)*w*2, c = q_vec*dot(q_vec, v)*2   (same association as the reference)
+IMX_HD void quat_rotate_inverse(float w, float x, float y, float z, float vx, float vy, float vz, float& ox, float& oy,
+                                 float& oz) {
+    const float s = 2.0f * (w * w) - 1.0f;
+    const float ax = vx * s, ay = vy * s, az = vz * s;
+    const float cx = y * vz - z * vy, cy = z * vx - x * vz, cz = x * vy - y * vx;
+    const float bx = cx * w * 2.0f, by = cy * w * 2.0f, bz = cz * w * 2.0f;
+    const float d = (x * vx + y * vy) + z * vz;  // bmm: sequential dot
+    const float ccx = x * d * 2.0f, ccy = y * d * 2.0f, ccz = z * d * 2.0f;
+    ox = ax - bx + ccx;
+    oy = ay - by + ccy;
+    oz = az - bz + ccz;
+}
+
+// yaw_quat (isaaclab/utils/math.py:521-542) -> (qw, qz) of the yaw-only quaternion (x = y = 0)
+IMX_HD void yaw_quat_wz(float w, float x, float y, float z, float& yw, float& yz) {
+    const float yaw = atan2f(2.0f * (w * z + x * y), 1.0f - 2.0f * (y * y + z * z));
+    const float s = sinf(yaw * 0.5f), c = cosf(yaw * 0.5f);
+    const float n = fmaxf(sqrtf(c * c + s * s), 1.0e-9f);  // normalize(): x / norm.clamp(min=eps)
+    yw = c / n;
+    yz = s / n;
+}
+
+// wrap_to_pi (isaaclab/utils/math.py:95-117), torch.remainder semantics
+IMX_HD float wrap_to_pi(float a) {
+    const float PI = 3.14159265358979323846f, TWO_PI = 6.28318530717958647692f;
+    float m = fmodf(a + PI, TWO_PI);
+    if (m != 0.0f && m < 0.0f) m += TWO_PI;
+    return (m == 0.0f && a > 0.0f) ? PI : m - PI;
+}
+
+// counter-based uniform [0,1): two rounds of a 32-bit multiply-xorshift hash (Wellons' "lowbias32") over
+// (seed, step, element index); 24-bit mantissa like torch.rand.  ~12 VALU ops (a 64-bit splitmix cost ~40).
+IMX_HD float uniform01(uint64_t seed, uint32_t step, uint64_t idx) {
+    uint32_t x = (uint32_t)idx ^ ((uint32_t)(idx >> 32) * 0x9E3779B9u) ^ (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x85EBCA6Bu);
+    x += step * 0x9E3779B9u + 0x7F4A7C15u;
+    x ^= x >> 16; x *= 0x7FEB352Du;
+    x ^= x >> 15; x *= 0x846CA68Bu;
+    x ^= x >> 16;
+    x += step; x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15;
+    return (float)(x >> 8) * (1.0f / 16777216.0f);
+}
+
 // quat_rotate (sign +1) / quat_rotate_inverse (sign -1) (utils/math.py:583-625): a +- b + c.  Not quat_apply: the two round differently.
 IMX_HD void quat_rotate_ref(float4 q, float sign, float vx, float vy, float vz, float& ox, float& oy, float& oz) {
     const float w = q.x, x = q.y, y = q.z, z = q.w;

@@ -35,8 +35,10 @@ __device__ __forceinline__ float wsum(float v) {
 // the velocity cfgs run the register budget they always had, dispatched on the host.  MANIP: the manipulation tasks' launch
 // (imx_reset_orchestrate_manip) -- reset_scene_to_default, events on the scene's rigid object and the modify_reward_weight curriculum,
 // with imx_orch_manip_t as a second kernel argument; again an instantiation of its own (k_reset_orchestrate_manip below)
-template <bool POSE, bool MANIP>
-__device__ __forceinline__ void orch_body(const imx_orch_t& o, const imx_orch_manip_t* mp) {
+// P2D: the command term is a pose-2d command (imx_reset_orchestrate_pose2d; imx_pose2d_command_t as a second kernel argument, has_command
+// is 0): the third instantiation of its own (k_reset_orchestrate_pose2d below), no terrain curriculum
+template <bool POSE, bool MANIP, bool P2D = false>
+__device__ __forceinline__ void orch_body(const imx_orch_t& o, const imx_orch_manip_t* mp, const imx_pose2d_command_t* pc = nullptr) {
     const int lane = threadIdx.x;
     const int64_t N = o.num_envs;
     const int64_t e0 = (int64_t)blockIdx.x * ORCH_BLOCK + lane;
@@ -49,7 +51,7 @@ __device__ __forceinline__ void orch_body(const imx_orch_t& o, const imx_orch_ma
     // ---- CurriculumManager.compute: terrain_levels_vel (curriculums.py:26-55) + update_env_origins (terrain_importer.py:307-326)
     float ox = o.env_origins_d[e * 3], oy = o.env_origins_d[e * 3 + 1], oz = o.env_origins_d[e * 3 + 2];
     float level_f = 0.0f;
-    if (!MANIP && o.terrain_levels_d) {
+    if (!MANIP && !P2D && o.terrain_levels_d) {
         int64_t lv = o.terrain_levels_d[e];
         if (reset) {
             const float dx = o.root_pos_w_d[e * 3] - ox, dy = o.root_pos_w_d[e * 3 + 1] - oy;
@@ -246,7 +248,9 @@ __device__ __forceinline__ void orch_body(const imx_orch_t& o, const imx_orch_ma
         pose_command_env(N, e, c, o.dt, o.do_step, o.root_pos_w_d, o.root_quat_w_d, o.body_pos_w_d, o.body_quat_w_d, reset,
                          o.command_uniforms_d, o.seed ^ 0xC0FFEEull, step, st, mxy0, myaw0);
     }
-    if (!POSE && o.has_command && live) {
+    if (P2D && live)  // the same place, the same reset flag and the same two log columns (error_pos_2d, error_heading)
+        pose2d_command_env(N, e, *pc, o.dt, o.do_step, o.root_pos_w_d, o.root_quat_w_d, reset, o.seed ^ 0xC0FFEEull, step, mxy0, myaw0);
+    if (!POSE && !P2D && o.has_command && live) {
         VelCmdCfg c;
         c.resample_lo = o.command_cfg[0]; c.resample_hi = o.command_cfg[1];
         c.lin_x_lo = o.command_cfg[2]; c.lin_x_hi = o.command_cfg[3]; c.lin_y_lo = o.command_cfg[4]; c.lin_y_hi = o.command_cfg[5];
@@ -326,17 +330,24 @@ __global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate_manip(imx_orch
     orch_body<true, true>(o, &m);
 }
 
+__global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate_pose2d(imx_orch_t o, imx_pose2d_command_t c) {
+    orch_body<false, false, true>(o, nullptr, &c);
+}
+
 }  // namespace
 
 extern "C" size_t imx_orch_part_floats(int64_t num_envs) { return num_envs > 0 ? (size_t)((num_envs + ORCH_BLOCK - 1) / ORCH_BLOCK) * 4 : 0; }
 
-// the argument checks of both entry points (m = NULL: imx_reset_orchestrate) and the launch
-static int orch_launch(const imx_orch_t* o, const imx_orch_manip_t* m, imx_stream_t stream) {
+// the argument checks of the entry points (m = NULL and pc = NULL: imx_reset_orchestrate; pc: imx_reset_orchestrate_pose2d) and the launch
+static int orch_launch(const imx_orch_t* o, const imx_orch_manip_t* m, imx_stream_t stream, const imx_pose2d_command_t* pc = nullptr) {
     IMX_REQUIRE(o, "imx_reset_orchestrate: null descriptor");
     IMX_REQUIRE(o->num_envs > 0 && o->num_envs < (1ll << 31), "imx_reset_orchestrate: num_envs out of range");
     IMX_REQUIRE(o->num_terms >= 0 && o->num_terms <= IMX_ORCH_MAX_TERMS, "imx_reset_orchestrate: %d event terms (at most %d)", o->num_terms,
                 IMX_ORCH_MAX_TERMS);
     IMX_REQUIRE(o->env_origins_d, "imx_reset_orchestrate: env_origins missing");
+    if (pc)
+        IMX_REQUIRE(o->has_command == 0, "imx_reset_orchestrate_pose2d: has_command is %d: the pose-2d command travels in "
+                    "imx_pose2d_command_t, has_command must be 0 here", o->has_command);
     bool need_root = false, need_vel = false;
     for (int t = 0; t < o->num_terms; ++t) {
         const imx_event_term_t& T = o->terms[t];
@@ -424,7 +435,14 @@ static int orch_launch(const imx_orch_t* o, const imx_orch_manip_t* m, imx_strea
     if (o->lstm_hidden_d) IMX_REQUIRE(o->lstm_cell_d && o->lstm_layers > 0 && o->lstm_hidden_dim > 0 && o->num_joints > 0,
                                       "imx_reset_orchestrate: incomplete actuator-net state");
     const unsigned grid = (unsigned)((o->num_envs + ORCH_BLOCK - 1) / ORCH_BLOCK);
-    if (m) {
+    if (pc) {
+        IMX_REQUIRE(!o->terrain_levels_d, "imx_reset_orchestrate_pose2d: the terrain curriculum (terrain_levels_vel) reads a velocity command "
+                    "and moves env_origins; it is not part of this launch");
+        if (const char* why = pose2d_command_check(pc)) IMX_FAIL("imx_reset_orchestrate_pose2d: %s", why);
+        IMX_REQUIRE(o->root_pos_w_d, "imx_reset_orchestrate_pose2d: root_pos_w missing");
+        IMX_REQUIRE(o->root_quat_w_d, "imx_reset_orchestrate_pose2d: root_quat_w missing");
+        hipLaunchKernelGGL(k_reset_orchestrate_pose2d, dim3(grid), dim3(ORCH_BLOCK), 0, (hipStream_t)stream, *o, *pc);
+    } else if (m) {
         IMX_REQUIRE(o->has_command != 1, "imx_reset_orchestrate_manip: the command term is a velocity command (has_command 0 or 2 here)");
         IMX_REQUIRE(!o->terrain_levels_d, "imx_reset_orchestrate_manip: the terrain curriculum is not part of this launch");
         IMX_REQUIRE(m->num_weight_terms >= 0 && m->num_weight_terms <= IMX_ORCH_MAX_WEIGHT_TERMS,
@@ -450,4 +468,9 @@ extern "C" int imx_reset_orchestrate(const imx_orch_t* o, imx_stream_t stream) {
 extern "C" int imx_reset_orchestrate_manip(const imx_orch_t* o, const imx_orch_manip_t* m, imx_stream_t stream) {
     IMX_REQUIRE(m, "imx_reset_orchestrate_manip: null imx_orch_manip_t");
     return orch_launch(o, m, stream);
+}
+
+extern "C" int imx_reset_orchestrate_pose2d(const imx_orch_t* o, const imx_pose2d_command_t* cmd, imx_stream_t stream) {
+    IMX_REQUIRE(cmd, "imx_reset_orchestrate_pose2d: null imx_pose2d_command_t");
+    return orch_launch(o, nullptr, stream, cmd);
 }

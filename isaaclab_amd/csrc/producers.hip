@@ -4,6 +4,7 @@
 //   * CommandManager.compute / UniformVelocityCommand (isaaclab/managers/command_manager.py:122-187,
 //     isaaclab/envs/mdp/commands/velocity_command.py:111-160): metrics, resampling timer, uniform resampling,
 //     heading P-controller (wrap_to_pi), standing envs.
+//   * CommandManager.compute / UniformPose2dCommand, TerrainBasedPose2dCommand (isaaclab/envs/mdp/commands/pose_2d_command.py:26-203)
 //   * CommandManager.compute / UniformPoseCommand (isaaclab/envs/mdp/commands/pose_command.py:25-127): pose error metrics through the
 //     root pose, resampling timer, uniform position + Euler angle resampling (quat_from_euler_xyz, quat_unique).
 #include "imx_internal.h"
@@ -153,6 +154,32 @@ extern "C" int imx_pose_command(int64_t N, const float* cfg16, int make_quat_uni
     PoseCmdState st{pose_command_b_d, pose_command_w_d, time_left_d, command_counter_d, metric_position_error_d, metric_orientation_error_d};
     hipLaunchKernelGGL(k_pose_command, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, N, c, dt, do_compute,
                        root_pos_w_d, root_quat_w_d, body_pos_w_d, body_quat_w_d, reset_mask_d, uniforms_d, seed, step_counter_d, st);
+    IMX_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------- pose-2d command
+// lane = env (the per-env logic is pose2d_command_env, imx_pose2d.h: shared with the orchestration kernel); no LDS, no atomics
+__global__ void __launch_bounds__(256)
+k_pose2d_command(int64_t N, imx_pose2d_command_t c, float dt, int do_compute, const float* __restrict__ root_pos,
+                 const float* __restrict__ root_quat, const uint8_t* __restrict__ reset_mask, uint64_t seed,
+                 const int32_t* __restrict__ step_d) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    const uint32_t step = step_d ? (uint32_t)step_d[0] : 0u;
+    float m0, m1;
+    pose2d_command_env(N, e, c, dt, do_compute, root_pos, root_quat, reset_mask && reset_mask[e], seed, step, m0, m1);
+}
+
+extern "C" int imx_pose2d_command(int64_t N, const imx_pose2d_command_t* cmd, float dt, int do_compute, const float* root_pos_w_d,
+                                  const float* root_quat_w_d, const uint8_t* reset_mask_d, uint64_t seed, const int32_t* step_counter_d,
+                                  imx_stream_t stream) {
+    IMX_REQUIRE(N > 0 && N < (1ll << 31), "imx_pose2d_command: N out of range");
+    if (const char* why = pose2d_command_check(cmd)) IMX_FAIL("imx_pose2d_command: %s", why);
+    IMX_REQUIRE(root_pos_w_d, "imx_pose2d_command: root_pos_w missing");
+    IMX_REQUIRE(root_quat_w_d, "imx_pose2d_command: root_quat_w missing");
+    hipLaunchKernelGGL(k_pose2d_command, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, N, *cmd, dt, do_compute,
+                       root_pos_w_d, root_quat_w_d, reset_mask_d, seed, step_counter_d);
     IMX_HIP(hipGetLastError());
     return 0;
 }

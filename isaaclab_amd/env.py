@@ -647,7 +647,8 @@ class ManagerBasedRLEnv:
         command / interval updates of ``step`` as ONE orchestration launch (``imx_reset_orchestrate``) -- instead of taking commands
         from the feed; the single switches (``events_cfg`` = a dict or True for the cfg's own, ``command_term``, ``use_curriculum``)
         select parts of it.  ``command_term``: the name of a command term of the cfg (``"ee_pose"``, ``"base_velocity"``), built by its
-        ``class_type``, or a ready ``producers.Uniform*Command``; ``use_command_term=True`` is the older velocity-only switch.
+        ``class_type``, or a ready ``producers.Uniform*Command`` -- the only form a pose-2d command (``producers.UniformPose2dCommand`` /
+        ``TerrainBasedPose2dCommand``, run by ``imx_reset_orchestrate_pose2d``) is accepted in; ``use_command_term=True`` is the older velocity-only switch.
         ``terrain_importer``: an ``events.TerrainImporterState`` (default: built from the cfg's terrain generator grid).
         ``reward_curriculum=True``: the CurriculumManager also builds the cfg's ``modify_reward_weight`` terms (the Reach and Lift tasks'
         curriculum) -- the weight switch happens on the device, inside the orchestration launch, at the reference's step; without the
@@ -822,7 +823,7 @@ class ManagerBasedRLEnv:
         cmds = (env_dict.get("commands") or {})
         if command_term is not None:
             from .plan import command_width
-            from .producers import UniformPoseCommand, UniformVelocityCommand
+            from .producers import UniformPose2dCommand, UniformPoseCommand, UniformVelocityCommand
 
             if use_command_term:
                 raise ValueError("pass either command_term= or use_command_term=True, not both")
@@ -843,10 +844,15 @@ class ManagerBasedRLEnv:
                     raise NotImplementedError(f"command_term='{command_term}': class_type '{cls}' has no fused producer (UniformVelocityCommand "
                                               "and UniformPoseCommand have)")
                 self.command_term_name = command_term
-            elif isinstance(command_term, (UniformPoseCommand, UniformVelocityCommand)):
+            elif isinstance(command_term, (UniformPoseCommand, UniformVelocityCommand, UniformPose2dCommand)):
                 term = command_term
                 if term.num_envs != N or term.device != self.device:
                     raise ValueError(f"command_term: the term has {term.num_envs} envs on {term.device}, the env {N} on {self.device}")
+                if isinstance(term, UniformPose2dCommand) and (use_curriculum or reward_curriculum):
+                    # (the launch of a pose-2d command, imx_reset_orchestrate_pose2d, has neither curriculum: terrain_levels_vel reads a
+                    # velocity command and moves the origins the targets are drawn around, modify_reward_weight runs in the manipulation launch)
+                    raise NotImplementedError(f"command_term: a {type(term).__name__} beside use_curriculum=True / reward_curriculum=True is not "
+                                              "built: the launch that runs a pose-2d command has no terrain curriculum and switches no reward weights")
                 if isinstance(term, UniformPoseCommand) and term.num_bodies != plan.robot.num_bodies:
                     raise ValueError(f"command_term: the pose command was built for {term.num_bodies} bodies, the robot has {plan.robot.num_bodies}")
                 self.command_term_name = next(iter(cmds), "command")
@@ -870,6 +876,10 @@ class ManagerBasedRLEnv:
             raise ValueError(f"the state feed's command is {state_feed['command'].shape[-1]} wide, the plan's {plan.cmd_dim} "
                              f"(robot {state_feed.robot.name}: command_dim {state_feed.robot.command_dim})")
         self._pose_command = self.command_term is not None and self.command_term.command.shape[-1] == 7  # has_command = 2
+        # a producers.UniformPose2dCommand / TerrainBasedPose2dCommand: has_command = 0, the term travels in imx_pose2d_command_t
+        from .producers import UniformPose2dCommand as _Pose2d
+
+        self._pose2d_command = isinstance(self.command_term, _Pose2d)
         self.contact_sensor = None
         if use_contact_sensor:
             from .producers import ContactSensorState
@@ -891,7 +901,7 @@ class ManagerBasedRLEnv:
             from .producers import ArticulationRootState
 
             self.articulation = ArticulationRootState(N, plan.num_joints, self.device)
-        self._orch = self._orch_manip = None
+        self._orch = self._orch_manip = self._orch_pose2d = None
         self._weight_switch_step = None  # one device word per modify_reward_weight term (imx_weight_term_t.switch_step_d)
         J = plan.num_joints
         if events_cfg:
@@ -938,6 +948,12 @@ class ManagerBasedRLEnv:
             drs[:, 7:10] = torch.tensor(init.get("lin_vel", (0.0, 0.0, 0.0)), device=self.device)
             drs[:, 10:13] = torch.tensor(init.get("ang_vel", (0.0, 0.0, 0.0)), device=self.device)
             self.default_root_state = drs
+            if self._pose2d_command:  # scene.env_origins and default_root_state[:, 2]: the env's own, or the term's checked against them
+                ct, origins = self.command_term, state_feed["env_origins"]
+                for name, mine, given in (("env_origins", origins, ct.env_origins_given), ("default_root_z", drs[:, 2], ct.default_root_z_given)):
+                    if given and not torch.equal(getattr(ct, name), mine):
+                        raise ValueError(f"command_term: the term's {name} differs from the env's (leave {name}= out and the env fills its own in)")
+                    getattr(ct, name).copy_(mine)
             NB = plan.robot.num_bodies
             self.sim_writes = {"root_pose": torch.zeros(N, 7, device=self.device), "root_vel": torch.zeros(N, 6, device=self.device),
                                "joint_pos": torch.zeros(N, J, device=self.device), "joint_vel": torch.zeros(N, J, device=self.device),
@@ -970,7 +986,14 @@ class ManagerBasedRLEnv:
         self._log_index.update({"Episode_Termination/" + n: len(names_r) + i for i, n in enumerate(names_t)})
         base = len(names_r) + len(names_t) + 1  # (the slot before holds the reset count)
         ev_flags = 0
-        if self.command_term is not None:  # CommandManager.reset (command_manager.py:340-358): "Metrics/{term}/{metric}"
+        if self._pose2d_command:
+            # UniformPose2dCommand's metrics as the reference logs them (pose_2d_command.py:60-61, :84-85): error_pos_2d and error_heading
+            # are the launch's two columns; error_pos is created, never written and still logged -- the third slot, which only a terrain
+            # curriculum would write, stays 0 for it
+            for m, i in (("error_pos", 2), ("error_heading", 1), ("error_pos_2d", 0)):
+                self._log_index[f"Metrics/{self.command_term_name}/{m}"] = base + i
+            ev_flags |= 1
+        elif self.command_term is not None:  # CommandManager.reset (command_manager.py:340-358): "Metrics/{term}/{metric}"
             if len(self.command_term.metrics) != 2:
                 raise ValueError("the step tail has two log slots for the command term's metrics")
             for i, m in enumerate(self.command_term.metrics):  # (error_vel_xy, error_vel_yaw) or (position_error, orientation_error)
@@ -981,6 +1004,8 @@ class ManagerBasedRLEnv:
                 self._log_index[f"Curriculum/{n}"] = base + 2
             ev_flags |= 2
         self._log_views = {k: self._log_out[i] for k, i in self._log_index.items()}
+        # (a pose-2d command's error_pos_2d does not exist, and is not logged, before the term's first compute)
+        self._log_views_before_compute = {k: v for k, v in self._log_views.items() if not (self._pose2d_command and k.endswith("/error_pos_2d"))}
         if getattr(self, "_ev_part", None) is not None:
             self._bufs.ev_part = self._ev_part.data_ptr()
             self._bufs.ev_flags = ev_flags
@@ -1409,7 +1434,13 @@ class ManagerBasedRLEnv:
             o.terrain_rows, o.terrain_cols = int(ti.terrain_origins.shape[0]), int(ti.terrain_origins.shape[1])
             o.terrain_size_x, o.max_episode_length_s = float(ti.size_x), float(self.max_episode_length_s)
         ct = self.command_term
-        if ct is not None and self._pose_command:
+        self._orch_pose2d = None
+        if ct is not None and self._pose2d_command:  # (has_command stays 0: imx_reset_orchestrate_pose2d takes the term's own struct)
+            if self.event_manager is not None and self.event_manager.needs_manip:
+                raise NotImplementedError(f"command term '{self.command_term_name}': a pose-2d command beside an event on a rigid object or "
+                                          "reset_scene_to_default is not built (those run in imx_reset_orchestrate_manip)")
+            self._orch_pose2d = ct.struct()
+        elif ct is not None and self._pose_command:
             o.has_command = 2
             for k, v in enumerate(ct._cfg16):
                 o.command_cfg[k] = float(v)
@@ -1480,7 +1511,13 @@ class ManagerBasedRLEnv:
                 o.terms[i].uniforms_d, o.terms[i].interval_uniforms_d = _lib.ptr(t.uniforms), _lib.ptr(t.interval_uniforms)
         o.command_uniforms_d = _lib.ptr(self._orch_draws.get("command"))
         o.rand_levels_d = _lib.ptr(self._orch_draws.get("rand_levels"))
-        if self._orch_manip is not None:
+        if self._orch_pose2d is not None:
+            c = self._orch_pose2d
+            c.uniforms_d, c.patch_ids_d = _lib.ptr(self._orch_draws.get("command")), _lib.ptr(self._orch_draws.get("patch_ids"))
+            check(self._lib.imx_reset_orchestrate_pose2d(ctypes.byref(o), ctypes.byref(c), _lib.current_stream(self.device)))
+            if do_step:
+                self.command_term.mark_computed()
+        elif self._orch_manip is not None:
             check(self._lib.imx_reset_orchestrate_manip(ctypes.byref(o), ctypes.byref(self._orch_manip), _lib.current_stream(self.device)))
         else:
             check(self._lib.imx_reset_orchestrate(ctypes.byref(o), _lib.current_stream(self.device)))
@@ -1596,7 +1633,8 @@ class ManagerBasedRLEnv:
                                                          1 if self.defer_step_tail else 0,
                                                          ctypes.byref(rollout_slot) if rollout_slot is not None else None,
                                                          _lib.current_stream(self.device)))
-        self.extras["log"] = self._log_views
+        # (the resets of this step log the metrics as they stand before this step's CommandManager.compute)
+        self.extras["log"] = self._log_views if not self._pose2d_command or "error_pos_2d" in self.command_term.metrics else self._log_views_before_compute
         if self._class_terms:
             # _reset_idx reaches the class terms between the reward and the observation pass (manager_based_rl_env.py:215-218 ->
             # RewardManager.reset / ObservationManager.reset).  This route is Python-evaluated anyway: the ids are read like the

@@ -6,6 +6,8 @@
   (isaaclab/managers/command_manager.py:119-187; isaaclab/envs/mdp/commands/velocity_command.py:37-160)
 * :class:`UniformPoseCommand` -- the same two steps for the uniform pose command of the Reach tasks
   (isaaclab/envs/mdp/commands/pose_command.py:25-127)
+* :class:`UniformPose2dCommand`, :class:`TerrainBasedPose2dCommand` -- the same two steps for the pose-2d commands of the Navigation
+  task (isaaclab/envs/mdp/commands/pose_2d_command.py:26-203)
 
 Attribute names follow the reference so that term functions reading ``sensor.data.*`` / ``command_manager`` keep working.
 """
@@ -184,6 +186,158 @@ class UniformPoseCommand:
             self.time_left.data_ptr(), self.command_counter.data_ptr(), self.metrics["position_error"].data_ptr(),
             self.metrics["orientation_error"].data_ptr(), _lib.current_stream(self.device)))
         return self.pose_command_b
+
+
+class UniformPose2dCommand:
+    """``cfg``: dict / object with the fields of ``UniformPose2dCommandCfg`` (commands_cfg.py): ``resampling_time_range``,
+    ``simple_heading``, ``ranges`` {pos_x, pos_y, heading}.  ``env_origins`` (N, 3) is ``scene.env_origins`` and ``default_root_z`` (a
+    number or (N)) ``robot.data.default_root_state[:, 2]``; left None, an env that is handed the term (``command_term=``) fills in its
+    own.  ``robot``: anything with ``data.root_pos_w`` / ``data.root_quat_w`` (or the two attributes themselves, as
+    ``ArticulationRootState`` has them), read by ``reset`` / ``compute`` in stand-alone use.
+
+    The ``CommandTerm`` surface of the reference class (pose_2d_command.py:26-143): ``command`` (N, 4) = ``pos_command_b`` +
+    ``heading_command_b`` (views of it), ``pos_command_w``, ``heading_command_w``, ``time_left``, ``command_counter`` and ``metrics``.
+    The metrics follow the reference to the letter: the constructor creates ``error_pos`` and ``error_heading``, ``_update_metrics``
+    writes ``error_pos_2d`` -- that key exists only after the first compute -- and ``error_pos`` stays zero for ever."""
+
+    kind = 0
+
+    def __init__(self, cfg, num_envs: int, step_dt: float, device="cuda:0", seed: int = 0, robot=None, env_origins=None,
+                 default_root_z=None):
+        get = (lambda k, d=None: cfg.get(k, d)) if isinstance(cfg, dict) else (lambda k, d=None: getattr(cfg, k, d))
+        rng = get("ranges")
+        rget = (lambda k, d=None: rng.get(k, d)) if isinstance(rng, dict) else (lambda k, d=None: getattr(rng, k, d))
+        self.simple_heading = bool(get("simple_heading", False))
+        rt = get("resampling_time_range")
+        if not float(rt[1]) > 0.0:
+            raise ValueError(f"{type(self).__name__}: resampling_time_range[1] must be positive (it is {rt[1]})")
+        pos_x, pos_y, heading = rget("pos_x") or (0.0, 0.0), rget("pos_y") or (0.0, 0.0), rget("heading")
+        if heading is None:
+            if not self.simple_heading:
+                raise ValueError(f"{type(self).__name__}: simple_heading is off but `ranges.heading` is None")
+            heading = (0.0, 0.0)
+        if self.kind == 0 and (rget("pos_x") is None or rget("pos_y") is None):
+            raise ValueError("UniformPose2dCommand: `ranges.pos_x` and `ranges.pos_y` are needed")
+        self._cfg8 = np.asarray([rt[0], rt[1], *pos_x, *pos_y, *heading], dtype=np.float32)
+        N = num_envs
+        dev = torch.device(device)
+        self.num_envs, self.device, self.seed, self.step_dt, self.robot = N, dev, int(seed), float(step_dt), robot
+        self.env_origins_given, self.default_root_z_given = env_origins is not None, default_root_z is not None
+        self.env_origins = torch.zeros(N, 3, device=dev)
+        if env_origins is not None:
+            if tuple(env_origins.shape) != (N, 3):
+                raise ValueError(f"{type(self).__name__}: env_origins is {tuple(env_origins.shape)}, expected ({N}, 3)")
+            self.env_origins.copy_(env_origins)
+        self.default_root_z = torch.zeros(N, device=dev)
+        if default_root_z is not None:
+            self.default_root_z.copy_(torch.as_tensor(default_root_z, dtype=torch.float32).expand(N))
+        self._command = torch.zeros(N, 4, device=dev)
+        self.pos_command_b, self.heading_command_b = self._command[:, :3], self._command[:, 3]
+        self.pos_command_w = torch.zeros(N, 3, device=dev)
+        self.heading_command_w = torch.zeros(N, device=dev)
+        self.time_left = torch.zeros(N, device=dev)
+        self.command_counter = torch.zeros(N, dtype=torch.long, device=dev)
+        self.metrics = {"error_pos": torch.zeros(N, device=dev), "error_heading": torch.zeros(N, device=dev)}
+        self._error_pos_2d = torch.zeros(N, device=dev)  # metrics["error_pos_2d"] from the first compute on
+        self._step = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._struct = None
+
+    @property
+    def command(self) -> torch.Tensor:
+        return self._command
+
+    def struct(self, uniforms=None, patch_ids=None) -> "_lib.ImxPose2dCommand":
+        """The term as ``imx_pose2d_command`` / ``imx_reset_orchestrate_pose2d`` take it (it points at the term's own tensors)."""
+        p = _lib.ptr
+        c = _lib.ImxPose2dCommand(kind=self.kind, simple_heading=int(self.simple_heading), env_origins_d=p(self.env_origins),
+                                  default_root_z_d=p(self.default_root_z), uniforms_d=p(uniforms), patch_ids_d=p(patch_ids),
+                                  command_d=p(self._command), pos_command_w_d=p(self.pos_command_w),
+                                  heading_command_w_d=p(self.heading_command_w), time_left_d=p(self.time_left),
+                                  command_counter_d=p(self.command_counter), metric_error_pos_2d_d=p(self._error_pos_2d),
+                                  metric_error_heading_d=p(self.metrics["error_heading"]))
+        for k, v in enumerate(self._cfg8):
+            c.cfg[k] = float(v)
+        return c
+
+    def mark_computed(self):
+        """After a launch that ran ``compute``: ``_update_metrics`` has written ``error_pos_2d`` (pose_2d_command.py:84)."""
+        self.metrics.setdefault("error_pos_2d", self._error_pos_2d)
+
+    def _root(self, root_pos_w, root_quat_w):
+        if root_pos_w is None or root_quat_w is None:
+            if self.robot is None:
+                raise ValueError(f"{type(self).__name__}: pass root_pos_w / root_quat_w or build the term with robot=")
+            data = getattr(self.robot, "data", self.robot)
+            root_pos_w, root_quat_w = data.root_pos_w, data.root_quat_w
+        N = self.num_envs
+        for name, t, shape in (("root_pos_w", root_pos_w, (N, 3)), ("root_quat_w", root_quat_w, (N, 4))):
+            if tuple(t.shape) != shape or t.dtype != torch.float32:
+                raise ValueError(f"{type(self).__name__}: {name} is {tuple(t.shape)} {t.dtype}, expected {shape} float32")
+        return root_pos_w, root_quat_w
+
+    def _launch(self, dt, do_compute, reset_mask, uniforms, patch_ids, root_pos_w, root_quat_w):
+        N = self.num_envs
+        root_pos_w, root_quat_w = self._root(root_pos_w, root_quat_w)
+        if reset_mask is not None and (reset_mask.numel() != N or reset_mask.element_size() != 1):
+            raise ValueError(f"{type(self).__name__}: reset_mask must hold {N} one-byte entries")
+        if uniforms is not None and (tuple(uniforms.shape) != (2, N, 4) or uniforms.dtype != torch.float32):
+            raise ValueError(f"{type(self).__name__}: uniforms is {tuple(uniforms.shape)} {uniforms.dtype}, expected (2, {N}, 4) float32")
+        if patch_ids is not None and (tuple(patch_ids.shape) != (2, N) or patch_ids.dtype != torch.int64):
+            raise ValueError(f"{type(self).__name__}: patch_ids is {tuple(patch_ids.shape)} {patch_ids.dtype}, expected (2, {N}) int64")
+        self._step += 1
+        if self._struct is None:  # (the term's own tensors never move: built once, the draw tables re-pointed per call)
+            self._struct = self.struct()
+        c = self._struct
+        c.uniforms_d, c.patch_ids_d = _lib.ptr(uniforms), _lib.ptr(patch_ids)
+        check(lib().imx_pose2d_command(N, ctypes.byref(c), float(dt), int(do_compute), _lib.ptr(root_pos_w), _lib.ptr(root_quat_w),
+                                       _lib.ptr(reset_mask), self.seed, self._step.data_ptr(), _lib.current_stream(self.device)))
+        if do_compute:
+            self.mark_computed()
+
+    def reset(self, env_ids=None, uniforms=None, patch_ids=None, root_pos_w=None, root_quat_w=None) -> dict:
+        """``CommandTerm.reset(env_ids)`` (command_manager.py:120-149): returns the metrics' means over ``env_ids`` as they stood."""
+        ids = slice(None) if env_ids is None else env_ids
+        log = {k: float(torch.mean(v[ids])) for k, v in self.metrics.items()}
+        mask = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)
+        mask[ids] = True
+        self._launch(0.0, False, mask, uniforms, patch_ids, root_pos_w, root_quat_w)
+        return log
+
+    def compute(self, dt: float, reset_mask=None, uniforms=None, patch_ids=None, root_pos_w=None, root_quat_w=None, do_compute: bool = True):
+        """``reset(ids of reset_mask)`` then (``do_compute``) ``CommandTerm.compute(dt)`` in ONE launch; ``uniforms``: optional (2, N, 4)
+        parity samples, ``patch_ids``: optional (2, N) int64 patch draws of the terrain-based class."""
+        self._launch(dt, do_compute, reset_mask, uniforms, patch_ids, root_pos_w, root_quat_w)
+        return self._command
+
+
+class TerrainBasedPose2dCommand(UniformPose2dCommand):
+    """``TerrainBasedPose2dCommand`` (pose_2d_command.py:146-203): the position is one of the P valid patches ``valid_targets`` (L, T, P, 3)
+    (``terrain.flat_patches["target"]``) of the env's terrain cell (``terrain_levels``, ``terrain_types``: (N) int64), at the default
+    root height above it."""
+
+    kind = 1
+
+    def __init__(self, cfg, num_envs: int, step_dt: float, device="cuda:0", seed: int = 0, robot=None, env_origins=None,
+                 default_root_z=None, valid_targets=None, terrain_levels=None, terrain_types=None):
+        super().__init__(cfg, num_envs, step_dt, device, seed, robot, env_origins, default_root_z)
+        if valid_targets is None or terrain_levels is None or terrain_types is None:
+            raise ValueError("TerrainBasedPose2dCommand needs valid_targets=, terrain_levels= and terrain_types=")
+        if valid_targets.dim() != 4 or valid_targets.shape[-1] != 3 or 0 in valid_targets.shape:
+            raise ValueError(f"TerrainBasedPose2dCommand: valid_targets is {tuple(valid_targets.shape)}, expected (L, T, P, 3)")
+        L, T = valid_targets.shape[:2]
+        for name, t, n in (("terrain_levels", terrain_levels, L), ("terrain_types", terrain_types, T)):
+            if tuple(t.shape) != (num_envs,) or t.dtype != torch.int64:
+                raise ValueError(f"TerrainBasedPose2dCommand: {name} is {tuple(t.shape)} {t.dtype}, expected ({num_envs},) int64")
+            if int(t.min()) < 0 or int(t.max()) >= n:
+                raise ValueError(f"TerrainBasedPose2dCommand: {name} has entries outside [0, {n})")
+        self.valid_targets = valid_targets.to(self.device, torch.float32).contiguous()
+        self.terrain_levels, self.terrain_types = terrain_levels.to(self.device).contiguous(), terrain_types.to(self.device).contiguous()
+
+    def struct(self, uniforms=None, patch_ids=None):
+        c = super().struct(uniforms, patch_ids)
+        c.valid_targets_d, c.terrain_levels_d, c.terrain_types_d = _lib.ptr(self.valid_targets), _lib.ptr(self.terrain_levels), _lib.ptr(self.terrain_types)
+        c.num_levels, c.num_types, c.num_patches = (int(x) for x in self.valid_targets.shape[:3])
+        return c
 
 
 class ArticulationRootState:

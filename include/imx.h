@@ -110,8 +110,13 @@ enum imx_term_op {
     IMX_T_TERRAIN_OUT_OF_BOUNDS,   /* isaaclab_tasks .../velocity/mdp/terminations.py:24-52  p0=x_lim p1=y_lim */
     IMX_T_EXTERNAL,                /* value computed by a Python term; aux0 = column in ext_term */
     IMX_T_COMMAND_RESAMPLE,        /* :35-42    p0 = f32(step_dt), nids = num_resamples; state.command_time_left / command_counter */
-    IMX_T_OBJECT_REACHED_GOAL      /* isaaclab_tasks .../manipulation/lift/mdp/terminations.py:25-53  ||des_pos_w - object_root_pos_w|| < p0
+    IMX_T_OBJECT_REACHED_GOAL,     /* isaaclab_tasks .../manipulation/lift/mdp/terminations.py:25-53  ||des_pos_w - object_root_pos_w|| < p0
                                       (threshold); des_pos_w as for the reach rewards, CMD == 7 */
+    /* isaaclab_tasks .../manipulation/inhand/mdp/terminations.py (Isaac-Repose-Cube-Allegro-v0); command = (N, 7): the goal position in
+       the ENV frame + the goal quaternion in the world frame (InHandReOrientationCommand.command, orientation_command.py:75-78) */
+    IMX_T_MAX_CONSECUTIVE_SUCCESS, /* :18-28   imx_object_state_t.command_consecutive_success >= p0 (num_success as f32: the metric is a float tensor) */
+    IMX_T_OBJECT_AWAY_FROM_GOAL,   /* :31-56   ||(object_root_pos_w - env_origins) - cmd[:3]|| > p0 (threshold): env frame */
+    IMX_T_OBJECT_AWAY_FROM_ROBOT   /* :59-83   ||root_pos_w - object_root_pos_w|| > p0 (threshold) */
 };
 
 /* reward ops -- envs/mdp/rewards.py unless noted */
@@ -187,7 +192,15 @@ enum imx_rew_op {
        frame (CMD == 4): pos_command_b 3, heading_command_b 1.  A plan with these ops runs k_term_rew_nav and holds no classic, reach or
        lift op */
     IMX_W_NAV_POSITION_COMMAND_ERROR_TANH, /* :17-22  1 - tanh(||cmd[:3]|| / p0), p0 = std */
-    IMX_W_NAV_HEADING_COMMAND_ERROR_ABS    /* :25-29  |cmd[3]| */
+    IMX_W_NAV_HEADING_COMMAND_ERROR_ABS,   /* :25-29  |cmd[3]| */
+    /* isaaclab_tasks .../manipulation/inhand/mdp/rewards.py (Isaac-Repose-Cube-Allegro-v0); command as for the in-hand terminations
+       (CMD == 7); dtheta = quat_error_magnitude(object_root_quat_w, cmd[3:7]) (utils/math.py:678-690), computed once per env.  A plan with
+       these ops or the three in-hand termination ops runs k_term_rew_inhand and holds no classic, reach, lift or navigation reward op and
+       no object_reached_goal termination; root_height_below_minimum on the object (aux0 = 1) is served there as well */
+    IMX_W_TRACK_ORIENTATION_INV_L2,   /* :71-96  1 / (dtheta + p0), p0 = rot_eps */
+    IMX_W_SUCCESS_BONUS,              /* :20-44  dtheta <= p0 -> 1 / 0, p0 = the command cfg's orientation_success_threshold (`<=`: the
+                                                  command term's own success test is `<`) */
+    IMX_W_TRACK_POS_L2                /* :47-68  ||cmd[:3] - (object_root_pos_w - env_origins)|| */
 };
 
 /* observation ops -- envs/mdp/observations.py */
@@ -196,7 +209,9 @@ enum imx_obs_op {
     IMX_O_BASE_LIN_VEL,     /* :40-44 */
     IMX_O_BASE_ANG_VEL,     /* :47-51 */
     IMX_O_PROJECTED_GRAVITY,/* :54-58 */
-    IMX_O_ROOT_POS_W,       /* :61-65 (minus env origins) */
+    /* the four root observations: aux0 = the asset -- 0 the robot (the word every older blob has), 1 the scene's rigid object
+       (state.object_root_pos_w and imx_object_state_t; as IMX_T_ROOT_HEIGHT_BELOW_MIN's selector) */
+    IMX_O_ROOT_POS_W,       /* :61-65 (minus env origins, on either asset) */
     IMX_O_ROOT_QUAT_W,      /* :68-83 */
     IMX_O_ROOT_LIN_VEL_W,   /* :85-89 */
     IMX_O_ROOT_ANG_VEL_W,   /* :92-96 */
@@ -216,9 +231,11 @@ enum imx_obs_op {
     IMX_O_BASE_ANGLE_TO_TARGET, /* :61-77 p0..p2 = target_pos */
     IMX_O_BODY_INCOMING_WRENCH, /* envs/mdp/observations.py:176-185 ids = asset bodies; 6 columns per body in id order;
                                    state.link_incoming_joint_force */
-    IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME /* isaaclab_tasks .../manipulation/lift/mdp/observations.py:19-31  3 columns:
+    IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME, /* isaaclab_tasks .../manipulation/lift/mdp/observations.py:19-31  3 columns:
                                    quat_apply(quat_inv(root_quat_w), object_root_pos_w - root_pos_w) (subtract_frame_transforms,
                                    utils/math.py:785-816; quat_inv = normalize(conjugate), :239-248) */
+    IMX_O_GOAL_QUAT_DIFF    /* isaaclab_tasks .../manipulation/inhand/mdp/observations.py:20-38  4 columns:
+                                   quat_mul(object_root_quat_w, quat_conjugate(cmd[3:7])), CMD == 7; IMX_F_QUAT_UNIQUE when make_quat_unique */
 };
 
 /* action ops.  A record takes the raw columns [OUT, OUT + DIM) of the action and writes the processed columns [PCOL, PCOL + NIDS) of
@@ -482,11 +499,35 @@ int imx_pose2d_command(int64_t N, const imx_pose2d_command_t* cmd, float dt, int
                        imx_stream_t stream);
 int imx_reset_orchestrate_pose2d(const imx_orch_t* orch, const imx_pose2d_command_t* cmd, imx_stream_t stream);
 
+/* ---- the in-hand re-orientation command term (Isaac-Repose-Cube-Allegro-v0): imx_inhand_command ---------------------------------
+ * InHandReOrientationCommand (isaaclab_tasks .../manipulation/inhand/mdp/commands/orientation_command.py:22-124) under
+ * CommandTerm.reset / compute (isaaclab/managers/command_manager.py:120-187), one lane per env.  The term travels in
+ * imx_inhand_command_t (imx_inhand_command_struct.h, which this header includes): its cfg, the fixed goal position, the object's root
+ * pose, the reset mask, the optional parity draws, the seed and its state / output buffers.
+ *   One launch: CommandTerm.reset on the envs of term->reset_mask_d (NULL = none) -- the metrics of those envs are summed for the log
+ *   first (term->log_part_d), then zeroed, command_counter = 0, resample -- and then, with flags bit 0, CommandTerm.compute(dt):
+ *   _update_metrics, time_left -= dt with a resample where it ran out, _update_command (a resample where the goal was reached).
+ * STAND-ALONE: no orchestration launch runs this term yet and imx_orch_t does not grow for it.
+ * Every NULL pointer or out-of-range value is refused and named in imx_last_error before any launch. */
+typedef struct imx_inhand_command imx_inhand_command_t;
+#include "imx_inhand_command_struct.h" /* the definition of imx_inhand_command_t */
+int imx_inhand_command(const imx_inhand_command_t* term, int64_t N, float dt, int flags, imx_stream_t stream);
+
+/* ---- the in-hand task's further per-step tensors: imx_object_state_t, imx_plan_bind_object_state -------------------------------
+ * The rest of the rigid object's root state (object_root_quat_w, object_root_lin_vel_w, object_root_ang_vel_w) and the command term's
+ * consecutive_success metric (imx_object_state.h, which this header includes).  imx_state_t does not grow for them: the caller binds
+ * the struct to the plan, and imx_terminations_rewards[_rollout] / imx_observations on that plan read the pointers bound at the time
+ * of the call (host side: a captured graph keeps what was bound when its launch was recorded).  os = NULL unbinds.  The struct is
+ * copied: it need not outlive the call. */
+typedef struct imx_object_state imx_object_state_t;
+#include "imx_object_state.h" /* the definition of imx_object_state_t */
+int imx_plan_bind_object_state(imx_plan_t* plan, const imx_object_state_t* os);
+
 /* ---- library ---------------------------------------------------------------------------------------------------- */
 const char* imx_version(void);
 /* sizeof of an ABI struct as this library was compiled (which: 0 imx_state_t, 1 imx_buffers_t, 2 imx_head_loss_t, 3 imx_rollout_slot_t, 4 imx_policy_act_t, 5 imx_orch_t, 6 imx_event_term_t,
  * 7 imx_diff_ik_t, 8 imx_osc_t, 10 imx_orch_manip_t, 11 imx_weight_term_t, 12 imx_pretrained_policy_t,
- * 13 imx_pose2d_command_t), 0 for an unknown index (9 is one):
+ * 13 imx_pose2d_command_t, 15 imx_inhand_command_t, 16 imx_object_state_t), 0 for an unknown index (9 and 14 are):
  * a binding checks its own layout against it at load time. */
 size_t imx_struct_size(int which);
 const char* imx_last_error(void);

@@ -169,5 +169,13 @@ try:
     POSE2D_HEADER = os.path.join(os.path.dirname(HEADER), "imx_pose2d_struct.h")
     with open(POSE2D_HEADER) as _f:
         _, _, POSE2D_STRUCTS, _ = parse(_f.read(), POSE2D_HEADER, DEFINES)
+    # imx_inhand_command_struct.h, likewise: imx_inhand_command_t (imx_inhand_command)
+    INHAND_HEADER = os.path.join(os.path.dirname(HEADER), "imx_inhand_command_struct.h")
+    with open(INHAND_HEADER) as _f:
+        _, _, INHAND_STRUCTS, _ = parse(_f.read(), INHAND_HEADER, DEFINES)
+    # imx_object_state.h, likewise: imx_object_state_t (imx_plan_bind_object_state)
+    OBJECT_STATE_HEADER = os.path.join(os.path.dirname(HEADER), "imx_object_state.h")
+    with open(OBJECT_STATE_HEADER) as _f:
+        _, _, OBJECT_STATE_STRUCTS, _ = parse(_f.read(), OBJECT_STATE_HEADER, DEFINES)
 except OSError as e:
     raise AbiError(f"the ABI header {HEADER} cannot be read ({e}): the whole binding is derived from it") from e

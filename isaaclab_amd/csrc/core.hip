@@ -37,6 +37,8 @@ extern "C" size_t imx_struct_size(int which) {
         case 11: return sizeof(imx_weight_term_t);
         case 12: return sizeof(imx_pretrained_policy_t);
         case 13: return sizeof(imx_pose2d_command_t);
+        case 15: return sizeof(imx_inhand_command_t);
+        case 16: return sizeof(imx_object_state_t);
         default: return 0;
     }
 }
@@ -107,7 +109,7 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
     for (int k = 0; k < p->nterm; ++k) {
         const int32_t* r = &w[p->term_off + k * IMX_REC_WORDS];
         const int op = r[IMX_R_OP];
-        IMX_REQUIRE(op >= IMX_T_TIME_OUT && op <= IMX_T_OBJECT_REACHED_GOAL, "plan: unknown termination op %d", op);
+        IMX_REQUIRE(op >= IMX_T_TIME_OUT && op <= IMX_T_OBJECT_AWAY_FROM_ROBOT, "plan: unknown termination op %d", op);
         IMX_REQUIRE(r[IMX_R_OUT] == k, "plan: termination record %d has index %d", k, r[IMX_R_OUT]);
         const bool body = op == IMX_T_ILLEGAL_CONTACT;
         if (op != IMX_T_COMMAND_RESAMPLE &&  // its NIDS word is num_resamples, not a list length
@@ -118,12 +120,14 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
             IMX_REQUIRE(r[IMX_R_AUX0] == 0 || r[IMX_R_AUX0] == 1, "plan: termination record %d: asset selector %d (0 robot, 1 object)", k, r[IMX_R_AUX0]);
         if (op == IMX_T_OBJECT_REACHED_GOAL)
             IMX_REQUIRE(p->CMD == 7, "plan: termination record %d (object_reached_goal) needs a 7-wide pose command (CMD=%d)", k, p->CMD);
+        if (op == IMX_T_OBJECT_AWAY_FROM_GOAL)
+            IMX_REQUIRE(p->CMD == 7, "plan: termination record %d (object_away_from_goal) needs a 7-wide pose command (CMD=%d)", k, p->CMD);
     }
     // ---- rewards
     for (int k = 0; k < p->nrew; ++k) {
         const int32_t* r = &w[p->rew_off + k * IMX_REC_WORDS];
         const int op = r[IMX_R_OP];
-        IMX_REQUIRE(op >= IMX_W_IS_ALIVE && op <= IMX_W_NAV_HEADING_COMMAND_ERROR_ABS, "plan: unknown reward op %d", op);
+        IMX_REQUIRE(op >= IMX_W_IS_ALIVE && op <= IMX_W_TRACK_POS_L2, "plan: unknown reward op %d", op);
         IMX_REQUIRE(r[IMX_R_OUT] == k, "plan: reward record %d has index %d", k, r[IMX_R_OUT]);
         int limit = p->J;
         const char* what = "joint";
@@ -152,6 +156,8 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
             IMX_REQUIRE(p->CMD == 7, "plan: reward record %d (object_goal_distance) needs a 7-wide pose command (CMD=%d)", k, p->CMD);
         if (op == IMX_W_NAV_POSITION_COMMAND_ERROR_TANH || op == IMX_W_NAV_HEADING_COMMAND_ERROR_ABS)
             IMX_REQUIRE(p->CMD == 4, "plan: reward record %d (op %d) needs a 4-wide pose-2d command (CMD=%d)", k, op, p->CMD);
+        if (op >= IMX_W_TRACK_ORIENTATION_INV_L2 && op <= IMX_W_TRACK_POS_L2)
+            IMX_REQUIRE(p->CMD == 7, "plan: reward record %d (op %d) needs the 7-wide in-hand pose command (CMD=%d)", k, op, p->CMD);
         if (op == IMX_W_PROGRESS_REWARD)
             IMX_REQUIRE(r[IMX_R_AUX0] >= 0 && r[IMX_R_AUX0] < p->term_slots, "plan: reward record %d: state slot %d outside [0, %d)", k,
                         r[IMX_R_AUX0], p->term_slots);
@@ -185,7 +191,7 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
     for (int k = 0; k < p->nobs; ++k) {
         const int32_t* r = &w[p->obs_off + k * IMX_REC_WORDS];
         const int op = r[IMX_R_OP];
-        IMX_REQUIRE(op >= IMX_O_BASE_POS_Z && op <= IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME, "plan: unknown observation op %d", op);
+        IMX_REQUIRE(op >= IMX_O_BASE_POS_Z && op <= IMX_O_GOAL_QUAT_DIFF, "plan: unknown observation op %d", op);
         const int g = r[IMX_R_WEIGHT];
         IMX_REQUIRE(g >= 0 && g < p->ngroups, "plan: observation record %d names group %d", k, g);
         {
@@ -227,6 +233,9 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
         if (op == IMX_O_BASE_UP_PROJ || op == IMX_O_BASE_HEADING_PROJ || op == IMX_O_BASE_ANGLE_TO_TARGET)
             IMX_REQUIRE(d == 1, "plan: observation op %d must have dim 1", op);
         if (op == IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME) IMX_REQUIRE(d == 3, "plan: object_position_in_robot_root_frame must have dim 3");
+        if (op == IMX_O_GOAL_QUAT_DIFF) IMX_REQUIRE(d == 4 && p->CMD == 7, "plan: goal_quat_diff must have dim 4 and a 7-wide pose command (CMD=%d)", p->CMD);
+        if (op >= IMX_O_ROOT_POS_W && op <= IMX_O_ROOT_ANG_VEL_W)
+            IMX_REQUIRE(r[IMX_R_AUX0] == 0 || r[IMX_R_AUX0] == 1, "plan: observation record %d: asset selector %d (0 robot, 1 object)", k, r[IMX_R_AUX0]);
         if (op == IMX_O_LAST_ACTION) IMX_REQUIRE(d == p->A, "plan: last_action dim %d != A=%d", d, p->A);
         if (op == IMX_O_GENERATED_COMMANDS) IMX_REQUIRE(d == p->CMD, "plan: command dim mismatch");
         if (op == IMX_O_EXTERNAL)
@@ -344,6 +353,7 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
                            op == IMX_O_JOINT_VEL_REL || op == IMX_O_JOINT_POS_LIMIT_NORMALIZED;
         if (joint) x[10] = w[(size_t)w[ro + IMX_R_IDS_OFF] + j];
         if (op == IMX_O_EXTERNAL) x[10] = w[ro + IMX_R_AUX0];
+        if (op >= IMX_O_ROOT_POS_W && op <= IMX_O_ROOT_ANG_VEL_W) x[10] = w[ro + IMX_R_AUX0];  // the asset: 0 robot, 1 object
         if (op == IMX_O_BODY_INCOMING_WRENCH) x[10] = w[(size_t)w[ro + IMX_R_IDS_OFF] + j / 6] * 6 + j % 6;  // body * 6 + component
         if (op == IMX_O_BASE_HEADING_PROJ || op == IMX_O_BASE_ANGLE_TO_TARGET) {  // target_pos: x in XC_P0, y, z in XC_RX, XC_RY
             x[11] = w[ro + IMX_R_P1]; x[12] = w[ro + IMX_R_P2];
@@ -422,6 +432,12 @@ extern "C" int imx_plan_update(imx_plan_t* plan, const int32_t* blob, size_t nwo
     plan->dev = dev;
     q.dev = nullptr;
     if (dev && upload_plan(plan, (hipStream_t)stream, true)) return 1;
+    return 0;
+}
+
+extern "C" int imx_plan_bind_object_state(imx_plan_t* plan, const imx_object_state_t* os) {
+    IMX_REQUIRE(plan, "imx_plan_bind_object_state: null plan");
+    plan->object_state = os ? *os : imx_object_state_t{};
     return 0;
 }
 

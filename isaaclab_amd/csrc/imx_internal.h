@@ -37,6 +37,7 @@ struct imx_plan {
     int32_t* dev = nullptr;     // device copy (null when no GPU is visible)
     int J = 0, B = 0, H = 0, A = 0, D = 0, R = 0, NB = 0, CMD = 3;
     int nterm = 0, nrew = 0, nobs = 0, nact = 0, nrew_all = 0;
+    imx_object_state_t object_state{};  // what imx_plan_bind_object_state bound (host side; all NULL = nothing bound)
     int term_off = 0, rew_off = 0, obs_off = 0, act_off = 0, ray_off = 0;
     int col_off = 0;    // D words: (obs record index << 16) | local index j
     int order_off = 0;  // D words: column permutation, ray columns first

@@ -101,6 +101,14 @@ IMX_DEV float object_pos_in_root_frame(const float* __restrict__ es, const float
     return j == 0 ? ox : (j == 1 ? oy : oz);
 }
 
+// goal_quat_diff (manipulation/inhand/mdp/observations.py:20-38), component j: quat_mul(object_quat_w, quat_conjugate(goal_quat_w)), then
+// quat_unique (utils/math.py:251-263: -q where w < 0) when make_quat_unique
+IMX_DEV float goal_quat_diff(const float* __restrict__ obj_quat, const float* __restrict__ cmd, bool unique, int j) {
+    const float4 q = quat_mul_ref(make_float4(obj_quat[0], obj_quat[1], obj_quat[2], obj_quat[3]), make_float4(cmd[3], -cmd[4], -cmd[5], -cmd[6]));
+    const float v = j == 0 ? q.x : (j == 1 ? q.y : (j == 2 ? q.z : q.w));
+    return (unique && q.x < 0.0f) ? -v : v;
+}
+
 // value of one non-ray observation column (every op but HEIGHT_SCAN); es = the env's frame (k_frame).  OBJECT: with the op that reads the
 // scene's rigid object -- k_obs only; k_obs_lean, tuned to its SGPR budget, is not chosen for a plan that has it (choose_obs_kernel)
 template <bool OBJECT>
@@ -142,4 +150,21 @@ IMX_DEV float obs_plain_value(const PlanView& P, const imx_state_t& S, const imx
         case IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME: return OBJECT ? object_pos_in_root_frame(es, S.object_root_pos_w + e * 3, j) : 0.0f;
         default: return 0.0f;
     }
+}
+
+// k_obs_inhand's column value: the root observations on the scene's rigid object (XC_AUX = 1; X = the bound imx_object_state_t) and
+// goal_quat_diff; every other column is obs_plain_value's.  In a function of its own, so that every other kernel keeps the instruction
+// stream it had
+IMX_DEV float obs_inhand_value(const PlanView& P, const imx_state_t& S, const imx_object_state_t& X, const imx_buffers_t& Bf,
+                               const float* __restrict__ es, int64_t e, const XCol& x) {
+    const int op = x.a.y, j = x.a.z, flags = x.a.w, aux = x.c.z;
+    if (op == IMX_O_GOAL_QUAT_DIFF) return goal_quat_diff(X.object_root_quat_w + e * 4, S.command + e * P.CMD, (flags & IMX_F_QUAT_UNIQUE) != 0, j);
+    if (aux && op >= IMX_O_ROOT_POS_W && op <= IMX_O_ROOT_ANG_VEL_W) {
+        if (op == IMX_O_ROOT_POS_W) return S.object_root_pos_w[e * 3 + j] - S.env_origins[e * 3 + j];
+        if (op == IMX_O_ROOT_LIN_VEL_W) return X.object_root_lin_vel_w[e * 3 + j];
+        if (op == IMX_O_ROOT_ANG_VEL_W) return X.object_root_ang_vel_w[e * 3 + j];
+        const float* __restrict__ q = X.object_root_quat_w + e * 4;
+        return ((flags & IMX_F_QUAT_UNIQUE) && q[0] < 0.0f) ? -q[j] : q[j];
+    }
+    return obs_plain_value<true>(P, S, Bf, es, e, x);
 }

@@ -174,6 +174,8 @@ static int pp_check(const imx_plan_t* plan, int64_t N, const imx_state_t* st, co
         IMX_REQUIRE(!(w[plan->obs_off + k * IMX_REC_WORDS + IMX_R_FLAGS] & IMX_F_MODIFIERS), "imx_pretrained_policy: observation record %d has modifiers", k);
         const void* p = (const void*)1;
         const char* name = "";
+        if (op >= IMX_O_ROOT_POS_W && op <= IMX_O_ROOT_ANG_VEL_W && w[plan->obs_off + k * IMX_REC_WORDS + IMX_R_AUX0])
+            IMX_FAIL("imx_pretrained_policy: observation record %d (op %d on the rigid object) is not built into the fused low-level step", k, op);
         switch (op) {
             case IMX_O_ROOT_POS_W: p = st->env_origins; name = "env_origins"; break;
             case IMX_O_JOINT_POS: p = st->joint_pos; name = "joint_pos"; break;
@@ -184,7 +186,7 @@ static int pp_check(const imx_plan_t* plan, int64_t N, const imx_state_t* st, co
             case IMX_O_LAST_ACTION: p = bf->action; name = "action"; break;
             case IMX_O_GENERATED_COMMANDS: p = st->command; name = "command"; break;
             case IMX_O_BODY_INCOMING_WRENCH: p = st->link_incoming_joint_force; name = "link_incoming_joint_force"; break;
-            case IMX_O_HEIGHT_SCAN: case IMX_O_EXTERNAL: case IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME:
+            case IMX_O_HEIGHT_SCAN: case IMX_O_EXTERNAL: case IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME: case IMX_O_GOAL_QUAT_DIFF:
                 IMX_FAIL("imx_pretrained_policy: observation record %d (op %d) is not built into the fused low-level step", k, op);
             default: break;
         }

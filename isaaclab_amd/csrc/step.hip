@@ -259,6 +259,21 @@ IMX_DEV float nav_reward(const PlanView& P, const imx_state_t& S, const int32_t*
     return 1.0f - tanhf(d / f_of(r[IMX_R_P0]));
 }
 
+// ---- manipulation/inhand/mdp/rewards.py (Isaac-Repose-Cube-Allegro-v0): the (N, 7) command = goal position in the env frame + goal
+// quaternion in the world frame; in phase 2 of k_term_rew_inhand.  dtheta = the env's orientation error, computed once in phase 1.
+// track_orientation_inv_l2 :71-96, success_bonus :20-44 (`<=`), track_pos_l2 :47-68: torch.norm(goal_pos_e - object_pos_e) with
+// object_pos_e = object_root_pos_w - env_origins
+IMX_DEV float inhand_reward(const PlanView& P, const imx_state_t& S, const int32_t* __restrict__ r, int op, int64_t ec, float dtheta) {
+    const float p0 = f_of(r[IMX_R_P0]);
+    if (op == IMX_W_TRACK_ORIENTATION_INV_L2) return 1.0f / (dtheta + p0);
+    if (op == IMX_W_SUCCESS_BONUS) return dtheta <= p0 ? 1.0f : 0.0f;
+    const float* __restrict__ cmd = S.command + ec * P.CMD;
+    const float dx = cmd[0] - (S.object_root_pos_w[ec * 3] - S.env_origins[ec * 3]);
+    const float dy = cmd[1] - (S.object_root_pos_w[ec * 3 + 1] - S.env_origins[ec * 3 + 1]);
+    const float dz = cmd[2] - (S.object_root_pos_w[ec * 3 + 2] - S.env_origins[ec * 3 + 2]);
+    return sqrtf((dx * dx + dy * dy) + dz * dz);
+}
+
 // scratch layout for k_term_rew (4-byte words, nw = number of env groups; sized for the smallest group: ceil(N/16) groups)
 //   [0, nw*KA)               float  per-group partial sums of episode_sums over reset envs
 //   [.., + nw*NT)            int    per-group counts of term_dones over reset envs
@@ -536,6 +551,17 @@ k_term_rew_nav(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, StepScrat
 #undef IMX_TR_NAV
 }
 
+// INHAND: the in-hand task's three reward and three termination ops (manipulation/inhand/mdp), in a kernel of their own for the same
+// reason.  need_dtheta: a reward of the plan reads the orientation error (the host looks at the ops): it is then computed once per env.
+__global__ void __launch_bounds__(64 * IMX_TR_MAX_WAVES)
+k_term_rew_inhand(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, StepScratch sc, float* __restrict__ frame, int G, int defer_tail,
+                  imx_rollout_slot_t ro, int need_dtheta, imx_object_state_t X) {
+    constexpr bool CLASSIC = false, REACH = false;
+#define IMX_TR_INHAND
+#include "term_rew_body.inc"
+#undef IMX_TR_INHAND
+}
+
 // ------------------------------------------------------------------------------------------------- observations
 // One WAVE = one environment (4 envs per 256-thread block).  Every lane first derives the env's root-frame vectors
 // and scanner yaw from the same 13 root-state floats (wave-uniform loads: one transaction, no LDS, no barrier);
@@ -805,83 +831,21 @@ __global__ void __launch_bounds__(256)
 k_obs(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, MeshView M, const float* __restrict__ frame,
       const float* __restrict__ noise_u, uint64_t seed, int corrupt, float* __restrict__ ray_hits_out, StepScratch sc, int tail_G,
       int tail_parts) {
-    // One workgroup per env.  (A resident grid walking the envs -- sized to what the chip holds at once -- was measured and dropped:
-    // the loop costs 13 more VGPRs, i.e. one wave per SIMD less, and three uneven rounds: 35 us against 29.)
-    if ((int)blockIdx.x < tail_parts) {  // extra workgroups, first in the grid: the step tail k_term_rew deferred (kernel boundary = its partials are complete)
-        step_tail(P, N, Bf, sc, tail_G, (int)blockIdx.x, tail_parts);
-        return;
-    }
-    const int64_t e = blockIdx.x - (unsigned)tail_parts;
-    const int32_t* __restrict__ W = P.w;
-    const uint32_t step = (uint32_t)Bf.counters[2];
-    const bool fill_all = (corrupt & 2) != 0;
-    const bool keep_all_hits = (corrupt & 8) != 0;
-    corrupt &= 1;
-    extern __shared__ float s_hz[];  // R hit heights of this env
-    const float* __restrict__ es = frame + e * IMX_ES_WORDS;  // wave-uniform address
-    const float yw = es[16], yz = es[17];
-    // the sensor's decision for this step (scanner_step, made where the frame row was produced): cast?  keep the hits?  from where?
-    const int sflags = (int)es[20];
-    const bool cast = (sflags & 1) != 0, cache_z = P.scan_stateful && ((sflags & 2) || keep_all_hits);
-    const float px = es[21], py = es[22], pz = es[23];
-#ifdef IMX_TRACE
-    const uint64_t trace_tp = 0;
-    const uint64_t trace_t0 = wall_clock64();
-    uint64_t trace_t1 = 0, trace_t2 = 0;
-#endif
-    // -- phase A: the env's rays.  RayCaster._update_buffers_impl (ray_caster.py:242-260): ray j of the scanner -> hit height into LDS.
-    //    Kept apart from the column loop below on purpose: what limits this kernel is how many waves a SIMD can hold (wave life x
-    //    residency, tools/trace_kobs.py), i.e. its register count -- a ray lane carries the ray and one cell's data, a column lane its
-    //    16-word column record, never both.
-    if (P.R > 0) {
-        const float* __restrict__ ray_local = reinterpret_cast<const float*>(W + P.ray_off);
-        for (int j = threadIdx.x; j < P.R; j += blockDim.x) {
-            float hz;
-            if (cast) {
-                hz = scan_ray<GENERAL_RAYS>(P, M, es, ray_local, j, px, py, pz, yw, yz, ray_hits_out, e);
-                if (cache_z) Bf.scan_hit_z[(size_t)e * P.R + j] = hz;
-            } else {
-                hz = Bf.scan_hit_z[(size_t)e * P.R + j];  // data.ray_hits_w of the last update
-            }
-            s_hz[j] = hz;
-        }
-#ifdef IMX_TRACE
-        trace_t1 = wall_clock64();
-#endif
-        __syncthreads();
-#ifdef IMX_TRACE
-        trace_t2 = wall_clock64();
-#endif
-    }
-    if (e == 0 && threadIdx.x == 0) Bf.counters[3] = (int32_t)step;  // the shadow the next step kernel counts on from
-    // -- phase B: the observation columns (ObservationManager.compute_group, observation_manager.py:260-335)
-    for (int i = threadIdx.x; i < P.DC; i += blockDim.x) {
-        const XCol x = load_xcol(W, P.xcol_off, i);
-        const int op = x.a.y, j = x.a.z;
-        float v;
-        if (op == IMX_O_HEIGHT_SCAN) {  // height_scan (observations.py:165-173): sensor.data.pos_w z - hit z - offset
-            const float hz = s_hz[j];
-            v = pz - hz - f_of(x.b.x);
-            // further height_scan terms on the same sensor (another group, another offset / noise / clip): same hit, own post-processing
-            for (int nx = LEAN ? 0 : x.c.z; nx != 0;) {
-                const XCol tw = load_xcol(W, P.xcol_off, nx - 1);
-                obs_finish<false>(P, Bf, tw, nx - 1, pz - hz - f_of(tw.b.x), e, corrupt, fill_all, noise_u, seed, step);
-                nx = tw.c.z;
-            }
-        } else {
-            v = obs_plain_value<true>(P, S, Bf, es, e, x);
-        }
-        obs_finish<LEAN>(P, Bf, x, i, v, e, corrupt, fill_all, noise_u, seed, step);
-    }
-#ifdef IMX_TRACE
-    if (g_trace && (threadIdx.x & 63) == 0) {
-        uint64_t* t = g_trace + ((size_t)e * 4 + (threadIdx.x >> 6)) * 8;
-        t[0] = trace_t0; t[1] = wall_clock64();
-        t[2] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_ID (wave/simd/cu/sh/se ids)
-        t[3] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11));   // XCC_ID
-        t[4] = trace_t1; t[5] = trace_t2; t[6] = trace_tp;
-    }
-#endif
+#include "obs_body.inc"
+}
+
+// INHAND: a plan whose observations read the rigid object's root state (root_pos_w / root_quat_w / root_lin_vel_w / root_ang_vel_w with
+// asset word 1) or goal_quat_diff (Isaac-Repose-Cube-Allegro-v0) runs the same body in a kernel of its own, with the general ray path
+// (a plan without a height scanner casts nothing): k_obs<...> and k_obs_lean<...> stay the instruction streams they were.
+template <bool LEAN>
+__global__ void __launch_bounds__(256)
+k_obs_inhand(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, MeshView M, const float* __restrict__ frame,
+             const float* __restrict__ noise_u, uint64_t seed, int corrupt, float* __restrict__ ray_hits_out, StepScratch sc, int tail_G,
+             int tail_parts, imx_object_state_t X) {
+    constexpr bool GENERAL_RAYS = true;
+#define IMX_OBS_INHAND
+#include "obs_body.inc"
+#undef IMX_OBS_INHAND
 }
 
 // ------------------------------------------------------------------------------------------------- root frame
@@ -1001,6 +965,11 @@ extern "C" int imx_terminations_rewards_rollout(const imx_plan_t* plan, int64_t 
             case IMX_T_OBJECT_REACHED_GOAL:
                 if (need(st->command, "command") || need(st->root_pos_w, "root_pos_w") || need(st->object_root_pos_w, "object_root_pos_w")) return 1;
                 break;
+            case IMX_T_MAX_CONSECUTIVE_SUCCESS: if (need(plan->object_state.command_consecutive_success, "command_consecutive_success")) return 1; break;
+            case IMX_T_OBJECT_AWAY_FROM_GOAL:
+                if (need(st->command, "command") || need(st->env_origins, "env_origins") || need(st->object_root_pos_w, "object_root_pos_w")) return 1;
+                break;
+            case IMX_T_OBJECT_AWAY_FROM_ROBOT: if (need(st->root_pos_w, "root_pos_w") || need(st->object_root_pos_w, "object_root_pos_w")) return 1; break;
             case IMX_T_JOINT_VEL_LIMIT: if (need(st->joint_vel, "joint_vel") || need(st->soft_joint_vel_limits, "soft_joint_vel_limits")) return 1; break;
             case IMX_T_JOINT_VEL_MANUAL_LIMIT: if (need(st->joint_vel, "joint_vel")) return 1; break;
             case IMX_T_JOINT_EFFORT_LIMIT: if (need(st->computed_torque, "computed_torque") || need(st->applied_torque, "applied_torque")) return 1; break;
@@ -1059,6 +1028,12 @@ extern "C" int imx_terminations_rewards_rollout(const imx_plan_t* plan, int64_t 
                 if (need(st->command, "command") || need(st->root_pos_w, "root_pos_w") || need(st->object_root_pos_w, "object_root_pos_w")) return 1;
                 break;
             case IMX_W_NAV_POSITION_COMMAND_ERROR_TANH: case IMX_W_NAV_HEADING_COMMAND_ERROR_ABS: if (need(st->command, "command")) return 1; break;
+            case IMX_W_TRACK_ORIENTATION_INV_L2: case IMX_W_SUCCESS_BONUS:
+                if (need(st->command, "command") || need(plan->object_state.object_root_quat_w, "object_root_quat_w")) return 1;
+                break;
+            case IMX_W_TRACK_POS_L2:
+                if (need(st->command, "command") || need(st->env_origins, "env_origins") || need(st->object_root_pos_w, "object_root_pos_w")) return 1;
+                break;
             default: break;
         }
     }
@@ -1074,25 +1049,36 @@ extern "C" int imx_terminations_rewards_rollout(const imx_plan_t* plan, int64_t 
     // one wave per work item (termination or reward term) up to 16 waves; more items go round-robin
     const int items = plan->nterm + plan->nrew;
     const int NW = items < 2 ? 2 : (items > IMX_TR_MAX_WAVES ? IMX_TR_MAX_WAVES : items);
-    const size_t lds = ((size_t)(plan->nterm > 0 ? plan->nterm : 1) * 64 + 3 * (size_t)(plan->nrew > 0 ? plan->nrew : 1) * 64) * 4;
+    size_t lds = ((size_t)(plan->nterm > 0 ? plan->nterm : 1) * 64 + 3 * (size_t)(plan->nrew > 0 ? plan->nrew : 1) * 64) * 4;
     // with the root position at hand the kernel also leaves the frame table imx_observations needs (flag 4 there skips k_frame)
     float* frame = st->root_pos_w ? reinterpret_cast<float*>(reinterpret_cast<char*>(bf->scratch) + frame_offset_bytes(plan, N)) : nullptr;
-    bool classic = false, reach = false, lift = false, nav = false;
+    bool classic = false, reach = false, lift = false, nav = false, inhand = false, need_dtheta = false, object_height = false;
     for (int k = 0; k < plan->nrew; ++k) {
         const int op = w[plan->rew_off + k * IMX_REC_WORDS + IMX_R_OP];
         classic = classic || (op >= IMX_W_UPRIGHT_POSTURE_BONUS && op <= IMX_W_POWER_CONSUMPTION);
         reach = reach || (op >= IMX_W_POSITION_COMMAND_ERROR && op <= IMX_W_OBJECT_GOAL_DISTANCE);
         lift = lift || (op >= IMX_W_OBJECT_IS_LIFTED && op <= IMX_W_OBJECT_GOAL_DISTANCE);
-        nav = nav || op >= IMX_W_NAV_POSITION_COMMAND_ERROR_TANH;
+        nav = nav || (op >= IMX_W_NAV_POSITION_COMMAND_ERROR_TANH && op <= IMX_W_NAV_HEADING_COMMAND_ERROR_ABS);
+        inhand = inhand || (op >= IMX_W_TRACK_ORIENTATION_INV_L2 && op <= IMX_W_TRACK_POS_L2);
+        need_dtheta = need_dtheta || op == IMX_W_TRACK_ORIENTATION_INV_L2 || op == IMX_W_SUCCESS_BONUS;
     }
     for (int k = 0; k < plan->nterm; ++k) {  // the terminations on the object
         const int32_t* r = &w[plan->term_off + k * IMX_REC_WORDS];
-        lift = lift || r[IMX_R_OP] == IMX_T_OBJECT_REACHED_GOAL || (r[IMX_R_OP] == IMX_T_ROOT_HEIGHT_BELOW_MIN && r[IMX_R_AUX0]);
+        lift = lift || r[IMX_R_OP] == IMX_T_OBJECT_REACHED_GOAL;
+        object_height = object_height || (r[IMX_R_OP] == IMX_T_ROOT_HEIGHT_BELOW_MIN && r[IMX_R_AUX0]);
+        inhand = inhand || (r[IMX_R_OP] >= IMX_T_MAX_CONSECUTIVE_SUCCESS && r[IMX_R_OP] <= IMX_T_OBJECT_AWAY_FROM_ROBOT);
     }
+    lift = lift || (object_height && !inhand);  // root_height_below_minimum on the object: the lift kernel, or the in-hand one beside its ops
     reach = reach || lift;
+    IMX_REQUIRE(!(inhand && (classic || reach || nav)),
+                "imx_terminations_rewards: a plan with in-hand (manipulation/inhand) ops beside classic/humanoid, reach, lift or navigation ops is not supported");
     IMX_REQUIRE(!(classic && reach), "imx_terminations_rewards: a plan with both classic/humanoid and manipulation/reach or lift ops is not supported");
     IMX_REQUIRE(!(nav && (classic || reach)), "imx_terminations_rewards: a plan with navigation reward ops beside classic/humanoid, reach or lift ops is not supported");
-    if (nav)
+    if (inhand) {
+        lds += 64 * 4;  // the env's orientation error
+        hipLaunchKernelGGL(k_term_rew_inhand, dim3(grid), dim3(64 * NW), lds, (hipStream_t)stream, imx_plan_view(plan), N, *st, *bf, sc, frame, G,
+                           flags & 1, ro, need_dtheta ? 1 : 0, plan->object_state);
+    } else if (nav)
         hipLaunchKernelGGL(k_term_rew_nav, dim3(grid), dim3(64 * NW), lds, (hipStream_t)stream, imx_plan_view(plan), N, *st, *bf, sc, frame, G,
                            flags & 1, ro);
     else if (lift)
@@ -1141,6 +1127,7 @@ struct ObsKernelChoice {
     bool lean;         // one group, no modifier programs, no history windows, no gaussian noise (DC == D also rules out twin scan columns)
     bool vertical;     // height-scanner frame yaw-only + vertical direction (the reference cfg): register-lean single-cell ray path
     bool single_wave;  // k_obs_lean: one single-wave workgroup per 64 rays + one for the env's other columns
+    bool inhand;       // k_obs_inhand: a root observation on the rigid object (asset word 1) or goal_quat_diff
     int scan_rec;
 };
 static ObsKernelChoice choose_obs_kernel(const imx_plan_t* plan) {
@@ -1151,12 +1138,16 @@ static ObsKernelChoice choose_obs_kernel(const imx_plan_t* plan) {
     for (int k = 0; k < plan->nobs && c.lean; ++k) c.lean = !(w[plan->obs_off + k * IMX_REC_WORDS + IMX_R_FLAGS] & (IMX_F_MODIFIERS | IMX_F_NOISE_GAUSS));
     c.vertical = pv.R == 0 || (pv.ray_yaw_only && pv.rdx == 0.0f && pv.rdy == 0.0f && pv.rdz != 0.0f);
     c.scan_rec = -1;
+    c.inhand = false;
     bool object_op = false;  // (k_obs_lean is compiled without it)
     for (int k = 0; k < plan->nobs; ++k) {
         if (w[plan->obs_off + k * IMX_REC_WORDS + IMX_R_OP] == IMX_O_HEIGHT_SCAN) c.scan_rec = k;
-        object_op = object_op || w[plan->obs_off + k * IMX_REC_WORDS + IMX_R_OP] == IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME;
+        const int op = w[plan->obs_off + k * IMX_REC_WORDS + IMX_R_OP];
+        object_op = object_op || op == IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME;
+        c.inhand = c.inhand || op == IMX_O_GOAL_QUAT_DIFF ||
+                   (op >= IMX_O_ROOT_POS_W && op <= IMX_O_ROOT_ANG_VEL_W && w[plan->obs_off + k * IMX_REC_WORDS + IMX_R_AUX0]);
     }
-    c.single_wave = c.lean && c.scan_rec >= 0 && pv.R > 0 && pv.R <= 64 * 15 && !object_op;
+    c.single_wave = c.lean && c.scan_rec >= 0 && pv.R > 0 && pv.R <= 64 * 15 && !object_op && !c.inhand;
     return c;
 }
 
@@ -1164,6 +1155,7 @@ extern "C" const char* imx_observations_kernel_name(const imx_plan_t* plan) {
     if (!plan) return "";
     const ObsKernelChoice c = choose_obs_kernel(plan);
     if (c.single_wave) return c.vertical ? "k_obs_lean<false>" : "k_obs_lean<true>";
+    if (c.inhand) return c.lean ? "k_obs_inhand<true>" : "k_obs_inhand<false>";
     if (c.vertical) return c.lean ? "k_obs<false,true>" : "k_obs<false,false>";
     return c.lean ? "k_obs<true,true>" : "k_obs<true,false>";
 }
@@ -1190,8 +1182,19 @@ extern "C" int imx_observations(const imx_plan_t* plan, int64_t N, const imx_sta
         const int op = w[plan->obs_off + k * IMX_REC_WORDS + IMX_R_OP];
         const void* p = (const void*)1;
         const char* name = "";
+        const bool on_object = w[plan->obs_off + k * IMX_REC_WORDS + IMX_R_AUX0] != 0;  // (read for the four root ops only)
         switch (op) {
-            case IMX_O_ROOT_POS_W: p = st->env_origins; name = "env_origins"; break;
+            case IMX_O_ROOT_POS_W:
+                p = st->env_origins; name = "env_origins";
+                if (p && on_object) { p = st->object_root_pos_w; name = "object_root_pos_w"; }
+                break;
+            case IMX_O_ROOT_QUAT_W: if (on_object) { p = plan->object_state.object_root_quat_w; name = "object_root_quat_w"; } break;
+            case IMX_O_ROOT_LIN_VEL_W: if (on_object) { p = plan->object_state.object_root_lin_vel_w; name = "object_root_lin_vel_w"; } break;
+            case IMX_O_ROOT_ANG_VEL_W: if (on_object) { p = plan->object_state.object_root_ang_vel_w; name = "object_root_ang_vel_w"; } break;
+            case IMX_O_GOAL_QUAT_DIFF:
+                p = plan->object_state.object_root_quat_w; name = "object_root_quat_w";
+                if (p && !st->command) { p = nullptr; name = "command"; }
+                break;
             case IMX_O_JOINT_POS: p = st->joint_pos; name = "joint_pos"; break;
             case IMX_O_JOINT_POS_REL: p = (st->joint_pos && st->default_joint_pos) ? (const void*)1 : nullptr; name = "joint_pos/default_joint_pos"; break;
             case IMX_O_JOINT_POS_LIMIT_NORMALIZED: p = (st->joint_pos && st->soft_joint_pos_limits) ? (const void*)1 : nullptr; name = "joint_pos/soft_joint_pos_limits"; break;
@@ -1262,7 +1265,14 @@ extern "C" int imx_observations(const imx_plan_t* plan, int64_t N, const imx_sta
     } else {
         if (tail) tail_parts = 1 + ((nlog < 16 ? nlog : 16) * 64 + bs - 1) / bs;
         const unsigned grid = (unsigned)N + (unsigned)tail_parts;
-        if (vertical) { if (lean) IMX_LAUNCH_OBS(false, true); else IMX_LAUNCH_OBS(false, false); }
+        if (ch.inhand) {
+            if (lean)
+                hipLaunchKernelGGL(k_obs_inhand<true>, dim3(grid), dim3(bs), lds, (hipStream_t)stream, pv, N, *st, *bf, mv, frame, noise_u_d, seed,
+                                   enable_corruption, ray_hits_out_d, sc, tail_G, tail_parts, plan->object_state);
+            else
+                hipLaunchKernelGGL(k_obs_inhand<false>, dim3(grid), dim3(bs), lds, (hipStream_t)stream, pv, N, *st, *bf, mv, frame, noise_u_d, seed,
+                                   enable_corruption, ray_hits_out_d, sc, tail_G, tail_parts, plan->object_state);
+        } else if (vertical) { if (lean) IMX_LAUNCH_OBS(false, true); else IMX_LAUNCH_OBS(false, false); }
         else { if (lean) IMX_LAUNCH_OBS(true, true); else IMX_LAUNCH_OBS(true, false); }
     }
 #undef IMX_LAUNCH_OBS

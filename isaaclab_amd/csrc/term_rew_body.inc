@@ -1,5 +1,5 @@
 // The body of k_term_rew (step.hip), included once per kernel: in k_term_rew<CLASSIC, REACH> as it always was, and with IMX_TR_LIFT
-// defined in k_term_rew_lift.  A textual include, not a device function: the kernels of the existing tasks then compile to the very
+// defined in k_term_rew_lift, IMX_TR_NAV in k_term_rew_nav, IMX_TR_INHAND in k_term_rew_inhand.  A textual include, not a device function: the kernels of the existing tasks then compile to the very
 // instruction streams they had (a shared force-inlined body moved their register allocation and cost them 0.4 us per launch).
     extern __shared__ int32_t smem[];
     const int lane = threadIdx.x & 63;
@@ -24,6 +24,15 @@
     float* s_f = reinterpret_cast<float*>(s_tv + (nterm > 0 ? nterm : 1) * 64);
     float* s_es = s_f + nrew * 64;
     float* s_val = s_es + nrew * 64;
+#ifdef IMX_TR_INHAND
+    // dtheta = quat_error_magnitude(object_root_quat_w, cmd[3:7]) of the env, once for all the terms that read it: the last wave (it has
+    // the fewest items) leaves it in 64 more floats of LDS before the barrier that ends phase 1; the rewards read it in phase 2
+    float* s_dth = s_val + nrew * 64;
+    if (need_dtheta && wv == NW - 1) {
+        const float* __restrict__ gq = S.command + ec * P.CMD + 3;
+        s_dth[lane] = quat_error_magnitude(reinterpret_cast<const float4*>(X.object_root_quat_w)[ec], make_float4(gq[0], gq[1], gq[2], gq[3]));
+    }
+#endif
 
     // -- phase 0: everything that needs no table is issued at once: root state, and the episodic sum of this wave's first reward item
     const int first_rew = wv >= nterm ? wv - nterm : wv - nterm + ((nterm - wv + NW - 1) / NW) * NW;  // first item >= nterm of this wave
@@ -84,7 +93,7 @@
                     v = any_ids(ids, n, [&](int j) { const float q = S.joint_pos[ec * J + j]; return (q > p1) || (q < p0); });
                     break;
                 case IMX_T_BAD_ORIENTATION: v = fabsf(acosf(-pgz)) > p0; break;
-#ifdef IMX_TR_LIFT  // (the object's root only in the lift kernel: the launch sends such a plan there)
+#if defined(IMX_TR_LIFT) || defined(IMX_TR_INHAND)  // (the object's root only in these kernels: the launch sends such a plan there)
                 case IMX_T_ROOT_HEIGHT_BELOW_MIN: v = (r[IMX_R_AUX0] ? S.object_root_pos_w : S.root_pos_w)[ec * 3 + 2] < p0; break;
 #else
                 case IMX_T_ROOT_HEIGHT_BELOW_MIN: v = S.root_pos_w[ec * 3 + 2] < p0; break;
@@ -113,6 +122,23 @@
                         float px, py, pz;
                         command_des_pos_w(S.root_pos_w + ec * 3, q4, cmdx, cmdy, cmdz, px, py, pz);
                         v = object_goal_dist(S.object_root_pos_w + ec * 3, px, py, pz) < p0;
+                    }
+                    break;
+#endif
+#ifdef IMX_TR_INHAND  // inhand/mdp/terminations.py; cmdx, cmdy, cmdz = cmd[:3] of phase 0: the goal position in the env frame
+                case IMX_T_MAX_CONSECUTIVE_SUCCESS: v = X.command_consecutive_success[ec] >= p0; break;  // :18-28
+                case IMX_T_OBJECT_AWAY_FROM_GOAL: {  // :31-56: (object - origin) - goal, the norm as sqrt((x^2 + y^2) + z^2)
+                        const float dx = (S.object_root_pos_w[ec * 3] - S.env_origins[ec * 3]) - cmdx;
+                        const float dy = (S.object_root_pos_w[ec * 3 + 1] - S.env_origins[ec * 3 + 1]) - cmdy;
+                        const float dz = (S.object_root_pos_w[ec * 3 + 2] - S.env_origins[ec * 3 + 2]) - cmdz;
+                        v = sqrtf((dx * dx + dy * dy) + dz * dz) > p0;
+                    }
+                    break;
+                case IMX_T_OBJECT_AWAY_FROM_ROBOT: {  // :59-83
+                        const float dx = S.root_pos_w[ec * 3] - S.object_root_pos_w[ec * 3];
+                        const float dy = S.root_pos_w[ec * 3 + 1] - S.object_root_pos_w[ec * 3 + 1];
+                        const float dz = S.root_pos_w[ec * 3 + 2] - S.object_root_pos_w[ec * 3 + 2];
+                        v = sqrtf((dx * dx + dy * dy) + dz * dz) > p0;
                     }
                     break;
 #endif
@@ -360,6 +386,9 @@
             if (CLASSIC && op >= IMX_W_UPRIGHT_POSTURE_BONUS) f = classic_reward(P, S, Bf, r, op, live ? e : min(grp * G, N - 1), N);
 #ifdef IMX_TR_NAV
             if (op >= IMX_W_NAV_POSITION_COMMAND_ERROR_TANH) f = nav_reward(P, S, r, op, live ? e : min(grp * G, N - 1));
+#endif
+#ifdef IMX_TR_INHAND
+            if (op >= IMX_W_TRACK_ORIENTATION_INV_L2) f = inhand_reward(P, S, r, op, live ? e : min(grp * G, N - 1), s_dth[lane]);
 #endif
 #ifdef IMX_TR_LIFT
             if (op >= IMX_W_POSITION_COMMAND_ERROR && op < IMX_W_OBJECT_IS_LIFTED) f = reach_reward(P, S, r, op, live ? e : min(grp * G, N - 1));

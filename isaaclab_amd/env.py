@@ -716,6 +716,11 @@ class ManagerBasedRLEnv:
         if state_feed.num_envs != N or torch.device(state_feed.device) != self.device:
             raise ValueError("state_feed has a different num_envs/device than the env")
         self.feed = state_feed
+        if plan.state_reads:  # the rigid object's further root state / the in-hand command's metric: served on request
+            try:
+                state_feed.ensure_object_state()
+            except KeyError:  # a recorded feed without them: the launch checks refuse the step and name the missing tensor
+                pass
         self.step_dt = plan.step_dt
         self.physics_dt = float(env_dict["sim"]["dt"])
         self.max_episode_length = plan.max_episode_length
@@ -808,6 +813,7 @@ class ManagerBasedRLEnv:
             scan_state=_lib.ptr(self._scan_state), scan_hit_z=_lib.ptr(self._scan_hit_z), term_state=_lib.ptr(self._term_state),
             **{f"obs_extra{g}": self._obs_groups[g].data_ptr() for g in range(1, len(self._obs_groups))})
         self._state_cache: dict[int, ImxState] = {}
+        self._object_state_cache: dict[int, _lib.ImxObjectState] = {}
         self._root_cache = None
 
         if self._pp is not None:
@@ -823,10 +829,23 @@ class ManagerBasedRLEnv:
         cmds = (env_dict.get("commands") or {})
         if command_term is not None:
             from .plan import command_width
-            from .producers import UniformPose2dCommand, UniformPoseCommand, UniformVelocityCommand
+            from .plan import _INHAND_COMMAND
+            from .producers import InHandReOrientationCommand, UniformPose2dCommand, UniformPoseCommand, UniformVelocityCommand
 
             if use_command_term:
                 raise ValueError("pass either command_term= or use_command_term=True, not both")
+            by_name = isinstance(command_term, str) and func_name_of((cmds.get(command_term) or {}).get("class_type")) == _INHAND_COMMAND
+            if by_name or isinstance(command_term, InHandReOrientationCommand):
+                if events_cfg:  # (own_managers=True: what the cfg's EventManager lacks is named first)
+                    from .events import EventManager
+
+                    EventManager(env_dict.get("events") if events_cfg is True else events_cfg, N, plan.robot, self.device, seed=noise_seed,
+                                 entities=self._entities, scene=env_dict.get("scene"))
+                what = f"command_term='{command_term}'" if by_name else "command_term=<producers.InHandReOrientationCommand>"
+                raise NotImplementedError(f"{what}: the InHandReOrientationCommand producer (producers.InHandReOrientationCommand, "
+                                          "imx_inhand_command) is stand-alone: the orchestration launch does not run it yet.  This cfg's (N, 7) "
+                                          "command and its consecutive_success metric come from the state feed (drop command_term= / "
+                                          "own_managers=True)")
             if isinstance(command_term, str):
                 if cmds.get(command_term) is None:
                     raise ValueError(f"command_term='{command_term}': the env cfg has no such command term (it has {list(cmds)})")
@@ -1199,6 +1218,10 @@ class ManagerBasedRLEnv:
             kw["ext_obs"] = _lib.ptr(self._ext_obs)
             st = ImxState(**kw)
             self._state_cache[idx] = st
+            # the in-hand task's further tensors travel beside the state struct (imx_object_state_t), per snapshot like it
+            self._object_state_cache[idx] = _lib.ImxObjectState(**{n: snap[n].data_ptr() for n in _lib.OBJECT_STATE_FIELDS if n in snap})
+        if self.plan.state_reads:  # bound to the plan for the launches made with this state
+            check(self._lib.imx_plan_bind_object_state(self._plan_h, ctypes.byref(self._object_state_cache[idx])))
         return st
 
     def _root_frame(self) -> dict:

@@ -50,14 +50,18 @@ _LIFT = "isaaclab_tasks.manager_based.manipulation.lift.mdp"  # .observations, .
 _POSE_COMMAND = "isaaclab.envs.mdp.commands.pose_command:UniformPoseCommand"  # command = (N, 7): position + quaternion, base frame
 _NAV = "isaaclab_tasks.manager_based.navigation.mdp"  # .rewards, .pre_trained_policy_action (Isaac-Navigation-Flat-Anymal-C-v0)
 # command = (N, 4): pos_command_b 3 + heading_command_b 1 (pose_2d_command.py: UniformPose2dCommand.command and its terrain-based subclass)
+_INHAND = "isaaclab_tasks.manager_based.manipulation.inhand.mdp"  # .observations, .rewards, .terminations (Isaac-Repose-Cube-Allegro-v0)
+# command = (N, 7): pos_command_e 3 (the ENV frame) + quat_command_w 4 (orientation_command.py:75-78)
+_INHAND_COMMAND = f"{_INHAND}.commands.orientation_command:InHandReOrientationCommand"
 _POSE_2D_COMMANDS = tuple(f"isaaclab.envs.mdp.commands.pose_2d_command:{c}" for c in ("UniformPose2dCommand", "TerrainBasedPose2dCommand"))
 
 
 def command_width(command_cfg: dict | None) -> int:
-    """Width of a command term's ``command``: 7 for a ``UniformPoseCommand`` (pose_command.py:71-72), 4 for a ``UniformPose2dCommand`` /
+    """Width of a command term's ``command``: 7 for a ``UniformPoseCommand`` (pose_command.py:71-72) and an ``InHandReOrientationCommand``
+    (inhand/mdp/commands/orientation_command.py:75-78), 4 for a ``UniformPose2dCommand`` /
     ``TerrainBasedPose2dCommand`` (pose_2d_command.py), 3 for any other (the base velocity command every other task uses)."""
     cls = func_name(command_cfg.get("class_type")) if command_cfg is not None else None
-    return 7 if cls == _POSE_COMMAND else 4 if cls in _POSE_2D_COMMANDS else 3
+    return 7 if cls in (_POSE_COMMAND, _INHAND_COMMAND) else 4 if cls in _POSE_2D_COMMANDS else 3
 
 
 def f32(x: float) -> float:
@@ -400,6 +404,9 @@ class Plan:
     ik_terms: list = dataclasses.field(default_factory=list)  # IkTerm of the env's DifferentialInverseKinematicsAction (at most one)
     osc_terms: list = dataclasses.field(default_factory=list)  # OscTerm of the env's OperationalSpaceControllerAction (at most one, and no IkTerm beside it)
     policy_terms: list = dataclasses.field(default_factory=list)  # PolicyTerm of the env's PreTrainedPolicyAction (at most one, no IK / OSC term beside it)
+    # which of the rigid object's further state tensors and of the in-hand command's metrics the terms read (state_feed.OBJECT_STATE
+    # names, sorted): the env asks the feed for them (StateFeed.ensure_object_state); a plan that reads none allocates none
+    state_reads: tuple = ()
 
 
 @dataclasses.dataclass
@@ -544,7 +551,8 @@ class _Fused:
 # of theirs without a table entry is refused in the managers named here.  Any other unknown function is Python-evaluated (``EXTERNAL``).
 _CLOSED = {_SPOT: ("reward",), _REACH: ("reward",), **{f"{_CLASSIC}.{m}": ("termination", "reward", "observation") for m in ("observations", "rewards")},
            **{f"{_LIFT}.{m}": ("termination", "reward", "observation") for m in ("observations", "rewards", "terminations")},
-           f"{_NAV}.rewards": ("reward",)}
+           f"{_NAV}.rewards": ("reward",),
+           **{f"{_INHAND}.{m}": ("termination", "reward", "observation") for m in ("observations", "rewards", "terminations")}}
 
 
 def _target_pos(kind: str, name: str, p: dict) -> list[float]:
@@ -660,6 +668,91 @@ def _object_position(c, name, p, rec):
     _object(c, "observation", name, p)
 
 
+# -- the in-hand task's own terms (isaaclab_tasks .../manipulation/inhand/mdp: Isaac-Repose-Cube-Allegro-v0)
+def _inhand_command(c, kind, name, p, threshold=False) -> dict:
+    """``command_name`` must name a command term of the cfg whose command is (N, 7); with ``threshold`` its cfg must carry
+    ``orientation_success_threshold`` (an ``InHandReOrientationCommandCfg``: the term reads that field or the term's
+    ``consecutive_success`` metric, which a ``UniformPoseCommand`` does not have).  Returns the command cfg."""
+    cname = p.get("command_name")
+    ccfg = (c.cfg.get("commands") or {}).get(cname)
+    if ccfg is None:
+        raise ValueError(f"{kind} term '{name}': command_name '{cname}' is not a command term of the cfg (it has {list(c.cfg.get('commands') or {})})")
+    if command_width(ccfg) != 7 or c.cmd_dim != 7:
+        raise ValueError(f"{kind} term '{name}': command '{cname}' must be an InHandReOrientationCommand (N, 7); it is {command_width(ccfg)} wide")
+    if threshold and not isinstance(ccfg.get("orientation_success_threshold"), (int, float)):
+        raise NotImplementedError(f"{kind} term '{name}': command '{cname}' ({func_name(ccfg.get('class_type'))}) has no "
+                                  "orientation_success_threshold: the term reads the success threshold / the consecutive_success metric of an "
+                                  "InHandReOrientationCommand, which a UniformPoseCommand does not have")
+    return ccfg
+
+
+def _reads(c, *names):
+    c.state_reads.update(names)
+
+
+def _max_consecutive_success(c, name, p, rec):
+    _inhand_command(c, "termination", name, p, threshold=True)
+    _reads(c, "command_consecutive_success")
+    rec["p0"] = f32(p["num_success"])  # (the metric is a float tensor: `>= num_success` compares in fp32)
+
+
+def _object_away_from_goal(c, name, p, rec):
+    _inhand_command(c, "termination", name, p)
+    _object(c, "termination", name, p)
+
+
+def _object_away_from_robot(c, name, p, rec):
+    _robot(c, "termination", name, p, key="asset_cfg")
+    _object(c, "termination", name, p)
+
+
+def _track_orientation(c, name, p, rec):
+    _inhand_command(c, "reward", name, p)
+    _object(c, "reward", name, p)
+    _reads(c, "object_root_quat_w")
+
+
+def _success_bonus(c, name, p, rec):
+    ccfg = _inhand_command(c, "reward", name, p, threshold=True)
+    _object(c, "reward", name, p)
+    _reads(c, "object_root_quat_w")
+    rec["p0"] = f32(ccfg["orientation_success_threshold"])
+
+
+def _track_pos(c, name, p, rec):
+    _inhand_command(c, "reward", name, p)
+    _object(c, "reward", name, p)
+
+
+def _goal_quat_diff(c, name, p, rec):
+    _inhand_command(c, "observation", name, p)
+    if p.get("asset_cfg") is None:
+        raise KeyError(f"observation term '{name}': goal_quat_diff needs 'asset_cfg'")
+    _object(c, "observation", name, p, key="asset_cfg")
+    _reads(c, "object_root_quat_w")
+    _quat_unique(c, name, p, rec)
+
+
+_ROOT_OBJECT_READS = {"ROOT_QUAT_W": "object_root_quat_w", "ROOT_LIN_VEL_W": "object_root_lin_vel_w", "ROOT_ANG_VEL_W": "object_root_ang_vel_w"}
+
+
+def _root_asset(op, c, name, p, rec):
+    """``asset_cfg`` of the four root observations selects whose root: the robot (AUX0 = 0, the word every older blob has) or the scene's
+    rigid object (AUX0 = 1), as for ``root_height_below_minimum``.  Anything else is refused."""
+    ent = _entity_name(p.get("asset_cfg"), "robot")
+    if ent in c.entities.rigid_objects:
+        _object(c, "observation", name, p, key="asset_cfg")
+        rec["aux0"] = 1
+        if op in _ROOT_OBJECT_READS:
+            _reads(c, _ROOT_OBJECT_READS[op])
+    elif ent != "robot":
+        c.entities.names(ent, "body")  # raises: the entity does not exist
+        raise NotImplementedError(f"observation term '{name}': asset_cfg names the scene entity '{ent}'; the fused op reads the root state of "
+                                  "the robot or of the scene's rigid object")
+    if op == "ROOT_QUAT_W":
+        _quat_unique(c, name, p, rec)
+
+
 _T = f"{_MDP}.terminations:"
 TERMINATION_TERMS = {
     _T + "time_out": _Fused("TIME_OUT"),
@@ -673,6 +766,9 @@ TERMINATION_TERMS = {
     _T + "command_resample": _Fused("COMMAND_RESAMPLE", hook=_command_resample),
     f"{_VEL}.terminations:terrain_out_of_bounds": _Fused("TERRAIN_OUT_OF_BOUNDS", hook=_terrain_out_of_bounds),
     f"{_LIFT}.terminations:object_reached_goal": _Fused("OBJECT_REACHED_GOAL", params=(("threshold", 0.02),), hook=_object_reached_goal),  # :25-53
+    f"{_INHAND}.terminations:max_consecutive_success": _Fused("MAX_CONSECUTIVE_SUCCESS", hook=_max_consecutive_success),  # :18-28
+    f"{_INHAND}.terminations:object_away_from_goal": _Fused("OBJECT_AWAY_FROM_GOAL", params=("threshold",), hook=_object_away_from_goal),  # :31-56
+    f"{_INHAND}.terminations:object_away_from_robot": _Fused("OBJECT_AWAY_FROM_ROBOT", params=("threshold",), hook=_object_away_from_robot),  # :59-83
 }
 
 
@@ -821,6 +917,9 @@ REWARD_TERMS = {
     f"{_LIFT}.rewards:object_is_lifted": _Fused("OBJECT_IS_LIFTED", params=("minimal_height",), hook=_object_is_lifted),  # :20-25
     f"{_LIFT}.rewards:object_ee_distance": _Fused("OBJECT_EE_DISTANCE", params=("std",), hook=_object_ee_distance),  # :28-45
     f"{_LIFT}.rewards:object_goal_distance": _Fused("OBJECT_GOAL_DISTANCE", params=("std", "minimal_height"), hook=_object_goal_distance),  # :48-67
+    f"{_INHAND}.rewards:track_orientation_inv_l2": _Fused("TRACK_ORIENTATION_INV_L2", params=(("rot_eps", 1.0e-3),), hook=_track_orientation),  # :71-96
+    f"{_INHAND}.rewards:success_bonus": _Fused("SUCCESS_BONUS", hook=_success_bonus),  # :20-44
+    f"{_INHAND}.rewards:track_pos_l2": _Fused("TRACK_POS_L2", hook=_track_pos),  # :47-68
 }
 
 
@@ -875,10 +974,10 @@ def _height_scan(c, name, p, rec):
 
 _O, _OC = f"{_MDP}.observations:", f"{_CLASSIC}.observations:"
 OBSERVATION_TERMS = {
-    **{_O + f: _Fused(f.upper(), width=w) for f, w in (("base_pos_z", 1), ("base_lin_vel", 3), ("base_ang_vel", 3), ("projected_gravity", 3),
-                                                       ("root_pos_w", 3), ("root_lin_vel_w", 3), ("root_ang_vel_w", 3))},
+    **{_O + f: _Fused(f.upper(), width=w) for f, w in (("base_pos_z", 1), ("base_lin_vel", 3), ("base_ang_vel", 3), ("projected_gravity", 3))},
+    **{_O + f: _Fused(f.upper(), width=w, hook=functools.partial(_root_asset, f.upper()))
+       for f, w in (("root_pos_w", 3), ("root_quat_w", 4), ("root_lin_vel_w", 3), ("root_ang_vel_w", 3))},
     **{_O + f: _Fused(f.upper(), _JOINTS) for f in ("joint_pos", "joint_pos_rel", "joint_pos_limit_normalized", "joint_vel", "joint_vel_rel")},
-    _O + "root_quat_w": _Fused("ROOT_QUAT_W", width=4, hook=_quat_unique),
     _O + "height_scan": _Fused("HEIGHT_SCAN", hook=_height_scan),
     _O + "last_action": _Fused("LAST_ACTION", hook=_last_action, applies=lambda p: p.get("action_name") is None),
     _O + "generated_commands": _Fused("GENERATED_COMMANDS", hook=_generated_commands),
@@ -888,6 +987,7 @@ OBSERVATION_TERMS = {
     _OC + "base_heading_proj": _Fused("BASE_HEADING_PROJ", width=1, hook=_target_obs),  # :43-58
     _OC + "base_angle_to_target": _Fused("BASE_ANGLE_TO_TARGET", width=1, hook=_target_obs),  # :61-77
     f"{_LIFT}.observations:object_position_in_robot_root_frame": _Fused("OBJECT_POSITION_IN_ROBOT_ROOT_FRAME", width=3, hook=_object_position),  # :19-31
+    f"{_INHAND}.observations:goal_quat_diff": _Fused("GOAL_QUAT_DIFF", width=4, hook=_goal_quat_diff),  # :20-38
 }
 
 _JOINT_ACTIONS = ("JointPositionAction", "JointVelocityAction", "JointEffortAction", "RelativeJointPositionAction",
@@ -911,6 +1011,7 @@ class PlanCompiler:
         self.robot = robot
         self.entities = SceneEntityResolver(robot, self.cfg.get("scene"))
         self.blob = _Blob()
+        self.state_reads: set[str] = set()
 
     def compile(self) -> Plan:
         self._scalars()
@@ -1400,7 +1501,7 @@ class PlanCompiler:
                     ray_max_distance=self.ray_max, scanner_cfg=scanner, n_ext_rew=self.n_ext_rew, n_ext_term=self.n_ext_term,
                     n_ext_obs=self.n_ext_obs, gravity_dir=tuple(float(x) for x in gdir), mod_state_dim=self.mod_state,
                     term_slots=len(self.term_slots), processed_action_dim=self.processed_dim, ik_terms=self.ik_terms, osc_terms=self.osc_terms,
-                    policy_terms=self.policy_terms)
+                    policy_terms=self.policy_terms, state_reads=tuple(sorted(self.state_reads)))
 
 
 def compile_plan(env_cfg: Any, robot: RobotSpec) -> Plan:

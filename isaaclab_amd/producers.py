@@ -8,6 +8,8 @@
   (isaaclab/envs/mdp/commands/pose_command.py:25-127)
 * :class:`UniformPose2dCommand`, :class:`TerrainBasedPose2dCommand` -- the same two steps for the pose-2d commands of the Navigation
   task (isaaclab/envs/mdp/commands/pose_2d_command.py:26-203)
+* :class:`InHandReOrientationCommand` -- the same two steps for the in-hand re-orientation command of the Repose-Cube task
+  (isaaclab_tasks .../manipulation/inhand/mdp/commands/orientation_command.py:22-124), stand-alone: no env runs it yet
 
 Attribute names follow the reference so that term functions reading ``sensor.data.*`` / ``command_manager`` keep working.
 """
@@ -338,6 +340,105 @@ class TerrainBasedPose2dCommand(UniformPose2dCommand):
         c.valid_targets_d, c.terrain_levels_d, c.terrain_types_d = _lib.ptr(self.valid_targets), _lib.ptr(self.terrain_levels), _lib.ptr(self.terrain_types)
         c.num_levels, c.num_types, c.num_patches = (int(x) for x in self.valid_targets.shape[:3])
         return c
+
+
+class InHandReOrientationCommand:
+    """``InHandReOrientationCommand`` (isaaclab_tasks .../manipulation/inhand/mdp/commands/orientation_command.py:22-124) as a stand-alone
+    producer: ``k_inhand_command`` runs ``CommandTerm.reset`` on a mask and / or ``CommandTerm.compute(dt)`` in one launch.  No env runs
+    it yet (the orchestration launch does not know the term): an env on the in-hand task takes its command from the state feed.
+
+    ``cfg``: dict / object with the fields of ``InHandReOrientationCommandCfg`` (commands_cfg.py:19-71): ``resampling_time_range``,
+    ``init_pos_offset``, ``make_quat_unique``, ``orientation_success_threshold``, ``update_goal_on_success``.  ``env_origins`` (N, 3) is
+    ``scene.env_origins``, ``default_object_pos`` (3 numbers or (N, 3)) ``object.data.default_root_state[:, :3]``; both are fixed at
+    construction, as in the reference (:43-45).
+
+    The ``CommandTerm`` surface of the reference class: ``command`` (N, 7) = ``pos_command_e`` + ``quat_command_w`` (views of it),
+    ``pos_command_w``, ``time_left``, ``command_counter`` and ``metrics`` with ``orientation_error``, ``position_error``,
+    ``consecutive_success`` in the reference's order."""
+
+    def __init__(self, cfg, num_envs: int, step_dt: float, device="cuda:0", seed: int = 0, env_origins=None, default_object_pos=None):
+        get = (lambda k, d=None: cfg.get(k, d)) if isinstance(cfg, dict) else (lambda k, d=None: getattr(cfg, k, d))
+        rt = get("resampling_time_range", (1.0e6, 1.0e6))
+        if not float(rt[1]) > 0.0 or float(rt[0]) > float(rt[1]):
+            raise ValueError(f"InHandReOrientationCommand: resampling_time_range {tuple(rt)} must be ordered and its upper end positive")
+        for key in ("make_quat_unique", "orientation_success_threshold", "update_goal_on_success"):  # (MISSING fields of the configclass)
+            if get(key) is None:
+                raise ValueError(f"InHandReOrientationCommand: the cfg has no '{key}'")
+        if env_origins is None or default_object_pos is None:
+            raise ValueError("InHandReOrientationCommand needs env_origins= and default_object_pos= (both are fixed at construction)")
+        N, dev = num_envs, torch.device(device)
+        self.num_envs, self.device, self.seed, self.step_dt = N, dev, int(seed), float(step_dt)
+        self.make_quat_unique, self.update_goal_on_success = bool(get("make_quat_unique")), bool(get("update_goal_on_success"))
+        self.orientation_success_threshold = float(get("orientation_success_threshold"))
+        self._cfg4 = np.asarray([rt[0], rt[1], self.orientation_success_threshold, 0.0], dtype=np.float32)
+        if tuple(env_origins.shape) != (N, 3):
+            raise ValueError(f"InHandReOrientationCommand: env_origins is {tuple(env_origins.shape)}, expected ({N}, 3)")
+        default = torch.as_tensor(default_object_pos, dtype=torch.float32).to(dev)
+        if tuple(default.shape) not in ((3,), (N, 3)):
+            raise ValueError(f"InHandReOrientationCommand: default_object_pos is {tuple(default.shape)}, expected (3,) or ({N}, 3)")
+        self._command = torch.zeros(N, 7, device=dev)
+        self.pos_command_e, self.quat_command_w = self._command[:, :3], self._command[:, 3:7]
+        self.pos_command_e.copy_(default.expand(N, 3) + torch.tensor(get("init_pos_offset", (0.0, 0.0, 0.0)), dtype=torch.float32, device=dev))
+        self.pos_command_w = (self.pos_command_e + env_origins.to(dev, torch.float32)).contiguous()
+        self.quat_command_w[:, 0] = 1.0
+        self.time_left = torch.zeros(N, device=dev)
+        self.command_counter = torch.zeros(N, dtype=torch.long, device=dev)
+        self.metrics = {k: torch.zeros(N, device=dev) for k in ("orientation_error", "position_error", "consecutive_success")}
+        self.log_part = torch.zeros((N + 63) // 64, 4, device=dev)  # per 64 envs: the reset envs' metric sums before the reset, their count
+        self._step = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._struct = None
+
+    @property
+    def command(self) -> torch.Tensor:
+        return self._command
+
+    def struct(self) -> "_lib.ImxInhandCommand":
+        """The term as ``imx_inhand_command`` takes it (it points at the term's own tensors; the per-call pointers are NULL)."""
+        p = _lib.ptr
+        c = _lib.ImxInhandCommand(make_quat_unique=int(self.make_quat_unique), update_goal_on_success=int(self.update_goal_on_success),
+                                  pos_command_w_d=p(self.pos_command_w), seed=self.seed, step_counter_d=self._step.data_ptr(),
+                                  command_d=p(self._command), time_left_d=p(self.time_left), command_counter_d=p(self.command_counter),
+                                  metric_orientation_error_d=p(self.metrics["orientation_error"]),
+                                  metric_position_error_d=p(self.metrics["position_error"]),
+                                  metric_consecutive_success_d=p(self.metrics["consecutive_success"]), log_part_d=p(self.log_part))
+        for k, v in enumerate(self._cfg4):
+            c.cfg[k] = float(v)
+        return c
+
+    def _launch(self, dt, do_compute, reset_mask, uniforms, object_root_pos_w, object_root_quat_w):
+        N = self.num_envs
+        for name, t, shape in (("object_root_pos_w", object_root_pos_w, (N, 3)), ("object_root_quat_w", object_root_quat_w, (N, 4))):
+            if t is None and not do_compute:
+                continue
+            if t is None or tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != self.device:
+                raise ValueError(f"InHandReOrientationCommand: {name} must be {shape} float32 on {self.device}")
+        if reset_mask is not None and (reset_mask.numel() != N or reset_mask.element_size() != 1 or reset_mask.device != self.device):
+            raise ValueError(f"InHandReOrientationCommand: reset_mask must hold {N} one-byte entries on {self.device}")
+        if uniforms is not None and (tuple(uniforms.shape) != (3, N, 3) or uniforms.dtype != torch.float32 or uniforms.device != self.device):
+            raise ValueError(f"InHandReOrientationCommand: uniforms must be (3, {N}, 3) float32 on {self.device}")
+        self._step += 1
+        if self._struct is None:  # (the term's own tensors never move: built once, the per-call pointers re-pointed)
+            self._struct = self.struct()
+        c = self._struct
+        c.object_root_pos_w_d, c.object_root_quat_w_d = _lib.ptr(object_root_pos_w), _lib.ptr(object_root_quat_w)
+        c.reset_mask_d, c.uniforms_d = _lib.ptr(reset_mask), _lib.ptr(uniforms)
+        check(lib().imx_inhand_command(ctypes.byref(c), N, float(dt), int(bool(do_compute)), _lib.current_stream(self.device)))
+
+    def reset(self, env_ids=None, uniforms=None, object_root_pos_w=None, object_root_quat_w=None) -> dict:
+        """``CommandTerm.reset(env_ids)`` (command_manager.py:120-149): returns the metrics' means over ``env_ids`` as they stood."""
+        ids = slice(None) if env_ids is None else env_ids
+        log = {k: float(torch.mean(v[ids])) for k, v in self.metrics.items()}
+        mask = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)
+        mask[ids] = True
+        self._launch(0.0, False, mask, uniforms, object_root_pos_w, object_root_quat_w)
+        return log
+
+    def compute(self, dt: float, object_root_pos_w, object_root_quat_w, reset_mask=None, uniforms=None):
+        """``reset(ids of reset_mask)`` then ``CommandTerm.compute(dt)`` in ONE launch on the object's root pose; ``uniforms``: optional
+        (3, N, 3) parity samples in [0, 1) -- {time_left, rand_floats[:, 0], rand_floats[:, 1]} of the reset's, the timer's and the
+        reached goal's resampling."""
+        self._launch(dt, True, reset_mask, uniforms, object_root_pos_w, object_root_quat_w)
+        return self._command
 
 
 class ArticulationRootState:

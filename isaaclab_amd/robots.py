@@ -4,7 +4,7 @@ The reference obtains joint/body names and default joint positions from PhysX af
 (``Articulation._initialize_impl``); neither PhysX nor the USD files exist here, so the *names* ship as data.
 Defaults follow the asset cfgs (reference ``source/isaaclab_assets/isaaclab_assets/robots/anymal.py:112-121``,
 ``unitree.py:290-307`` (G1), ``spot.py:151-160``, ``cartpole.py``, ``ant.py:33-42``, the humanoid task's init state, ``franka.py:39-47``,
-``universal_robots.py:35-41``).  The G1, Spot, Ant, Humanoid, Franka and UR10 joint / body orders are synthetic
+``universal_robots.py:35-41``, ``allegro.py:50-58``).  The G1, Spot, Ant, Humanoid, Franka and UR10 joint / body orders are synthetic
 breadth-first orders of the names the task cfgs' regexes refer to (the true PhysX order is not recoverable offline); term
 semantics do not depend on them because every index list is resolved by name through :func:`resolve_matching_names`.
 """
@@ -79,6 +79,7 @@ class RobotSpec:
     joint_vel_limit: float = 100.0
     command_dim: int = 3  # width of the command the state feed serves: 3 = base velocity (vx, vy, wz), 7 = end-effector pose
     fixed_base: bool = False  # Articulation.is_fixed_base: PhysX then computes no Jacobian row for the root body and no root columns
+    object_offset: tuple | None = None  # where the scene's rigid object lies relative to the root in the state feed; None = the Lift task's place
 
     @property
     def num_joints(self) -> int:
@@ -291,4 +292,19 @@ UR10 = RobotSpec(
 # ANYmal-C under the navigation task: the same articulation; the state feed serves the (N, 4) pose-2d command (command_dim = 4)
 ANYMAL_C_NAV = dataclasses.replace(ANYMAL_C, name="anymal_c_nav", command_dim=4)
 
-ROBOTS = {r.name: r for r in (ANYMAL_C, G1, CARTPOLE, SPOT, ANT, HUMANOID, FRANKA_PANDA, UR10, ANYMAL_C_NAV)}
+# Allegro hand (isaaclab_assets/robots/allegro.py:50-58): the 16 joints in the order the reference's own tasks list them
+# (isaaclab_tasks/direct/allegro_hand/allegro_hand_env_cfg.py:45-62: the four finger roots, then each finger's chain); a synthetic
+# body list, the root link first.  The feed's command is the in-hand task's (N, 7) goal pose.
+_FINGERS = ("index", "middle", "ring", "thumb")
+ALLEGRO_HAND = RobotSpec(
+    name="allegro_hand",
+    joint_names=[f"{f}_joint_0" for f in _FINGERS] + [f"{f}_joint_{i}" for f in _FINGERS for i in (1, 2, 3)],
+    body_names=["palm_link"] + [f"{f}_link_{i}" for i in (0, 1, 2, 3) for f in _FINGERS],
+    default_joint_pos={"^(?!thumb_joint_0).*": 0.0, "thumb_joint_0": 0.28},
+    default_root_height=0.5,
+    command_dim=7,
+    fixed_base=True,
+    object_offset=(0.0, -0.19, 0.06),  # inhand_env_cfg.py: the cube's init pos (0, -0.19, 0.56) over the hand's (0, 0, 0.5)
+)
+
+ROBOTS = {r.name: r for r in (ANYMAL_C, G1, CARTPOLE, SPOT, ANT, HUMANOID, FRANKA_PANDA, UR10, ANYMAL_C_NAV, ALLEGRO_HAND)}

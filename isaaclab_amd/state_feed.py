@@ -26,6 +26,10 @@ DYNAMIC = (
 # the reach rewards, the lift terms' object): drawn from their own generators so that the tensors above are unchanged by their presence;
 # recorded fixtures carry them only when their cfg needs them
 EXTRA = ("body_lin_acc_w", "command_time_left", "command_counter", "body_pos_w", "link_incoming_joint_force", "body_quat_w", "object_root_pos_w")
+# the rest of the rigid object's root state and the in-hand command's consecutive_success metric (the in-hand terms, the root
+# observations on the object): served on request only (StateFeed.ensure_object_state), from a generator of their own -- a feed that is
+# never asked allocates nothing and no other tensor changes by a bit
+OBJECT_STATE = ("object_root_quat_w", "object_root_lin_vel_w", "object_root_ang_vel_w", "command_consecutive_success")
 # tensors fixed for the lifetime of the scene
 STATIC = ("default_joint_pos", "default_joint_vel", "soft_joint_pos_limits", "soft_joint_vel_limits", "env_origins")
 
@@ -169,13 +173,29 @@ def generate_body_quat(robot: RobotSpec, num_envs: int, gen: torch.Generator) ->
     return (q / q.norm(dim=-1, keepdim=True).clamp_min(1e-12)).contiguous()
 
 
-def generate_object_offset(num_envs: int, gen: torch.Generator) -> torch.Tensor:
+def generate_object_offset(num_envs: int, gen: torch.Generator, mean=None) -> torch.Tensor:
     """Where the scene's rigid object lies relative to the robot root (N, 3): around the Lift task's initial (0.5, 0, 0.055) m
     (lift_env_cfg.py / joint_pos_env_cfg.py), x, y ~ N(0, 0.1) about it, the height uniform in [-0.15, 0.5) m -- below the -0.05 m
-    dropping threshold on a sixth of the envs, below and above the 0.04 m lifting height on the rest."""
+    dropping threshold on a sixth of the envs, below and above the 0.04 m lifting height on the rest.  ``mean`` (a robot's
+    ``object_offset``): N(mean, 0.08) on every axis instead -- for the Allegro hand's (0, -0.19, 0.06) m (inhand_env_cfg.py: the cube
+    0.56 m up, the hand 0.5 m) about one env in six lies beyond the in-hand task's 0.3 m reach."""
+    if mean is not None:
+        return (torch.randn(num_envs, 3, generator=gen) * 0.08 + torch.tensor(mean, dtype=torch.float32)).contiguous()
     xy = torch.randn(num_envs, 2, generator=gen) * 0.1 + torch.tensor([0.5, 0.0])
     z = 0.055 + (torch.rand(num_envs, 1, generator=gen) * 0.65 - 0.205)
     return torch.cat([xy, z], dim=-1).contiguous()
+
+
+def generate_object_state(num_envs: int, gen: torch.Generator) -> dict[str, torch.Tensor]:
+    """The rest of ``RigidObjectData``'s root state and the in-hand command's metric: ``root_quat_w`` (N, 4) uniform unit quaternions w, x, y, z
+    (normalised N(0, 1) 4-vectors: w < 0 on half of them), ``root_lin_vel_w`` ~ N(0, 0.3) m/s, ``root_ang_vel_w`` ~ N(0, 1) rad/s, and
+    ``InHandReOrientationCommand.metrics["consecutive_success"]`` (N), whole numbers 0..59 as float32 (the reference keeps a float tensor):
+    at or past the task's 50 on a sixth of the envs."""
+    q = torch.randn(num_envs, 4, generator=gen)
+    return {"object_root_quat_w": (q / q.norm(dim=-1, keepdim=True).clamp_min(1e-12)).contiguous(),
+            "object_root_lin_vel_w": torch.randn(num_envs, 3, generator=gen) * 0.3,
+            "object_root_ang_vel_w": torch.randn(num_envs, 3, generator=gen),
+            "command_consecutive_success": torch.randint(0, 60, (num_envs,), generator=gen).to(torch.float32)}
 
 
 def generate_jacobians(robot: RobotSpec, num_envs: int, gen: torch.Generator) -> torch.Tensor:
@@ -260,7 +280,7 @@ class StateFeed:
             sn["body_pos_w"] = generate_body_pos(robot, num_envs, gen_p)
             sn["link_incoming_joint_force"] = generate_link_wrench(robot, num_envs, gen_w)
             sn["body_quat_w"] = generate_body_quat(robot, num_envs, gen_q)
-            sn["object_root_pos_w"] = generate_object_offset(num_envs, gen_o)  # (the offset; the root position is added below)
+            sn["object_root_pos_w"] = generate_object_offset(num_envs, gen_o, robot.object_offset)  # (the offset; the root position is added below)
             if robot.command_dim == 7:  # a pose command (the velocity command drawn above is dropped: other tensors keep their draws)
                 sn["command"] = generate_pose_command(num_envs, gen_c)
             elif robot.command_dim == 4:  # the navigation task's pose-2d command, likewise
@@ -309,6 +329,19 @@ class StateFeed:
         for n in DYNAMICS:
             self._stack[n] = torch.stack([sn[n] for sn in snaps], dim=0).to(self.device).contiguous()
 
+    def ensure_object_state(self) -> None:
+        """Serve the :data:`OBJECT_STATE` tensors (:func:`generate_object_state`): built on the first request from a generator of their own
+        seeded off the feed's seed, like the Jacobians.  A recorded feed (``from_tensors``) has them only when its snapshots carried them."""
+        if all(n in self._stack for n in OBJECT_STATE):
+            return
+        seed = getattr(self, "seed", None)
+        if seed is None:
+            raise KeyError(f"this recorded feed carries no {[n for n in OBJECT_STATE if n not in self._stack]}")
+        gen = torch.Generator().manual_seed(seed + 0x0B57)
+        snaps = [generate_object_state(self.num_envs, gen) for _ in range(self.num_snapshots)]
+        for n in OBJECT_STATE:
+            self._stack[n] = torch.stack([sn[n] for sn in snaps], dim=0).to(self.device).contiguous()
+
     @classmethod
     def from_tensors(cls, robot: RobotSpec, snapshots: list[dict[str, torch.Tensor]], device="cpu",
                      gravity_dir=(0.0, 0.0, -1.0)) -> "StateFeed":
@@ -321,7 +354,7 @@ class StateFeed:
         self.history = snapshots[0]["net_forces_w_history"].shape[1]
         self._stack = {
             n: torch.stack([torch.as_tensor(s[n]) for s in snapshots], 0).to(self.device).contiguous()
-            for n in DYNAMIC + EXTRA + ("jacobians",) + DYNAMICS if n in snapshots[0]
+            for n in DYNAMIC + EXTRA + ("jacobians",) + DYNAMICS + OBJECT_STATE if n in snapshots[0]
         }
         self._static = {n: torch.as_tensor(snapshots[0][n]).to(self.device).contiguous() for n in STATIC}
         self.gravity_dir = [float(x) for x in gravity_dir]

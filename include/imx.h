@@ -32,6 +32,15 @@ typedef void* imx_stream_t;         /* hipStream_t */
 #define IMX_HEADER_WORDS 48
 #define IMX_MAX_OBS_GROUPS 4
 #define IMX_REC_WORDS 20
+/* The frame table of a plan whose terms read FrameTransformer frames (the manipulation/cabinet terms): written once into the blob's
+ * list area, referenced by the records that read it (their IMX_R_AUX0 word = its offset).  IMX_FT_HEADER_WORDS words
+ * [J2, B2, number of ee_frame targets, number of cabinet_frame targets] -- J2 / B2 = joints / bodies of the scene's second
+ * articulation, the row widths of imx_articulation_state_t (0 without one) -- then one frame of IMX_FRAME_WORDS words
+ * [body id, asset (0 the robot: imx_state_t.body_pos_w / body_quat_w, 1 the second articulation: imx_articulation_state_t),
+ * offset position x y z (f32), offset rotation w x y z (f32)] for: the ee_frame's source, its targets in cfg order, the
+ * cabinet_frame's source, its targets.  imx_frame_transformer takes frames in the same 9-word form. */
+#define IMX_FRAME_WORDS 9
+#define IMX_FT_HEADER_WORDS 4
 
 enum imx_header_word {
     IMX_H_MAGIC = 0, IMX_H_VERSION, IMX_H_J, IMX_H_B, IMX_H_H, IMX_H_A, IMX_H_D, IMX_H_R, IMX_H_NTERM, IMX_H_NREW,
@@ -200,7 +209,23 @@ enum imx_rew_op {
     IMX_W_TRACK_ORIENTATION_INV_L2,   /* :71-96  1 / (dtheta + p0), p0 = rot_eps */
     IMX_W_SUCCESS_BONUS,              /* :20-44  dtheta <= p0 -> 1 / 0, p0 = the command cfg's orientation_success_threshold (`<=`: the
                                                   command term's own success test is `<`) */
-    IMX_W_TRACK_POS_L2                /* :47-68  ||cmd[:3] - (object_root_pos_w - env_origins)|| */
+    IMX_W_TRACK_POS_L2,               /* :47-68  ||cmd[:3] - (object_root_pos_w - env_origins)|| */
+    /* (op number IMX_W_TRACK_POS_L2 + 1 = 60 is reserved: imx_plan_create keeps refusing it as an unknown reward op)
+       isaaclab_tasks .../manipulation/cabinet/mdp/rewards.py (Isaac-Open-Drawer-Franka-v0).  Every record: aux0 = the plan's frame table
+       (IMX_FT_*).  tcp / lfinger / rfinger = targets 0 / 1 / 2 of the ee_frame, handle = target 0 of the cabinet_frame, each
+       combine_frame_transforms(body pose, offset) (frame_transformer.py:357-363), computed once per env; is_graspable =
+       (rfinger.z < handle.z) & (lfinger.z > handle.z).  A plan with these ops runs k_term_rew_cabinet and holds no classic, reach, lift,
+       navigation or in-hand op */
+    IMX_W_APPROACH_EE_HANDLE = 61,    /* :18-40   r = (1 / (1 + d^2))^2, d = ||handle - tcp||; 2 r where d <= p0 (threshold) */
+    IMX_W_ALIGN_EE_HANDLE,            /* :43-72   0.5 (sign(az) az^2 + sign(ax) ax^2), az = tcp_z . -handle_x, ax = tcp_x . -handle_y (columns of
+                                                  matrix_from_quat, utils/math.py:144-174) */
+    IMX_W_ALIGN_GRASP_AROUND_HANDLE,  /* :75-91   is_graspable -> 1 / 0 (the manager's multiplication turns the bool into a float) */
+    IMX_W_APPROACH_GRIPPER_HANDLE,    /* :94-114  is_graspable * ((p0 - |lfinger.z - handle.z|) + (p0 - |rfinger.z - handle.z|)), p0 = offset */
+    IMX_W_GRASP_HANDLE,               /* :117-135 (d <= p0) * sum_ids(p1 - joint_pos[id]); p0 = threshold, p1 = open_joint_pos, ids = the
+                                                  robot's gripper joints */
+    IMX_W_OPEN_DRAWER_BONUS,          /* :138-146 (is_graspable + 1) * joint_pos[ids[0]]; aux1 = whose joint: 0 the robot, 1 the second
+                                                  articulation (imx_articulation_state_t.joint_pos, row width J2) */
+    IMX_W_MULTI_STAGE_OPEN_DRAWER     /* :149-162 (q > 0.01) 0.5 + (q > 0.2) g + (q > 0.3) g, q = joint_pos[ids[0]] as above, g = is_graspable */
 };
 
 /* observation ops -- envs/mdp/observations.py */
@@ -234,8 +259,19 @@ enum imx_obs_op {
     IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME, /* isaaclab_tasks .../manipulation/lift/mdp/observations.py:19-31  3 columns:
                                    quat_apply(quat_inv(root_quat_w), object_root_pos_w - root_pos_w) (subtract_frame_transforms,
                                    utils/math.py:785-816; quat_inv = normalize(conjugate), :239-248) */
-    IMX_O_GOAL_QUAT_DIFF    /* isaaclab_tasks .../manipulation/inhand/mdp/observations.py:20-38  4 columns:
+    IMX_O_GOAL_QUAT_DIFF,   /* isaaclab_tasks .../manipulation/inhand/mdp/observations.py:20-38  4 columns:
                                    quat_mul(object_root_quat_w, quat_conjugate(cmd[3:7])), CMD == 7; IMX_F_QUAT_UNIQUE when make_quat_unique */
+    /* isaaclab_tasks .../manipulation/cabinet/mdp/observations.py (Isaac-Open-Drawer-Franka-v0); aux0 = the plan's frame table
+       (IMX_FT_*), frames as for the cabinet rewards.  A plan with one of the six ops below runs k_obs_cabinet */
+    IMX_O_REL_EE_DRAWER_DISTANCE, /* :27-32  3 columns: handle - tcp */
+    IMX_O_EE_POS,           /* :43-48  3 columns: tcp - env_origins */
+    IMX_O_EE_QUAT,          /* :51-59  4 columns: the tcp's quaternion; IMX_F_QUAT_UNIQUE when make_quat_unique */
+    IMX_O_FINGERTIPS_POS,   /* :35-40  3 x (ee_frame targets - 1) columns: targets 1.. minus env_origins */
+    /* envs/mdp/observations.py joint_pos_rel :114-121 / joint_vel_rel :150-157 on the scene's second articulation: ids = its joints,
+       p2 (int) = word offset of as many f32 defaults (default_joint_pos / default_joint_vel of those joints, from the asset's
+       init_state), aux0 = the frame table (its first word is the row width J2 of imx_articulation_state_t.joint_pos / joint_vel) */
+    IMX_O_ARTICULATION_JOINT_POS_REL,
+    IMX_O_ARTICULATION_JOINT_VEL_REL
 };
 
 /* action ops.  A record takes the raw columns [OUT, OUT + DIM) of the action and writes the processed columns [PCOL, PCOL + NIDS) of
@@ -523,11 +559,33 @@ typedef struct imx_object_state imx_object_state_t;
 #include "imx_object_state.h" /* the definition of imx_object_state_t */
 int imx_plan_bind_object_state(imx_plan_t* plan, const imx_object_state_t* os);
 
+/* ---- the scene's second articulation (Isaac-Open-Drawer-Franka-v0: the cabinet): imx_articulation_state_t ----------------------
+ * Its joint state and body poses (imx_articulation_state.h, which this header includes), bound to the plan like the object state:
+ * imx_terminations_rewards[_rollout] / imx_observations read the pointers bound at the time of the call; as = NULL unbinds; the
+ * struct is copied.  A launch whose plan reads a tensor that is NULL names it in imx_last_error and launches nothing. */
+typedef struct imx_articulation_state imx_articulation_state_t;
+#include "imx_articulation_state.h" /* the definition of imx_articulation_state_t */
+int imx_plan_bind_articulation_state(imx_plan_t* plan, const imx_articulation_state_t* as);
+
+/* ---- FrameTransformer (sensors/frame_transformer/frame_transformer.py:337-384): imx_frame_transformer -----------------------------
+ * One launch fills the six FrameTransformerData tensors from the body poses of ONE articulation: the source frame and num_targets
+ * target frames, each combine_frame_transforms(body pose, offset) (utils/math.py:750-781: quat_apply, then add; quat_mul), and every
+ * target relative to the source (subtract_frame_transforms :785-816, quat_inv = normalised conjugate).  frames_d: (1 + num_targets) x
+ * IMX_FRAME_WORDS device words, the source first, in the form of the plan's frame table (the asset word is not read: every body id
+ * indexes body_pos_w / body_quat_w (N, num_bodies, 3 | 4)).  Lane = (env, target frame).  Outputs: source_pos_w (N,3), source_quat_w
+ * (N,4), target_pos_w (N,T,3), target_quat_w (N,T,4), target_pos_source (N,T,3), target_quat_source (N,T,4).  frames_h: the same
+ * words on the host, for the range check of the body ids before the launch. */
+int imx_frame_transformer(int64_t N, int num_targets, int num_bodies, const float* body_pos_w_d, const float* body_quat_w_d,
+                          const int32_t* frames_d, const int32_t* frames_h, float* source_pos_w_d, float* source_quat_w_d,
+                          float* target_pos_w_d, float* target_quat_w_d, float* target_pos_source_d, float* target_quat_source_d,
+                          imx_stream_t stream);
+
 /* ---- library ---------------------------------------------------------------------------------------------------- */
 const char* imx_version(void);
 /* sizeof of an ABI struct as this library was compiled (which: 0 imx_state_t, 1 imx_buffers_t, 2 imx_head_loss_t, 3 imx_rollout_slot_t, 4 imx_policy_act_t, 5 imx_orch_t, 6 imx_event_term_t,
  * 7 imx_diff_ik_t, 8 imx_osc_t, 10 imx_orch_manip_t, 11 imx_weight_term_t, 12 imx_pretrained_policy_t,
- * 13 imx_pose2d_command_t, 15 imx_inhand_command_t, 16 imx_object_state_t), 0 for an unknown index (9 and 14 are):
+ * 13 imx_pose2d_command_t, 15 imx_inhand_command_t, 16 imx_object_state_t, 18 imx_articulation_state_t), 0 for an unknown index
+ * (9, 14 and 17 are):
  * a binding checks its own layout against it at load time. */
 size_t imx_struct_size(int which);
 const char* imx_last_error(void);

@@ -177,5 +177,9 @@ try:
     OBJECT_STATE_HEADER = os.path.join(os.path.dirname(HEADER), "imx_object_state.h")
     with open(OBJECT_STATE_HEADER) as _f:
         _, _, OBJECT_STATE_STRUCTS, _ = parse(_f.read(), OBJECT_STATE_HEADER, DEFINES)
+    # imx_articulation_state.h, likewise: imx_articulation_state_t (imx_plan_bind_articulation_state)
+    ARTICULATION_STATE_HEADER = os.path.join(os.path.dirname(HEADER), "imx_articulation_state.h")
+    with open(ARTICULATION_STATE_HEADER) as _f:
+        _, _, ARTICULATION_STATE_STRUCTS, _ = parse(_f.read(), ARTICULATION_STATE_HEADER, DEFINES)
 except OSError as e:
     raise AbiError(f"the ABI header {HEADER} cannot be read ({e}): the whole binding is derived from it") from e

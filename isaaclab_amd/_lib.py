@@ -99,6 +99,12 @@ ImxInhandCommand = type("ImxInhandCommand", (ctypes.Structure,), {"_fields_": [(
 ImxObjectState = type("ImxObjectState", (ctypes.Structure,), {"_fields_": [(field, _abi.ctype(t, _STRUCTS))
                                                                           for field, t in _abi.OBJECT_STATE_STRUCTS["imx_object_state_t"]]})
 OBJECT_STATE_FIELDS = tuple(field for field, _ in ImxObjectState._fields_)
+# (imx_articulation_state.h, the same way)
+ImxArticulationState = type("ImxArticulationState", (ctypes.Structure,), {"_fields_": [(field, _abi.ctype(t, _STRUCTS))
+                                                                                      for field, t in _abi.ARTICULATION_STATE_STRUCTS["imx_articulation_state_t"]]})
+ARTICULATION_STATE_FIELDS = tuple(field for field, _ in ImxArticulationState._fields_)
+FRAME_WORDS = _abi.DEFINES["IMX_FRAME_WORDS"]
+FT_HEADER_WORDS = _abi.DEFINES["IMX_FT_HEADER_WORDS"]
 if set(_STRUCTS) != set(_abi.STRUCTS):
     raise _abi.AbiError(f"{_abi.HEADER}: no class for {sorted(set(_abi.STRUCTS) - set(_STRUCTS))}")
 STATE_FIELDS = tuple(field for field, _ in ImxState._fields_)
@@ -112,7 +118,8 @@ class ImxError(RuntimeError):
 _lib = None
 
 _BY_POINTER = {**_STRUCTS, "imx_pretrained_policy_t": ImxPretrainedPolicy, "imx_pose2d_command_t": ImxPose2dCommand,
-               "imx_inhand_command_t": ImxInhandCommand, "imx_object_state_t": ImxObjectState}  # (a struct of an included header travels as POINTER(class) too)
+               "imx_inhand_command_t": ImxInhandCommand, "imx_object_state_t": ImxObjectState,
+               "imx_articulation_state_t": ImxArticulationState}  # (a struct of an included header travels as POINTER(class) too)
 _SIGNATURES = {name: (_abi.ctype(res, _BY_POINTER, ret=True), [_abi.ctype(t, _BY_POINTER) for t in args])
                for name, (res, args, _) in _abi.FUNCTIONS.items()}
 EXPORTS = tuple(_SIGNATURES)
@@ -140,7 +147,8 @@ def lib():
         fn.restype = res
         fn.argtypes = args
     for which, cls in (*enumerate((ImxState, ImxBuffers, ImxHeadLoss, ImxRolloutSlot, ImxPolicyAct, ImxOrch, ImxEventTerm, ImxDiffIk, ImxOsc)),
-                       (10, ImxOrchManip), (11, ImxWeightTerm), (12, ImxPretrainedPolicy), (13, ImxPose2dCommand), (15, ImxInhandCommand), (16, ImxObjectState)):  # the binding's struct layouts against the library's (indices 9 and 14 are unknown)
+                       (10, ImxOrchManip), (11, ImxWeightTerm), (12, ImxPretrainedPolicy), (13, ImxPose2dCommand), (15, ImxInhandCommand), (16, ImxObjectState),
+                       (18, ImxArticulationState)):  # the binding's struct layouts against the library's (indices 9, 14 and 17 are unknown)
         if int(L.imx_struct_size(which)) != ctypes.sizeof(cls):
             raise ImxError(f"{LIB_PATH}: sizeof({cls.__name__}) is {int(L.imx_struct_size(which))} in the library, {ctypes.sizeof(cls)} in the "
                            "binding -- rebuild with `python -m isaaclab_amd.build`")

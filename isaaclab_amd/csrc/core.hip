@@ -39,6 +39,7 @@ extern "C" size_t imx_struct_size(int which) {
         case 13: return sizeof(imx_pose2d_command_t);
         case 15: return sizeof(imx_inhand_command_t);
         case 16: return sizeof(imx_object_state_t);
+        case 18: return sizeof(imx_articulation_state_t);
         default: return 0;
     }
 }
@@ -62,6 +63,29 @@ static int check_ids(const std::vector<int32_t>& w, int off, int n, int limit, c
     for (int i = 0; i < n; ++i)
         IMX_REQUIRE(w[off + i] >= 0 && w[off + i] < limit, "plan: %s index %d of record %d outside [0,%d)", what,
                     w[off + i], rec, limit);
+    return 0;
+}
+
+// The frame table a manipulation/cabinet record names in its AUX0 word (include/imx.h IMX_FT_*): bounds, counts, every frame's asset word
+// and body id.  A plan holds one table: every record names the same offset.
+static int check_frame_table(const std::vector<int32_t>& w, imx_plan* p, int off, const char* kind, int rec) {
+    if (p->ft_off) {
+        IMX_REQUIRE(off == p->ft_off, "plan: %s record %d names the frame table at word %d, an earlier record the one at %d", kind, rec, off, p->ft_off);
+        return 0;
+    }
+    IMX_REQUIRE(off >= IMX_HEADER_WORDS && (size_t)off + IMX_FT_HEADER_WORDS <= w.size(), "plan: %s record %d: frame table out of range (off=%d)", kind, rec, off);
+    const int J2 = w[off], B2 = w[off + 1], n_ee = w[off + 2], n_cab = w[off + 3];
+    IMX_REQUIRE(J2 >= 0 && J2 <= 4096 && B2 >= 0 && B2 <= 4096, "plan: frame table: bad second-articulation widths J2=%d B2=%d", J2, B2);
+    IMX_REQUIRE(n_ee >= 0 && n_ee <= 64 && n_cab >= 0 && n_cab <= 64, "plan: frame table: bad target counts %d / %d", n_ee, n_cab);
+    const int frames = 2 + n_ee + n_cab;
+    IMX_REQUIRE((size_t)off + IMX_FT_HEADER_WORDS + (size_t)frames * IMX_FRAME_WORDS <= w.size(), "plan: frame table: %d frames out of range", frames);
+    for (int f = 0; f < frames; ++f) {
+        const int32_t* fr = &w[off + IMX_FT_HEADER_WORDS + f * IMX_FRAME_WORDS];
+        IMX_REQUIRE(fr[1] == 0 || fr[1] == 1, "plan: frame table: frame %d: asset word %d (0 robot, 1 second articulation)", f, fr[1]);
+        const int limit = fr[1] ? B2 : p->NB;
+        IMX_REQUIRE(fr[0] >= 0 && fr[0] < limit, "plan: frame table: frame %d sits on body %d outside [0,%d)", f, fr[0], limit);
+    }
+    p->ft_off = off; p->J2 = J2; p->B2 = B2; p->ft_n_ee = n_ee; p->ft_n_cab = n_cab;
     return 0;
 }
 
@@ -127,7 +151,9 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
     for (int k = 0; k < p->nrew; ++k) {
         const int32_t* r = &w[p->rew_off + k * IMX_REC_WORDS];
         const int op = r[IMX_R_OP];
-        IMX_REQUIRE(op >= IMX_W_IS_ALIVE && op <= IMX_W_TRACK_POS_L2, "plan: unknown reward op %d", op);
+        // (IMX_W_TRACK_POS_L2 + 1 is reserved and stays refused; the manipulation/cabinet ops start one later)
+        IMX_REQUIRE((op >= IMX_W_IS_ALIVE && op <= IMX_W_TRACK_POS_L2) || (op >= IMX_W_APPROACH_EE_HANDLE && op <= IMX_W_MULTI_STAGE_OPEN_DRAWER),
+                    "plan: unknown reward op %d", op);
         IMX_REQUIRE(r[IMX_R_OUT] == k, "plan: reward record %d has index %d", k, r[IMX_R_OUT]);
         int limit = p->J;
         const char* what = "joint";
@@ -143,6 +169,18 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
                    op == IMX_W_POSITION_COMMAND_ERROR_TANH || op == IMX_W_ORIENTATION_COMMAND_ERROR || op == IMX_W_OBJECT_EE_DISTANCE) {
             limit = p->NB;
             what = "asset body";
+        }
+        if (op >= IMX_W_APPROACH_EE_HANDLE) {  // manipulation/cabinet: the frame table first (it holds J2), then the id list
+            if (check_frame_table(w, p, r[IMX_R_AUX0], "reward", k)) return 1;
+            IMX_REQUIRE(p->ft_n_ee >= 1 && p->ft_n_cab >= 1, "plan: reward record %d (op %d) needs a target frame of each sensor (%d / %d)", k, op,
+                        p->ft_n_ee, p->ft_n_cab);
+            if (op == IMX_W_ALIGN_GRASP_AROUND_HANDLE || op == IMX_W_APPROACH_GRIPPER_HANDLE || op >= IMX_W_OPEN_DRAWER_BONUS)
+                IMX_REQUIRE(p->ft_n_ee >= 3, "plan: reward record %d (op %d) reads the two fingertip frames: the ee_frame has %d targets", k, op, p->ft_n_ee);
+            if (op >= IMX_W_OPEN_DRAWER_BONUS) {
+                IMX_REQUIRE(r[IMX_R_AUX1] == 0 || r[IMX_R_AUX1] == 1, "plan: reward record %d: asset selector %d (0 robot, 1 second articulation)", k, r[IMX_R_AUX1]);
+                IMX_REQUIRE(r[IMX_R_NIDS] >= 1, "plan: reward record %d (op %d) needs the drawer joint", k, op);
+                if (r[IMX_R_AUX1]) { limit = p->J2; what = "second-articulation joint"; }
+            }
         }
         if (check_ids(w, r[IMX_R_IDS_OFF], r[IMX_R_NIDS], limit, what, k)) return 1;
         if (op == IMX_W_AIR_TIME_REWARD || op == IMX_W_GAIT_REWARD)
@@ -191,7 +229,7 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
     for (int k = 0; k < p->nobs; ++k) {
         const int32_t* r = &w[p->obs_off + k * IMX_REC_WORDS];
         const int op = r[IMX_R_OP];
-        IMX_REQUIRE(op >= IMX_O_BASE_POS_Z && op <= IMX_O_GOAL_QUAT_DIFF, "plan: unknown observation op %d", op);
+        IMX_REQUIRE(op >= IMX_O_BASE_POS_Z && op <= IMX_O_ARTICULATION_JOINT_VEL_REL, "plan: unknown observation op %d", op);
         const int g = r[IMX_R_WEIGHT];
         IMX_REQUIRE(g >= 0 && g < p->ngroups, "plan: observation record %d names group %d", k, g);
         {
@@ -234,6 +272,21 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
             IMX_REQUIRE(d == 1, "plan: observation op %d must have dim 1", op);
         if (op == IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME) IMX_REQUIRE(d == 3, "plan: object_position_in_robot_root_frame must have dim 3");
         if (op == IMX_O_GOAL_QUAT_DIFF) IMX_REQUIRE(d == 4 && p->CMD == 7, "plan: goal_quat_diff must have dim 4 and a 7-wide pose command (CMD=%d)", p->CMD);
+        if (op >= IMX_O_REL_EE_DRAWER_DISTANCE && op <= IMX_O_ARTICULATION_JOINT_VEL_REL) {  // manipulation/cabinet and the second articulation
+            if (check_frame_table(w, p, r[IMX_R_AUX0], "observation", k)) return 1;
+            if (op == IMX_O_REL_EE_DRAWER_DISTANCE)
+                IMX_REQUIRE(d == 3 && p->ft_n_ee >= 1 && p->ft_n_cab >= 1, "plan: rel_ee_drawer_distance must have dim 3 and a target frame of each sensor");
+            if (op == IMX_O_EE_POS) IMX_REQUIRE(d == 3 && p->ft_n_ee >= 1, "plan: ee_pos must have dim 3 and an ee_frame target");
+            if (op == IMX_O_EE_QUAT) IMX_REQUIRE(d == 4 && p->ft_n_ee >= 1, "plan: ee_quat must have dim 4 and an ee_frame target");
+            if (op == IMX_O_FINGERTIPS_POS)
+                IMX_REQUIRE(p->ft_n_ee >= 2 && d == 3 * (p->ft_n_ee - 1), "plan: fingertips_pos dim %d != 3 x (%d ee_frame targets - 1)", d, p->ft_n_ee);
+            if (op >= IMX_O_ARTICULATION_JOINT_POS_REL) {
+                IMX_REQUIRE(r[IMX_R_NIDS] == d, "plan: second-articulation joint observation dim %d != number of joint ids %d", d, r[IMX_R_NIDS]);
+                if (check_ids(w, r[IMX_R_IDS_OFF], r[IMX_R_NIDS], p->J2, "second-articulation joint", k)) return 1;
+                IMX_REQUIRE(r[IMX_R_P2] >= IMX_HEADER_WORDS && (size_t)r[IMX_R_P2] + (size_t)d <= nwords,
+                            "plan: observation record %d: default table out of range", k);
+            }
+        }
         if (op >= IMX_O_ROOT_POS_W && op <= IMX_O_ROOT_ANG_VEL_W)
             IMX_REQUIRE(r[IMX_R_AUX0] == 0 || r[IMX_R_AUX0] == 1, "plan: observation record %d: asset selector %d (0 robot, 1 object)", k, r[IMX_R_AUX0]);
         if (op == IMX_O_LAST_ACTION) IMX_REQUIRE(d == p->A, "plan: last_action dim %d != A=%d", d, p->A);
@@ -355,6 +408,10 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
         if (op == IMX_O_EXTERNAL) x[10] = w[ro + IMX_R_AUX0];
         if (op >= IMX_O_ROOT_POS_W && op <= IMX_O_ROOT_ANG_VEL_W) x[10] = w[ro + IMX_R_AUX0];  // the asset: 0 robot, 1 object
         if (op == IMX_O_BODY_INCOMING_WRENCH) x[10] = w[(size_t)w[ro + IMX_R_IDS_OFF] + j / 6] * 6 + j % 6;  // body * 6 + component
+        if (op >= IMX_O_REL_EE_DRAWER_DISTANCE && op <= IMX_O_FINGERTIPS_POS) x[10] = w[ro + IMX_R_AUX0];  // the frame table
+        if (op >= IMX_O_ARTICULATION_JOINT_POS_REL) {  // joint id in XC_AUX, its default in XC_RX, the row width J2 in XC_RY
+            x[10] = w[(size_t)w[ro + IMX_R_IDS_OFF] + j]; x[11] = w[(size_t)w[ro + IMX_R_P2] + j]; x[12] = p->J2;
+        }
         if (op == IMX_O_BASE_HEADING_PROJ || op == IMX_O_BASE_ANGLE_TO_TARGET) {  // target_pos: x in XC_P0, y, z in XC_RX, XC_RY
             x[11] = w[ro + IMX_R_P1]; x[12] = w[ro + IMX_R_P2];
         }
@@ -424,7 +481,8 @@ extern "C" int imx_plan_update(imx_plan_t* plan, const int32_t* blob, size_t nwo
     IMX_REQUIRE(q.host.size() == plan->host.size() && q.J == plan->J && q.B == plan->B && q.H == plan->H && q.A == plan->A && q.PA == plan->PA &&
                     q.D == plan->D && q.R == plan->R && q.NB == plan->NB && q.nterm == plan->nterm && q.nrew_all == plan->nrew_all &&
                     q.nobs == plan->nobs && q.DC == plan->DC && q.DX == plan->DX && q.MS == plan->MS && q.ngroups == plan->ngroups &&
-                    q.scan_stateful == plan->scan_stateful && q.term_slots == plan->term_slots,
+                    q.scan_stateful == plan->scan_stateful && q.term_slots == plan->term_slots && q.ft_off == plan->ft_off &&
+                    q.J2 == plan->J2 && q.B2 == plan->B2 && q.ft_n_ee == plan->ft_n_ee && q.ft_n_cab == plan->ft_n_cab,
                 "imx_plan_update: the new plan has a different shape (terms, widths or table sizes changed): create a new plan");
     for (int g = 0; g < q.ngroups; ++g) IMX_REQUIRE(q.gD[g] == plan->gD[g], "imx_plan_update: observation group %d changed width", g);
     int32_t* dev = plan->dev;
@@ -438,6 +496,12 @@ extern "C" int imx_plan_update(imx_plan_t* plan, const int32_t* blob, size_t nwo
 extern "C" int imx_plan_bind_object_state(imx_plan_t* plan, const imx_object_state_t* os) {
     IMX_REQUIRE(plan, "imx_plan_bind_object_state: null plan");
     plan->object_state = os ? *os : imx_object_state_t{};
+    return 0;
+}
+
+extern "C" int imx_plan_bind_articulation_state(imx_plan_t* plan, const imx_articulation_state_t* as) {
+    IMX_REQUIRE(plan, "imx_plan_bind_articulation_state: null plan");
+    plan->articulation_state = as ? *as : imx_articulation_state_t{};
     return 0;
 }
 

@@ -55,6 +55,10 @@ struct imx_plan {
     bool needs_mesh = false;
     int term_slots = 0;           // rows of imx_buffers.term_state (stateful reward terms)
     int PA = 0;                   // row width of imx_buffers.processed_action (IMX_H_PA, or A)
+    // the frame table of the manipulation/cabinet ops (include/imx.h IMX_FT_*): its word offset (0 = the plan has none), the second
+    // articulation's joint / body counts and the target-frame counts of the two sensors, as validated by parse_plan
+    int ft_off = 0, J2 = 0, B2 = 0, ft_n_ee = 0, ft_n_cab = 0;
+    imx_articulation_state_t articulation_state{};  // what imx_plan_bind_articulation_state bound (host side; all NULL = nothing bound)
 };
 
 // view passed by value to kernels

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "imx_internal.h"
+#include "imx_frame_transformer.h"
 
 // torch.clamp / Tensor.clip of an observation: NaN stays NaN (fminf / fmaxf alone return the bound).  A height-scan ray that misses
 // (+inf hit) through a DigitalFilter gives -inf - -inf = NaN, and the reference's observation is NaN, not the clip bound.
@@ -165,6 +166,45 @@ IMX_DEV float obs_inhand_value(const PlanView& P, const imx_state_t& S, const im
         if (op == IMX_O_ROOT_ANG_VEL_W) return X.object_root_ang_vel_w[e * 3 + j];
         const float* __restrict__ q = X.object_root_quat_w + e * 4;
         return ((flags & IMX_F_QUAT_UNIQUE) && q[0] < 0.0f) ? -q[j] : q[j];
+    }
+    return obs_plain_value<true>(P, S, Bf, es, e, x);
+}
+
+// ---- manipulation/cabinet (Isaac-Open-Drawer-Franka-v0): FrameTransformer frames out of the plan's frame table (include/imx.h IMX_FT_*)
+// The pose of the frame whose words start at P.w + fo for env e: its body's pose -- of the robot (S) or of the second articulation
+// (X, B2 bodies per env) by the frame's asset word -- combined with its offset (imx_frame_pose, imx_frame_transformer.h).
+IMX_DEV ImxFramePose cabinet_frame_pose(const PlanView& P, const imx_state_t& S, const imx_articulation_state_t& X, int fo, int B2, int64_t e) {
+    const int32_t* __restrict__ fr = P.w + fo;
+    const bool second = fr[1] != 0;
+    const int64_t b = e * (second ? B2 : P.NB) + fr[0];
+    return imx_frame_pose((second ? X.body_pos_w : S.body_pos_w) + b * 3, (second ? X.body_quat_w : S.body_quat_w) + b * 4, fr);
+}
+// word offset of a frame inside the table at ft: the ee_frame's target t, the cabinet_frame's target t (n_ee = the ee_frame's target count)
+IMX_DEV int ft_ee_target(int ft, int t) { return ft + IMX_FT_HEADER_WORDS + (1 + t) * IMX_FRAME_WORDS; }
+IMX_DEV int ft_cabinet_target(int ft, int n_ee, int t) { return ft + IMX_FT_HEADER_WORDS + (2 + n_ee + t) * IMX_FRAME_WORDS; }
+
+// k_obs_cabinet's column value: the four frame observations of manipulation/cabinet/mdp/observations.py (XC_AUX = the frame table) and
+// joint_pos_rel / joint_vel_rel on the second articulation (XC_AUX = the joint, XC_RX = its default, XC_RY = the row width J2); every
+// other column is obs_plain_value's.  One lane per column: a lane derives the frame it reads itself.
+IMX_DEV float obs_cabinet_value(const PlanView& P, const imx_state_t& S, const imx_articulation_state_t& X, const imx_buffers_t& Bf,
+                                const float* __restrict__ es, int64_t e, const XCol& x) {
+    const int op = x.a.y, j = x.a.z, flags = x.a.w, aux = x.c.z;
+    if (op >= IMX_O_ARTICULATION_JOINT_POS_REL)
+        return (op == IMX_O_ARTICULATION_JOINT_POS_REL ? X.joint_pos : X.joint_vel)[e * x.d.x + aux] - f_of(x.c.w);
+    if (op >= IMX_O_REL_EE_DRAWER_DISTANCE) {
+        const int B2 = P.w[aux + 1], n_ee = P.w[aux + 2];
+        const int t = op == IMX_O_FINGERTIPS_POS ? 1 + j / 3 : 0, c = op == IMX_O_FINGERTIPS_POS ? j % 3 : j;
+        const ImxFramePose tp = cabinet_frame_pose(P, S, X, ft_ee_target(aux, t), B2, e);
+        if (op == IMX_O_EE_QUAT) {  // ee_quat :51-59: quat_unique (utils/math.py:448-461: -q where w < 0) when make_quat_unique
+            const float v = c == 0 ? tp.q.x : (c == 1 ? tp.q.y : (c == 2 ? tp.q.z : tp.q.w));
+            return ((flags & IMX_F_QUAT_UNIQUE) && tp.q.x < 0.0f) ? -v : v;
+        }
+        const float pc = c == 0 ? tp.px : (c == 1 ? tp.py : tp.pz);
+        if (op == IMX_O_REL_EE_DRAWER_DISTANCE) {  // :27-32: handle - tcp
+            const ImxFramePose hd = cabinet_frame_pose(P, S, X, ft_cabinet_target(aux, n_ee, 0), B2, e);
+            return (c == 0 ? hd.px : (c == 1 ? hd.py : hd.pz)) - pc;
+        }
+        return pc - S.env_origins[e * 3 + c];  // ee_pos :43-48, fingertips_pos :35-40
     }
     return obs_plain_value<true>(P, S, Bf, es, e, x);
 }

@@ -1,5 +1,6 @@
 // The body of k_obs (step.hip), included once per kernel: in k_obs<GENERAL_RAYS, LEAN> as it always was, and in k_obs_inhand<LEAN>
-// with IMX_OBS_INHAND defined (the root observations on the scene's rigid object, goal_quat_diff: obs_inhand_value).  A textual include like
+// with IMX_OBS_INHAND defined (the root observations on the scene's rigid object, goal_quat_diff: obs_inhand_value), in
+// k_obs_cabinet<LEAN> with IMX_OBS_CABINET (the FrameTransformer frames, the second articulation's joints: obs_cabinet_value).  A textual include like
 // term_rew_body.inc, for the same reason: the kernels of the existing tasks compile to the very instruction streams they had.
     // One workgroup per env.  (A resident grid walking the envs -- sized to what the chip holds at once -- was measured and dropped:
     // the loop costs 13 more VGPRs, i.e. one wave per SIMD less, and three uneven rounds: 35 us against 29.)
@@ -65,8 +66,10 @@
                 nx = tw.c.z;
             }
         } else {
-#ifdef IMX_OBS_INHAND
+#if defined(IMX_OBS_INHAND)
             v = obs_inhand_value(P, S, X, Bf, es, e, x);
+#elif defined(IMX_OBS_CABINET)
+            v = obs_cabinet_value(P, S, X, Bf, es, e, x);
 #else
             v = obs_plain_value<true>(P, S, Bf, es, e, x);
 #endif

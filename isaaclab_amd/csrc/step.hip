@@ -274,6 +274,67 @@ IMX_DEV float inhand_reward(const PlanView& P, const imx_state_t& S, const int32
     return sqrtf((dx * dx + dy * dy) + dz * dz);
 }
 
+// ---- manipulation/cabinet/mdp/rewards.py (Isaac-Open-Drawer-Franka-v0); in phase 2 of k_term_rew_cabinet.  fr = the env's frames
+// in LDS (row k at fr[k * 64]: 0-2 tcp position, 3-6 tcp quaternion, 7-9 handle position, 10-13 handle quaternion, 14-16 / 17-19 left /
+// right fingertip position), computed once per env in phase 1.  J2 = joints of the second articulation (X.joint_pos's row width).
+// x and z columns of matrix_from_quat (utils/math.py:144-174): two_s = 2 / sum(q * q); column 0 = (1 - two_s (j j + k k), two_s (i j + k r),
+// two_s (i k - j r)), column 1 = (two_s (i j - k r), 1 - two_s (i i + k k), two_s (j k + i r)), column 2 = (two_s (i k + j r),
+// two_s (j k - i r), 1 - two_s (i i + j j))
+IMX_DEV void quat_matrix_column(float r, float i, float j, float k, int col, float& x, float& y, float& z) {
+    const float two_s = 2.0f / (((r * r + i * i) + j * j) + k * k);
+    if (col == 0) { x = 1.0f - two_s * (j * j + k * k); y = two_s * (i * j + k * r); z = two_s * (i * k - j * r); }
+    else if (col == 1) { x = two_s * (i * j - k * r); y = 1.0f - two_s * (i * i + k * k); z = two_s * (j * k + i * r); }
+    else { x = two_s * (i * k + j * r); y = two_s * (j * k - i * r); z = 1.0f - two_s * (i * i + j * j); }
+}
+IMX_DEV float cabinet_reward(const PlanView& P, const imx_state_t& S, const imx_articulation_state_t& X, const int32_t* __restrict__ r, int op,
+                             int64_t ec, const float* __restrict__ fr, int J2) {
+    const float p0 = f_of(r[IMX_R_P0]);
+    auto F = [&](int k) { return fr[k * 64]; };
+    // is_graspable (:88, :112): the right fingertip below the handle and the left one above it
+    auto graspable = [&]() { const float hz = F(9); return ((F(19) < hz) && (F(16) > hz)) ? 1.0f : 0.0f; };
+    // the drawer joint's position (:143, :155): asset_cfg.joint_ids[0] of the robot or of the second articulation
+    auto drawer = [&]() {
+        const int j = P.w[r[IMX_R_IDS_OFF]];
+        return r[IMX_R_AUX1] ? X.joint_pos[ec * J2 + j] : S.joint_pos[ec * P.J + j];
+    };
+    switch (op) {
+        case IMX_W_APPROACH_EE_HANDLE: case IMX_W_GRASP_HANDLE: {  // :18-40, :117-135: distance = ||handle - tcp||
+            const float dx = F(7) - F(0), dy = F(8) - F(1), dz = F(9) - F(2);
+            const float d = sqrtf((dx * dx + dy * dy) + dz * dz);
+            if (op == IMX_W_APPROACH_EE_HANDLE) {
+                float rw = 1.0f / (1.0f + d * d);
+                rw = rw * rw;
+                return d <= p0 ? 2.0f * rw : rw;
+            }
+            const float open = f_of(r[IMX_R_P1]);
+            const float s = sum_ids(P.w + r[IMX_R_IDS_OFF], r[IMX_R_NIDS], [&](int j) { return open - S.joint_pos[ec * P.J + j]; });
+            return (d <= p0 ? 1.0f : 0.0f) * s;
+        }
+        case IMX_W_ALIGN_EE_HANDLE: {  // :43-72
+            float hxx, hxy, hxz, hyx, hyy, hyz, exx, exy, exz, ezx, ezy, ezz;
+            quat_matrix_column(F(10), F(11), F(12), F(13), 0, hxx, hxy, hxz);
+            quat_matrix_column(F(10), F(11), F(12), F(13), 1, hyx, hyy, hyz);
+            quat_matrix_column(F(3), F(4), F(5), F(6), 0, exx, exy, exz);
+            quat_matrix_column(F(3), F(4), F(5), F(6), 2, ezx, ezy, ezz);
+            const float az = (ezx * -hxx + ezy * -hxy) + ezz * -hxz;  // bmm(ee_tcp_z, -handle_x)
+            const float ax = (exx * -hyx + exy * -hyy) + exz * -hyz;  // bmm(ee_tcp_x, -handle_y)
+            const float sz = az > 0.0f ? 1.0f : (az < 0.0f ? -1.0f : 0.0f), sx = ax > 0.0f ? 1.0f : (ax < 0.0f ? -1.0f : 0.0f);
+            return 0.5f * (sz * (az * az) + sx * (ax * ax));
+        }
+        case IMX_W_ALIGN_GRASP_AROUND_HANDLE: return graspable();  // :75-91
+        case IMX_W_APPROACH_GRIPPER_HANDLE: {  // :94-114
+            const float hz = F(9);
+            return graspable() * ((p0 - fabsf(F(16) - hz)) + (p0 - fabsf(F(19) - hz)));
+        }
+        case IMX_W_OPEN_DRAWER_BONUS: return (graspable() + 1.0f) * drawer();  // :138-146
+        case IMX_W_MULTI_STAGE_OPEN_DRAWER: {  // :149-162: open_easy + open_medium + open_hard
+            const float q = drawer(), g = graspable();
+            return ((q > 0.01f ? 0.5f : 0.0f) + (q > 0.2f ? g : 0.0f)) + (q > 0.3f ? g : 0.0f);
+        }
+        default: return 0.0f;
+    }
+}
+
 // scratch layout for k_term_rew (4-byte words, nw = number of env groups; sized for the smallest group: ceil(N/16) groups)
 //   [0, nw*KA)               float  per-group partial sums of episode_sums over reset envs
 //   [.., + nw*NT)            int    per-group counts of term_dones over reset envs
@@ -562,6 +623,18 @@ k_term_rew_inhand(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, StepSc
 #undef IMX_TR_INHAND
 }
 
+// CABINET: the Open-Drawer task's seven reward ops (manipulation/cabinet/mdp/rewards.py), in a kernel of their own for the same reason.
+// X = the second articulation's tensors (the cabinet), ft_off = the plan's frame table, fingers: a reward of the plan reads the
+// fingertip frames (the host looks at the ops).  The env's frames are computed once, by the last wave, into 20 more rows of LDS.
+__global__ void __launch_bounds__(64 * IMX_TR_MAX_WAVES)
+k_term_rew_cabinet(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, StepScratch sc, float* __restrict__ frame, int G, int defer_tail,
+                   imx_rollout_slot_t ro, int ft_off, int fingers, imx_articulation_state_t X) {
+    constexpr bool CLASSIC = false, REACH = false;
+#define IMX_TR_CABINET
+#include "term_rew_body.inc"
+#undef IMX_TR_CABINET
+}
+
 // ------------------------------------------------------------------------------------------------- observations
 // One WAVE = one environment (4 envs per 256-thread block).  Every lane first derives the env's root-frame vectors
 // and scanner yaw from the same 13 root-state floats (wave-uniform loads: one transaction, no LDS, no barrier);
@@ -848,6 +921,19 @@ k_obs_inhand(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, MeshView M,
 #undef IMX_OBS_INHAND
 }
 
+// CABINET: a plan whose observations read FrameTransformer frames (manipulation/cabinet/mdp/observations.py) or the second
+// articulation's joints (Isaac-Open-Drawer-Franka-v0) runs the same body in a kernel of its own, like the in-hand plans.
+template <bool LEAN>
+__global__ void __launch_bounds__(256)
+k_obs_cabinet(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, MeshView M, const float* __restrict__ frame,
+              const float* __restrict__ noise_u, uint64_t seed, int corrupt, float* __restrict__ ray_hits_out, StepScratch sc, int tail_G,
+              int tail_parts, imx_articulation_state_t X) {
+    constexpr bool GENERAL_RAYS = true;
+#define IMX_OBS_CABINET
+#include "obs_body.inc"
+#undef IMX_OBS_CABINET
+}
+
 // ------------------------------------------------------------------------------------------------- root frame
 __global__ void k_root_frame(int64_t N, const float* __restrict__ q, const float* __restrict__ lv,
                              const float* __restrict__ av, float gx, float gy, float gz, float* __restrict__ olv,
@@ -910,6 +996,18 @@ int imx_check_action_inputs(const imx_plan_t* plan, const imx_state_t* st, const
         if (flags & (IMX_F_ACT_TO_LIMITS | IMX_F_ACT_EMA)) IMX_REQUIRE(st->soft_joint_pos_limits, "%s: soft_joint_pos_limits missing", who);
         if (flags & IMX_F_ACT_EMA) IMX_REQUIRE(st->joint_pos, "%s: joint_pos missing", who);
     }
+    return 0;
+}
+
+// The body poses frame `index` of the plan's frame table reads (0 = the ee_frame's source, 1.. its targets, then the cabinet_frame's
+// source and targets): the robot's in the state struct or the second articulation's bound to the plan, by the frame's asset word.
+// who = "a term" | "an observation term".
+static int need_frame_inputs(const imx_plan_t* plan, const imx_state_t* st, int index, const char* who) {
+    const int32_t* fr = &plan->host[plan->ft_off + IMX_FT_HEADER_WORDS + index * IMX_FRAME_WORDS];
+    const float* pos = fr[1] ? plan->articulation_state.body_pos_w : st->body_pos_w;
+    const float* quat = fr[1] ? plan->articulation_state.body_quat_w : st->body_quat_w;
+    IMX_REQUIRE(pos, "state tensor '%s' is required by %s but missing", fr[1] ? "articulation_state.body_pos_w" : "body_pos_w", who);
+    IMX_REQUIRE(quat, "state tensor '%s' is required by %s but missing", fr[1] ? "articulation_state.body_quat_w" : "body_quat_w", who);
     return 0;
 }
 
@@ -1036,6 +1134,19 @@ extern "C" int imx_terminations_rewards_rollout(const imx_plan_t* plan, int64_t 
                 break;
             default: break;
         }
+        // manipulation/cabinet: the frames the kernel computes once per env (tcp, handle; the fingertips for the ops that read them),
+        // the gripper joints, the drawer joint
+        const int cop = w[plan->rew_off + k * IMX_REC_WORDS + IMX_R_OP];
+        if (cop >= IMX_W_APPROACH_EE_HANDLE) {
+            if (need_frame_inputs(plan, st, 1, "a term") || need_frame_inputs(plan, st, 2 + plan->ft_n_ee, "a term")) return 1;
+            if (cop == IMX_W_ALIGN_GRASP_AROUND_HANDLE || cop == IMX_W_APPROACH_GRIPPER_HANDLE || cop >= IMX_W_OPEN_DRAWER_BONUS)
+                if (need_frame_inputs(plan, st, 2, "a term") || need_frame_inputs(plan, st, 3, "a term")) return 1;
+            if (cop == IMX_W_GRASP_HANDLE && need(st->joint_pos, "joint_pos")) return 1;
+            if (cop >= IMX_W_OPEN_DRAWER_BONUS) {
+                if (w[plan->rew_off + k * IMX_REC_WORDS + IMX_R_AUX1] ? need(plan->articulation_state.joint_pos, "articulation_state.joint_pos")
+                                                                      : need(st->joint_pos, "joint_pos")) return 1;
+            }
+        }
     }
     if (plan->CMD > 0 && !st->command) IMX_FAIL("command tensor missing");
     IMX_REQUIRE(plan->term_slots == 0 || bf->term_state,
@@ -1053,8 +1164,11 @@ extern "C" int imx_terminations_rewards_rollout(const imx_plan_t* plan, int64_t 
     // with the root position at hand the kernel also leaves the frame table imx_observations needs (flag 4 there skips k_frame)
     float* frame = st->root_pos_w ? reinterpret_cast<float*>(reinterpret_cast<char*>(bf->scratch) + frame_offset_bytes(plan, N)) : nullptr;
     bool classic = false, reach = false, lift = false, nav = false, inhand = false, need_dtheta = false, object_height = false;
+    bool cabinet = false, fingers = false;
     for (int k = 0; k < plan->nrew; ++k) {
         const int op = w[plan->rew_off + k * IMX_REC_WORDS + IMX_R_OP];
+        cabinet = cabinet || op >= IMX_W_APPROACH_EE_HANDLE;
+        fingers = fingers || op == IMX_W_ALIGN_GRASP_AROUND_HANDLE || op == IMX_W_APPROACH_GRIPPER_HANDLE || op >= IMX_W_OPEN_DRAWER_BONUS;
         classic = classic || (op >= IMX_W_UPRIGHT_POSTURE_BONUS && op <= IMX_W_POWER_CONSUMPTION);
         reach = reach || (op >= IMX_W_POSITION_COMMAND_ERROR && op <= IMX_W_OBJECT_GOAL_DISTANCE);
         lift = lift || (op >= IMX_W_OBJECT_IS_LIFTED && op <= IMX_W_OBJECT_GOAL_DISTANCE);
@@ -1074,7 +1188,13 @@ extern "C" int imx_terminations_rewards_rollout(const imx_plan_t* plan, int64_t 
                 "imx_terminations_rewards: a plan with in-hand (manipulation/inhand) ops beside classic/humanoid, reach, lift or navigation ops is not supported");
     IMX_REQUIRE(!(classic && reach), "imx_terminations_rewards: a plan with both classic/humanoid and manipulation/reach or lift ops is not supported");
     IMX_REQUIRE(!(nav && (classic || reach)), "imx_terminations_rewards: a plan with navigation reward ops beside classic/humanoid, reach or lift ops is not supported");
-    if (inhand) {
+    IMX_REQUIRE(!(cabinet && (classic || reach || nav || inhand)),
+                "imx_terminations_rewards: a plan with cabinet (manipulation/cabinet) ops beside classic/humanoid, reach, lift, navigation or in-hand ops is not supported");
+    if (cabinet) {
+        lds += 20 * 64 * 4;  // the env's frames
+        hipLaunchKernelGGL(k_term_rew_cabinet, dim3(grid), dim3(64 * NW), lds, (hipStream_t)stream, imx_plan_view(plan), N, *st, *bf, sc, frame, G,
+                           flags & 1, ro, plan->ft_off, fingers ? 1 : 0, plan->articulation_state);
+    } else if (inhand) {
         lds += 64 * 4;  // the env's orientation error
         hipLaunchKernelGGL(k_term_rew_inhand, dim3(grid), dim3(64 * NW), lds, (hipStream_t)stream, imx_plan_view(plan), N, *st, *bf, sc, frame, G,
                            flags & 1, ro, need_dtheta ? 1 : 0, plan->object_state);
@@ -1128,6 +1248,7 @@ struct ObsKernelChoice {
     bool vertical;     // height-scanner frame yaw-only + vertical direction (the reference cfg): register-lean single-cell ray path
     bool single_wave;  // k_obs_lean: one single-wave workgroup per 64 rays + one for the env's other columns
     bool inhand;       // k_obs_inhand: a root observation on the rigid object (asset word 1) or goal_quat_diff
+    bool cabinet;      // k_obs_cabinet: a FrameTransformer frame observation or a joint observation on the second articulation
     int scan_rec;
 };
 static ObsKernelChoice choose_obs_kernel(const imx_plan_t* plan) {
@@ -1139,6 +1260,7 @@ static ObsKernelChoice choose_obs_kernel(const imx_plan_t* plan) {
     c.vertical = pv.R == 0 || (pv.ray_yaw_only && pv.rdx == 0.0f && pv.rdy == 0.0f && pv.rdz != 0.0f);
     c.scan_rec = -1;
     c.inhand = false;
+    c.cabinet = false;
     bool object_op = false;  // (k_obs_lean is compiled without it)
     for (int k = 0; k < plan->nobs; ++k) {
         if (w[plan->obs_off + k * IMX_REC_WORDS + IMX_R_OP] == IMX_O_HEIGHT_SCAN) c.scan_rec = k;
@@ -1146,8 +1268,9 @@ static ObsKernelChoice choose_obs_kernel(const imx_plan_t* plan) {
         object_op = object_op || op == IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME;
         c.inhand = c.inhand || op == IMX_O_GOAL_QUAT_DIFF ||
                    (op >= IMX_O_ROOT_POS_W && op <= IMX_O_ROOT_ANG_VEL_W && w[plan->obs_off + k * IMX_REC_WORDS + IMX_R_AUX0]);
+        c.cabinet = c.cabinet || op >= IMX_O_REL_EE_DRAWER_DISTANCE;
     }
-    c.single_wave = c.lean && c.scan_rec >= 0 && pv.R > 0 && pv.R <= 64 * 15 && !object_op && !c.inhand;
+    c.single_wave = c.lean && c.scan_rec >= 0 && pv.R > 0 && pv.R <= 64 * 15 && !object_op && !c.inhand && !c.cabinet;
     return c;
 }
 
@@ -1155,6 +1278,7 @@ extern "C" const char* imx_observations_kernel_name(const imx_plan_t* plan) {
     if (!plan) return "";
     const ObsKernelChoice c = choose_obs_kernel(plan);
     if (c.single_wave) return c.vertical ? "k_obs_lean<false>" : "k_obs_lean<true>";
+    if (c.cabinet) return c.lean ? "k_obs_cabinet<true>" : "k_obs_cabinet<false>";
     if (c.inhand) return c.lean ? "k_obs_inhand<true>" : "k_obs_inhand<false>";
     if (c.vertical) return c.lean ? "k_obs<false,true>" : "k_obs<false,false>";
     return c.lean ? "k_obs<true,true>" : "k_obs<true,false>";
@@ -1209,9 +1333,18 @@ extern "C" int imx_observations(const imx_plan_t* plan, int64_t N, const imx_sta
                 p = st->object_root_pos_w; name = "object_root_pos_w";
                 if (p && !st->root_pos_w) { p = nullptr; name = "root_pos_w"; }
                 break;
+            case IMX_O_ARTICULATION_JOINT_POS_REL: p = plan->articulation_state.joint_pos; name = "articulation_state.joint_pos"; break;
+            case IMX_O_ARTICULATION_JOINT_VEL_REL: p = plan->articulation_state.joint_vel; name = "articulation_state.joint_vel"; break;
+            case IMX_O_EE_POS: case IMX_O_FINGERTIPS_POS: p = st->env_origins; name = "env_origins"; break;
             default: break;
         }
         IMX_REQUIRE(p, "state tensor '%s' is required by an observation term but missing", name);
+        if (op >= IMX_O_REL_EE_DRAWER_DISTANCE && op <= IMX_O_FINGERTIPS_POS) {  // the frames the term reads (frame table indices)
+            const int first = op == IMX_O_FINGERTIPS_POS ? 2 : 1, last = op == IMX_O_FINGERTIPS_POS ? plan->ft_n_ee : 1;
+            for (int f = first; f <= last; ++f)
+                if (need_frame_inputs(plan, st, f, "an observation term")) return 1;
+            if (op == IMX_O_REL_EE_DRAWER_DISTANCE && need_frame_inputs(plan, st, 2 + plan->ft_n_ee, "an observation term")) return 1;
+        }
     }
     MeshView mv{};
     if (mesh) mv = mesh->v;
@@ -1265,7 +1398,16 @@ extern "C" int imx_observations(const imx_plan_t* plan, int64_t N, const imx_sta
     } else {
         if (tail) tail_parts = 1 + ((nlog < 16 ? nlog : 16) * 64 + bs - 1) / bs;
         const unsigned grid = (unsigned)N + (unsigned)tail_parts;
-        if (ch.inhand) {
+        IMX_REQUIRE(!(ch.cabinet && ch.inhand), "imx_observations: a plan with cabinet (manipulation/cabinet) observations beside observations on the "
+                                                "scene's rigid object (manipulation/inhand) is not supported");
+        if (ch.cabinet) {
+            if (lean)
+                hipLaunchKernelGGL(k_obs_cabinet<true>, dim3(grid), dim3(bs), lds, (hipStream_t)stream, pv, N, *st, *bf, mv, frame, noise_u_d, seed,
+                                   enable_corruption, ray_hits_out_d, sc, tail_G, tail_parts, plan->articulation_state);
+            else
+                hipLaunchKernelGGL(k_obs_cabinet<false>, dim3(grid), dim3(bs), lds, (hipStream_t)stream, pv, N, *st, *bf, mv, frame, noise_u_d, seed,
+                                   enable_corruption, ray_hits_out_d, sc, tail_G, tail_parts, plan->articulation_state);
+        } else if (ch.inhand) {
             if (lean)
                 hipLaunchKernelGGL(k_obs_inhand<true>, dim3(grid), dim3(bs), lds, (hipStream_t)stream, pv, N, *st, *bf, mv, frame, noise_u_d, seed,
                                    enable_corruption, ray_hits_out_d, sc, tail_G, tail_parts, plan->object_state);

@@ -1,5 +1,5 @@
 // The body of k_term_rew (step.hip), included once per kernel: in k_term_rew<CLASSIC, REACH> as it always was, and with IMX_TR_LIFT
-// defined in k_term_rew_lift, IMX_TR_NAV in k_term_rew_nav, IMX_TR_INHAND in k_term_rew_inhand.  A textual include, not a device function: the kernels of the existing tasks then compile to the very
+// defined in k_term_rew_lift, IMX_TR_NAV in k_term_rew_nav, IMX_TR_INHAND in k_term_rew_inhand, IMX_TR_CABINET in k_term_rew_cabinet.  A textual include, not a device function: the kernels of the existing tasks then compile to the very
 // instruction streams they had (a shared force-inlined body moved their register allocation and cost them 0.4 us per launch).
     extern __shared__ int32_t smem[];
     const int lane = threadIdx.x & 63;
@@ -31,6 +31,27 @@
     if (need_dtheta && wv == NW - 1) {
         const float* __restrict__ gq = S.command + ec * P.CMD + 3;
         s_dth[lane] = quat_error_magnitude(reinterpret_cast<const float4*>(X.object_root_quat_w)[ec], make_float4(gq[0], gq[1], gq[2], gq[3]));
+    }
+#endif
+#ifdef IMX_TR_CABINET
+    // the env's FrameTransformer frames, once for the seven cabinet rewards: the last wave leaves 20 floats per env in LDS before the
+    // barrier that ends phase 1 -- rows 0-2 the tool centre point's position, 3-6 its quaternion, 7-9 the handle's position, 10-13 its
+    // quaternion, 14-16 / 17-19 the left / right fingertip's position (fingers: a reward of the plan reads them); phase 2 reads them
+    float* s_fr = s_val + nrew * 64;
+    if (wv == NW - 1) {
+        const int B2 = W[ft_off + 1], n_ee = W[ft_off + 2];
+        const ImxFramePose tcp = cabinet_frame_pose(P, S, X, ft_ee_target(ft_off, 0), B2, ec);
+        const ImxFramePose hd = cabinet_frame_pose(P, S, X, ft_cabinet_target(ft_off, n_ee, 0), B2, ec);
+        s_fr[0 * 64 + lane] = tcp.px; s_fr[1 * 64 + lane] = tcp.py; s_fr[2 * 64 + lane] = tcp.pz;
+        s_fr[3 * 64 + lane] = tcp.q.x; s_fr[4 * 64 + lane] = tcp.q.y; s_fr[5 * 64 + lane] = tcp.q.z; s_fr[6 * 64 + lane] = tcp.q.w;
+        s_fr[7 * 64 + lane] = hd.px; s_fr[8 * 64 + lane] = hd.py; s_fr[9 * 64 + lane] = hd.pz;
+        s_fr[10 * 64 + lane] = hd.q.x; s_fr[11 * 64 + lane] = hd.q.y; s_fr[12 * 64 + lane] = hd.q.z; s_fr[13 * 64 + lane] = hd.q.w;
+        if (fingers) {
+            const ImxFramePose lf = cabinet_frame_pose(P, S, X, ft_ee_target(ft_off, 1), B2, ec);
+            const ImxFramePose rf = cabinet_frame_pose(P, S, X, ft_ee_target(ft_off, 2), B2, ec);
+            s_fr[14 * 64 + lane] = lf.px; s_fr[15 * 64 + lane] = lf.py; s_fr[16 * 64 + lane] = lf.pz;
+            s_fr[17 * 64 + lane] = rf.px; s_fr[18 * 64 + lane] = rf.py; s_fr[19 * 64 + lane] = rf.pz;
+        }
     }
 #endif
 
@@ -389,6 +410,9 @@
 #endif
 #ifdef IMX_TR_INHAND
             if (op >= IMX_W_TRACK_ORIENTATION_INV_L2) f = inhand_reward(P, S, r, op, live ? e : min(grp * G, N - 1), s_dth[lane]);
+#endif
+#ifdef IMX_TR_CABINET
+            if (op >= IMX_W_APPROACH_EE_HANDLE) f = cabinet_reward(P, S, X, r, op, live ? e : min(grp * G, N - 1), s_fr + lane, W[ft_off]);
 #endif
 #ifdef IMX_TR_LIFT
             if (op >= IMX_W_POSITION_COMMAND_ERROR && op < IMX_W_OBJECT_IS_LIFTED) f = reach_reward(P, S, r, op, live ? e : min(grp * G, N - 1));

@@ -565,12 +565,67 @@ def _looks_like_scene_entity(v) -> bool:
     return isinstance(v, dict) and "name" in v and any(k in v for k in ("joint_names", "body_names", "joint_ids", "body_ids"))
 
 
+class _SecondArticulationData:
+    """``asset.data`` of the scene's second articulation: the feed's ``articulation_*`` tensors under their ``ArticulationData`` names
+    (what the fused ops read), the defaults of its cfg's ``init_state`` and its name tables."""
+
+    def __init__(self, env, spec):
+        self._env, self._spec = env, spec
+        self.joint_names, self.body_names = list(spec.joint_names), list(spec.body_names)
+        dev, N = env.device, env.num_envs
+        self.default_joint_pos = torch.tensor(spec.default_joint_pos, dtype=torch.float32, device=dev).repeat(N, 1)
+        self.default_joint_vel = torch.tensor(spec.default_joint_vel, dtype=torch.float32, device=dev).repeat(N, 1)
+
+    def __getattr__(self, name):
+        if name in ("joint_pos", "joint_vel", "body_pos_w", "body_quat_w"):
+            env = self.__dict__["_env"]
+            try:
+                return env.feed["articulation_" + name]
+            except KeyError:
+                env.feed.ensure_articulation_state(self.__dict__["_spec"], env.plan.frame_tables)  # (a recorded feed without it raises KeyError)
+                return env.feed["articulation_" + name]
+        raise AttributeError(name)
+
+
+class _SecondArticulation(_Entity):
+    def __init__(self, env, spec):
+        super().__init__(env, spec.joint_names, spec.body_names)
+        self.data = _SecondArticulationData(env, spec)
+
+
+class _FrameSensor:
+    """``env.scene[<FrameTransformer>]``: a ``producers.FrameTransformer`` whose ``data`` is refreshed lazily, at most once per env step
+    (``SensorBase.data``, sensor_base.py:148-160) -- on the eager path only: it is no part of a captured rollout."""
+
+    def __init__(self, env, entity):
+        from .producers import FrameTransformer
+
+        self._env = env
+        self._sensor = FrameTransformer(entity, env._entities, env.num_envs, env.device)
+        self._stamp = None
+        self.cfg = env._entities.frames[entity]
+
+    @property
+    def data(self):
+        env = self._env
+        stamp = (env._sim_step_counter, env.feed.index)
+        if stamp != self._stamp:
+            src = env.scene[env._entities.second.name].data if self._sensor.asset == 1 else env.feed
+            bp, bq = (src.body_pos_w, src.body_quat_w) if self._sensor.asset == 1 else (src["body_pos_w"], src["body_quat_w"])
+            self._sensor.update(bp, bq)
+            self._stamp = stamp
+        return self._sensor.data
+
+
 class _Scene:
     def __init__(self, env):
         r = env.plan.robot
         self._e = {"robot": _Entity(env, r.joint_names, r.body_names)}
         self.sensors = {"contact_forces": _Entity(env, [], r.body_names)}
         self._e.update(self.sensors)
+        for name, spec in env._entities.articulations.items():  # the second articulation (the Open-Drawer task's cabinet)
+            self._e[name] = _SecondArticulation(env, spec)
+        self._frame_names = list(env._entities.frames)  # FrameTransformer sensors: built on first access (a scene that is never asked launches nothing)
         self._env = env
         self.num_envs = env.num_envs
 
@@ -579,9 +634,11 @@ class _Scene:
         return self._env.feed["env_origins"]
 
     def keys(self):
-        return list(self._e)
+        return list(self._e) + [k for k in self._frame_names if k not in self._e]
 
     def __getitem__(self, k):
+        if k not in self._e and k in self._frame_names:
+            self._e[k] = self.sensors[k] = _FrameSensor(self._env, k)
         return self._e[k]
 
 
@@ -716,11 +773,25 @@ class ManagerBasedRLEnv:
         if state_feed.num_envs != N or torch.device(state_feed.device) != self.device:
             raise ValueError("state_feed has a different num_envs/device than the env")
         self.feed = state_feed
-        if plan.state_reads:  # the rigid object's further root state / the in-hand command's metric: served on request
+        from .state_feed import ARTICULATION_STATE, OBJECT_STATE
+
+        # (a recorded feed without a tensor the plan reads: the launch checks refuse the step and name the missing tensor)
+        if any(n in OBJECT_STATE for n in plan.state_reads):  # the rigid object's further root state / the in-hand command's metric: served on request
             try:
                 state_feed.ensure_object_state()
-            except KeyError:  # a recorded feed without them: the launch checks refuse the step and name the missing tensor
+            except KeyError:
                 pass
+        if any(n in ARTICULATION_STATE for n in plan.state_reads):  # the second articulation's joint state and body poses, likewise
+            try:
+                state_feed.ensure_articulation_state(self._entities.second, plan.frame_tables)
+            except KeyError:
+                pass
+        if self._entities.second is not None and (events_cfg or own_managers):
+            # reset_scene_to_default writes every articulation's default root and joint state (envs/mdp/events.py:1096-1118): the
+            # orchestration launch's imx_orch_manip_t carries the robot and one rigid object only
+            raise NotImplementedError(f"the scene's second articulation '{self._entities.second.name}' has no place in the reset orchestration "
+                                      "(imx_orch_manip_t carries the robot and one rigid object): events_cfg= / own_managers=True "
+                                      "are not built for this cfg; the plain env steps it on the feed's state")
         self.step_dt = plan.step_dt
         self.physics_dt = float(env_dict["sim"]["dt"])
         self.max_episode_length = plan.max_episode_length
@@ -814,6 +885,9 @@ class ManagerBasedRLEnv:
             **{f"obs_extra{g}": self._obs_groups[g].data_ptr() for g in range(1, len(self._obs_groups))})
         self._state_cache: dict[int, ImxState] = {}
         self._object_state_cache: dict[int, _lib.ImxObjectState] = {}
+        self._articulation_state_cache: dict[int, _lib.ImxArticulationState] = {}
+        self._reads_object = any(n in OBJECT_STATE for n in plan.state_reads)
+        self._reads_articulation = any(n in ARTICULATION_STATE for n in plan.state_reads)
         self._root_cache = None
 
         if self._pp is not None:
@@ -1220,8 +1294,13 @@ class ManagerBasedRLEnv:
             self._state_cache[idx] = st
             # the in-hand task's further tensors travel beside the state struct (imx_object_state_t), per snapshot like it
             self._object_state_cache[idx] = _lib.ImxObjectState(**{n: snap[n].data_ptr() for n in _lib.OBJECT_STATE_FIELDS if n in snap})
-        if self.plan.state_reads:  # bound to the plan for the launches made with this state
+            # ... and the second articulation's (imx_articulation_state_t): feed name "articulation_<field>"
+            self._articulation_state_cache[idx] = _lib.ImxArticulationState(**{n: snap["articulation_" + n].data_ptr() for n in _lib.ARTICULATION_STATE_FIELDS
+                                                                               if "articulation_" + n in snap})
+        if self._reads_object:  # bound to the plan for the launches made with this state
             check(self._lib.imx_plan_bind_object_state(self._plan_h, ctypes.byref(self._object_state_cache[idx])))
+        if self._reads_articulation:
+            check(self._lib.imx_plan_bind_articulation_state(self._plan_h, ctypes.byref(self._articulation_state_cache[idx])))
         return st
 
     def _root_frame(self) -> dict:

@@ -53,6 +53,7 @@ _NAV = "isaaclab_tasks.manager_based.navigation.mdp"  # .rewards, .pre_trained_p
 _INHAND = "isaaclab_tasks.manager_based.manipulation.inhand.mdp"  # .observations, .rewards, .terminations (Isaac-Repose-Cube-Allegro-v0)
 # command = (N, 7): pos_command_e 3 (the ENV frame) + quat_command_w 4 (orientation_command.py:75-78)
 _INHAND_COMMAND = f"{_INHAND}.commands.orientation_command:InHandReOrientationCommand"
+_CABINET = "isaaclab_tasks.manager_based.manipulation.cabinet.mdp"  # .observations, .rewards (Isaac-Open-Drawer-Franka-v0)
 _POSE_2D_COMMANDS = tuple(f"isaaclab.envs.mdp.commands.pose_2d_command:{c}" for c in ("UniformPose2dCommand", "TerrainBasedPose2dCommand"))
 
 
@@ -407,6 +408,11 @@ class Plan:
     # which of the rigid object's further state tensors and of the in-hand command's metrics the terms read (state_feed.OBJECT_STATE
     # names, sorted): the env asks the feed for them (StateFeed.ensure_object_state); a plan that reads none allocates none
     state_reads: tuple = ()
+    # ... and which tensors of the scene's second articulation (state_feed.ARTICULATION_STATE names: "articulation_joint_pos", ...): the
+    # env asks the feed for those with StateFeed.ensure_articulation_state.  frame_tables: the FrameTransformer sensors the fused terms
+    # read, resolved (robots.FrameTable by entity name; None for a sensor the scene lacks), as written to the blob at frame_table_off
+    frame_tables: dict = dataclasses.field(default_factory=dict)
+    frame_table_off: int = 0
 
 
 @dataclasses.dataclass
@@ -545,6 +551,7 @@ class _Fused:
     width: int = 0                 # observations: columns of the term; 0 = one per id, or set by the hook (rec["dim"])
     hook: Callable | None = None   # the irregular rest: hook(c, name, p, rec), c the PlanCompiler
     applies: Callable | None = None  # applies(p) false: the entry is not for these params (the term is Python-evaluated)
+    articulation: bool = False     # an id list may name the scene's second articulation (the hook then says how the record tells)
 
 
 # Closed modules -- Spot's rewards, the classic tasks' observations and rewards, the reach rewards -- have no Python fallback: a function
@@ -552,7 +559,8 @@ class _Fused:
 _CLOSED = {_SPOT: ("reward",), _REACH: ("reward",), **{f"{_CLASSIC}.{m}": ("termination", "reward", "observation") for m in ("observations", "rewards")},
            **{f"{_LIFT}.{m}": ("termination", "reward", "observation") for m in ("observations", "rewards", "terminations")},
            f"{_NAV}.rewards": ("reward",),
-           **{f"{_INHAND}.{m}": ("termination", "reward", "observation") for m in ("observations", "rewards", "terminations")}}
+           **{f"{_INHAND}.{m}": ("termination", "reward", "observation") for m in ("observations", "rewards", "terminations")},
+           **{f"{_CABINET}.{m}": ("termination", "reward", "observation") for m in ("observations", "rewards")}}
 
 
 def _target_pos(kind: str, name: str, p: dict) -> list[float]:
@@ -731,6 +739,87 @@ def _goal_quat_diff(c, name, p, rec):
     _object(c, "observation", name, p, key="asset_cfg")
     _reads(c, "object_root_quat_w")
     _quat_unique(c, name, p, rec)
+
+
+# -- the Open-Drawer task's own terms (isaaclab_tasks .../manipulation/cabinet/mdp: Isaac-Open-Drawer-Franka-v0).  They read two
+#    FrameTransformer sensors by name -- env.scene["ee_frame"]: target 0 = the tool centre point, targets 1, 2 = the left / right
+#    fingertip; env.scene["cabinet_frame"]: target 0 = the drawer handle -- and the scene's second articulation (the cabinet)
+_EE_FRAME, _CABINET_FRAME = "ee_frame", "cabinet_frame"
+_NO_FRAME = [0, 0, _f2w(0.0), _f2w(0.0), _f2w(0.0), _f2w(1.0), _f2w(0.0), _f2w(0.0), _f2w(0.0)]  # the source slot of a sensor the scene does not have
+
+
+def _frame_table(c, kind, name, sensors=()) -> int:
+    """The plan's frame table (include/imx.h ``IMX_FT_*``), written into the blob by the first term that needs it: the row widths J2, B2
+    of the second articulation's tensors, the target counts of the two sensors, then source and targets of each as nine words.  Returns
+    its offset.  ``sensors``: the sensors this term reads -- they must exist in the scene."""
+    if c.ft_off is None:
+        tabs = {s: c.entities.frame_table(s) if s in c.entities.frames else None for s in (_EE_FRAME, _CABINET_FRAME)}
+        second = c.entities.second
+        w = [second.num_joints if second else 0, second.num_bodies if second else 0] + [len(t.targets) if t else 0 for t in tabs.values()]
+        for t in tabs.values():
+            for f in ([t.source] + list(t.targets)) if t else [None]:
+                w += _NO_FRAME if f is None else [f.body_id, f.asset] + [_f2w(f32(x)) for x in (*f.pos, *f.rot)]
+        c.ft_off, c.frame_tables = c.blob.ints(w), tabs
+    for s in sensors:
+        if c.frame_tables[s] is None:
+            raise ValueError(f"{kind} term '{name}': the scene entity '{s}' is not a FrameTransformer of the scene (it has {list(c.entities.frames)})")
+    return c.ft_off
+
+
+def _reads_frames(c, *frames):
+    """The body poses a frame reads: the robot's arrive with every state struct; the second articulation's are asked for by name."""
+    if any(f.asset == 1 for f in frames):
+        _reads(c, "articulation_body_pos_w", "articulation_body_quat_w")
+
+
+def _cabinet_reward(fingers, c, name, p, rec):
+    rec["aux0"] = _frame_table(c, "reward", name, (_EE_FRAME, _CABINET_FRAME))
+    ee, cab = c.frame_tables[_EE_FRAME], c.frame_tables[_CABINET_FRAME]
+    if fingers and len(ee.targets) < 3:
+        raise ValueError(f"reward term '{name}': the function reads the fingertip frames, targets 1 and 2 of '{_EE_FRAME}'; the sensor has "
+                         f"{len(ee.targets)} target frame(s) {ee.target_frame_names}")
+    _reads_frames(c, ee.targets[0], cab.targets[0], *(ee.targets[1:3] if fingers else ()))
+
+
+def _drawer_joint(c, name, p, rec):
+    """``asset_cfg.joint_ids[0]`` of ``env.scene[asset_cfg.name]``: the robot (AUX1 = 0) or the second articulation (AUX1 = 1)."""
+    _cabinet_reward(True, c, name, p, rec)
+    if rec["nids"] < 1:
+        raise ValueError(f"reward term '{name}': asset_cfg selects no joint")
+    if _entity_name(p.get("asset_cfg"), "robot") in c.entities.articulations:
+        rec["aux1"] = 1
+        _reads(c, "articulation_joint_pos")
+
+
+def _cabinet_obs(fn, c, name, p, rec):
+    sensors = (_EE_FRAME, _CABINET_FRAME) if fn == "rel_ee_drawer_distance" else (_EE_FRAME,)
+    rec["aux0"] = _frame_table(c, "observation", name, sensors)
+    ee = c.frame_tables[_EE_FRAME]
+    if fn == "rel_ee_drawer_distance":
+        _reads_frames(c, ee.targets[0], c.frame_tables[_CABINET_FRAME].targets[0])
+    elif fn == "fingertips_pos":  # (N, targets - 1, 3) flattened
+        if len(ee.targets) < 2:
+            raise ValueError(f"observation term '{name}': fingertips_pos reads the target frames after the first; '{_EE_FRAME}' has {len(ee.targets)}")
+        rec["dim"] = 3 * (len(ee.targets) - 1)
+        _reads_frames(c, *ee.targets[1:])
+    else:
+        _reads_frames(c, ee.targets[0])
+        if fn == "ee_quat" and p.get("make_quat_unique", True):  # (the function's default is True, observations.py:51)
+            rec["flags"] |= F_QUAT_UNIQUE
+
+
+def _joint_rel_asset(fn, c, name, p, rec):
+    """``joint_pos_rel`` / ``joint_vel_rel`` with an ``asset_cfg`` that names the second articulation: the op that reads its tensors, the
+    defaults of the selected joints beside the record (P2 = their offset).  On the robot the record stays word for word what it was."""
+    ent = _entity_name(p.get("asset_cfg"), "robot")
+    if ent not in c.entities.articulations:
+        return
+    art = c.entities.articulations[ent]
+    ids = c.entities.ids(p.get("asset_cfg"), "joint")
+    defaults = art.default_joint_pos if fn == "joint_pos_rel" else art.default_joint_vel
+    rec.update(op=O_OPS["ARTICULATION_" + fn.upper()], p2=int(c.blob.floats([f32(defaults[i]) for i in ids])),
+               aux0=_frame_table(c, "observation", name))
+    _reads(c, "articulation_joint_pos" if fn == "joint_pos_rel" else "articulation_joint_vel")
 
 
 _ROOT_OBJECT_READS = {"ROOT_QUAT_W": "object_root_quat_w", "ROOT_LIN_VEL_W": "object_root_lin_vel_w", "ROOT_ANG_VEL_W": "object_root_ang_vel_w"}
@@ -920,6 +1009,17 @@ REWARD_TERMS = {
     f"{_INHAND}.rewards:track_orientation_inv_l2": _Fused("TRACK_ORIENTATION_INV_L2", params=(("rot_eps", 1.0e-3),), hook=_track_orientation),  # :71-96
     f"{_INHAND}.rewards:success_bonus": _Fused("SUCCESS_BONUS", hook=_success_bonus),  # :20-44
     f"{_INHAND}.rewards:track_pos_l2": _Fused("TRACK_POS_L2", hook=_track_pos),  # :47-68
+    f"{_CABINET}.rewards:approach_ee_handle": _Fused("APPROACH_EE_HANDLE", params=("threshold",), hook=functools.partial(_cabinet_reward, False)),  # :18-40
+    f"{_CABINET}.rewards:align_ee_handle": _Fused("ALIGN_EE_HANDLE", hook=functools.partial(_cabinet_reward, False)),  # :43-72
+    f"{_CABINET}.rewards:align_grasp_around_handle": _Fused("ALIGN_GRASP_AROUND_HANDLE", hook=functools.partial(_cabinet_reward, True)),  # :75-91
+    f"{_CABINET}.rewards:approach_gripper_handle": _Fused("APPROACH_GRIPPER_HANDLE", params=(("offset", 0.04),),
+                                                          hook=functools.partial(_cabinet_reward, True)),  # :94-114
+    f"{_CABINET}.rewards:grasp_handle": _Fused("GRASP_HANDLE", _Ids("asset_cfg", "joint", required=True), params=("threshold", "open_joint_pos"),
+                                               hook=functools.partial(_cabinet_reward, False)),  # :117-135
+    f"{_CABINET}.rewards:open_drawer_bonus": _Fused("OPEN_DRAWER_BONUS", _Ids("asset_cfg", "joint", required=True), hook=_drawer_joint,
+                                                    articulation=True),  # :138-146
+    f"{_CABINET}.rewards:multi_stage_open_drawer": _Fused("MULTI_STAGE_OPEN_DRAWER", _Ids("asset_cfg", "joint", required=True), hook=_drawer_joint,
+                                                          articulation=True),  # :149-162
 }
 
 
@@ -988,7 +1088,13 @@ OBSERVATION_TERMS = {
     _OC + "base_angle_to_target": _Fused("BASE_ANGLE_TO_TARGET", width=1, hook=_target_obs),  # :61-77
     f"{_LIFT}.observations:object_position_in_robot_root_frame": _Fused("OBJECT_POSITION_IN_ROBOT_ROOT_FRAME", width=3, hook=_object_position),  # :19-31
     f"{_INHAND}.observations:goal_quat_diff": _Fused("GOAL_QUAT_DIFF", width=4, hook=_goal_quat_diff),  # :20-38
+    # manipulation/cabinet/mdp/observations.py (rel_ee_object_distance :19-24 reads a scene entity "object" the task does not have: no entry)
+    **{f"{_CABINET}.observations:{f}": _Fused(f.upper(), width=w, hook=functools.partial(_cabinet_obs, f))
+       for f, w in (("rel_ee_drawer_distance", 3), ("ee_pos", 3), ("ee_quat", 4), ("fingertips_pos", 0))},
 }
+# joint_pos_rel / joint_vel_rel also run on the scene's second articulation (the cabinet's drawer joint)
+OBSERVATION_TERMS.update({_O + f: _Fused(f.upper(), _JOINTS, hook=functools.partial(_joint_rel_asset, f), articulation=True)
+                          for f in ("joint_pos_rel", "joint_vel_rel")})
 
 _JOINT_ACTIONS = ("JointPositionAction", "JointVelocityAction", "JointEffortAction", "RelativeJointPositionAction",
                   "JointPositionToLimitsAction", "EMAJointPositionToLimitsAction")
@@ -1012,6 +1118,8 @@ class PlanCompiler:
         self.entities = SceneEntityResolver(robot, self.cfg.get("scene"))
         self.blob = _Blob()
         self.state_reads: set[str] = set()
+        self.ft_off: int | None = None  # the frame table (_frame_table): written by the first term that reads a FrameTransformer frame
+        self.frame_tables: dict = {}
 
     def compile(self) -> Plan:
         self._scalars()
@@ -1047,6 +1155,10 @@ class PlanCompiler:
         rec["op"] = ops[e.op]
         for slot, src in (("ids", e.ids), ("ids2", e.ids2)):
             if src is not None:
+                ent = _entity_name(p.get(src.key), src.entity)
+                if ent in self.entities.articulations and not e.articulation:
+                    raise NotImplementedError(f"{kind} term '{name}': '{src.key}' names the scene's second articulation '{ent}'; the fused op "
+                                              f"{e.op} reads the robot's tensors only")
                 ids = self.entities.ids(p[src.key] if src.required else p.get(src.key), src.kind, src.entity)
                 rec.update({f"{slot}_off": self.blob.ints(ids), f"n{slot}": len(ids)})
         if e.hook is not None:
@@ -1501,7 +1613,8 @@ class PlanCompiler:
                     ray_max_distance=self.ray_max, scanner_cfg=scanner, n_ext_rew=self.n_ext_rew, n_ext_term=self.n_ext_term,
                     n_ext_obs=self.n_ext_obs, gravity_dir=tuple(float(x) for x in gdir), mod_state_dim=self.mod_state,
                     term_slots=len(self.term_slots), processed_action_dim=self.processed_dim, ik_terms=self.ik_terms, osc_terms=self.osc_terms,
-                    policy_terms=self.policy_terms, state_reads=tuple(sorted(self.state_reads)))
+                    policy_terms=self.policy_terms, state_reads=tuple(sorted(self.state_reads)), frame_tables=dict(self.frame_tables),
+                    frame_table_off=int(self.ft_off or 0))
 
 
 def compile_plan(env_cfg: Any, robot: RobotSpec) -> Plan:

@@ -10,6 +10,8 @@
   task (isaaclab/envs/mdp/commands/pose_2d_command.py:26-203)
 * :class:`InHandReOrientationCommand` -- the same two steps for the in-hand re-orientation command of the Repose-Cube task
   (isaaclab_tasks .../manipulation/inhand/mdp/commands/orientation_command.py:22-124), stand-alone: no env runs it yet
+* :class:`FrameTransformer` -- the sensor's six data tensors from an articulation's body poses
+  (isaaclab/sensors/frame_transformer/frame_transformer.py:337-384)
 
 Attribute names follow the reference so that term functions reading ``sensor.data.*`` / ``command_manager`` keep working.
 """
@@ -688,3 +690,45 @@ class ActuatorNetMLP:
                                          p(self.effort_limit), p(self.velocity_limit), p(self.computed_effort), p(self.applied_effort),
                                          _lib.current_stream(self._weights.device)))
         return self.applied_effort
+
+
+class FrameTransformer:
+    """``FrameTransformer`` (isaaclab/sensors/frame_transformer/frame_transformer.py:337-384): ``update`` fills the six
+    ``FrameTransformerData`` tensors from the body poses of the articulation its frames sit on, in one launch (``imx_frame_transformer``,
+    lane = (env, target frame)).
+
+    ``cfg``: the scene entity's name in ``resolver`` (a ``robots.SceneEntityResolver`` that knows the sensor), or an already resolved
+    ``robots.FrameTable``.  ``data``: ``source_pos_w`` (N, 3), ``source_quat_w`` (N, 4), ``target_pos_w`` / ``target_pos_source``
+    (N, T, 3), ``target_quat_w`` / ``target_quat_source`` (N, T, 4) and ``target_frame_names``, as ``FrameTransformerData``.  ``asset``: 0
+    = the frames sit on the robot, 1 = on the scene's second articulation (whose ``body_pos_w`` / ``body_quat_w`` ``update`` then takes)."""
+
+    def __init__(self, cfg, resolver, num_envs: int, device="cuda:0"):
+        table = resolver.frame_table(cfg) if isinstance(cfg, str) else cfg
+        N, T, dev = int(num_envs), len(table.targets), torch.device(device)
+        self.table, self.asset, self.num_envs, self.device = table, table.asset, N, dev
+        words = np.zeros((1 + T, _lib.FRAME_WORDS), np.int32)
+        for row, f in zip(words, [table.source] + list(table.targets)):
+            w = f.words()
+            row[:2] = w[:2]
+            row[2:] = np.asarray(w[2:], np.float32).view(np.int32)
+        self._frames_h = np.ascontiguousarray(words)
+        self._frames_d = torch.from_numpy(self._frames_h).to(dev)
+        z = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
+        self.data = types.SimpleNamespace(source_pos_w=z(N, 3), source_quat_w=z(N, 4), target_pos_w=z(N, T, 3), target_quat_w=z(N, T, 4),
+                                          target_pos_source=z(N, T, 3), target_quat_source=z(N, T, 4),
+                                          target_frame_names=list(table.target_frame_names))
+
+    def update(self, body_pos_w: torch.Tensor, body_quat_w: torch.Tensor):
+        """One launch on ``body_pos_w`` (N, B, 3) / ``body_quat_w`` (N, B, 4) of the articulation the frames sit on; returns ``data``."""
+        N, d = self.num_envs, self.data
+        if body_pos_w.dim() != 3 or tuple(body_pos_w.shape) != (N, body_pos_w.shape[1], 3) or tuple(body_quat_w.shape) != (N, body_pos_w.shape[1], 4):
+            raise ValueError(f"FrameTransformer '{self.table.entity}': body_pos_w / body_quat_w must be ({N}, B, 3) / ({N}, B, 4), got "
+                             f"{tuple(body_pos_w.shape)} / {tuple(body_quat_w.shape)}")
+        for t in (body_pos_w, body_quat_w):
+            if t.dtype != torch.float32 or t.device != self.device:
+                raise ValueError(f"FrameTransformer '{self.table.entity}': body poses must be float32 on {self.device}")
+        p = _lib.ptr
+        check(lib().imx_frame_transformer(N, len(self.table.targets), int(body_pos_w.shape[1]), p(body_pos_w), p(body_quat_w), p(self._frames_d),
+                                          self._frames_h.ctypes.data, p(d.source_pos_w), p(d.source_quat_w), p(d.target_pos_w), p(d.target_quat_w),
+                                          p(d.target_pos_source), p(d.target_quat_source), _lib.current_stream(self.device)))
+        return d

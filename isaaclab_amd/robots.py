@@ -15,6 +15,7 @@ import dataclasses
 import math
 import re
 from collections.abc import Sequence
+from typing import NamedTuple
 
 
 def resolve_matching_names(keys, list_of_strings: Sequence[str], preserve_order: bool = False):
@@ -108,19 +109,96 @@ def _is_slice_all(x) -> bool:
     return x is None or x == slice(None) or (isinstance(x, str) and x.replace(" ", "") == "slice(None,None,None)")
 
 
+class Frame(NamedTuple):
+    """One FrameTransformer frame: its name, the asset its body belongs to (0 the robot, 1 the second articulation), the body and its
+    index in that asset, the offset position and rotation (w, x, y, z)."""
+
+    name: str
+    asset: int
+    body: str
+    body_id: int
+    pos: tuple
+    rot: tuple
+
+    def words(self) -> list:
+        """The frame as ``IMX_FRAME_WORDS`` blob entries (include/imx.h): two ints, then seven floats."""
+        return [int(self.body_id), int(self.asset), *(float(x) for x in self.pos), *(float(x) for x in self.rot)]
+
+
+class FrameTable(NamedTuple):
+    """A resolved FrameTransformer: the asset all its frames sit on, the source frame, the target frames in cfg order."""
+
+    entity: str
+    asset: int
+    source: Frame
+    targets: list
+
+    @property
+    def target_frame_names(self) -> list:
+        return [f.name for f in self.targets]
+
+
+@dataclasses.dataclass
+class SecondArticulation:
+    """The scene's articulation beside the robot (the Open-Drawer task's cabinet): what ``Articulation._initialize_impl`` learns from
+    PhysX -- the joint and body names, in the order its tensors are laid out -- and the defaults its cfg's ``init_state`` gives."""
+
+    name: str
+    joint_names: list
+    body_names: list
+    default_joint_pos: list  # one float per joint
+    default_joint_vel: list
+    root_pos: tuple
+    root_rot: tuple  # w, x, y, z
+    prim_path: str | None = None
+
+    @property
+    def num_joints(self) -> int:
+        return len(self.joint_names)
+
+    @property
+    def num_bodies(self) -> int:
+        return len(self.body_names)
+
+    @classmethod
+    def from_scene_entry(cls, name: str, ent: dict) -> "SecondArticulation":
+        jn, bn = ent.get("joint_names"), ent.get("body_names")
+        if not jn or not bn:
+            raise ValueError(f"scene entity '{name}' is an Articulation without 'joint_names' / 'body_names' tables: the reference learns them "
+                             "from PhysX; here they come with the scene entry (a cfg fixture's side file)")
+        init = ent.get("init_state") or {}
+
+        def table(key):  # InitialStateCfg.joint_pos / joint_vel: {regex: value} (articulation.py _process_cfg)
+            out = [0.0] * len(jn)
+            spec = init.get(key) or {}
+            if spec:
+                idx, _, vals = resolve_matching_names_values(spec, list(jn))
+                for i, v in zip(idx, vals):
+                    out[i] = float(v)
+            return out
+
+        return cls(name=name, joint_names=list(jn), body_names=list(bn), default_joint_pos=table("joint_pos"), default_joint_vel=table("joint_vel"),
+                   root_pos=tuple(float(x) for x in init.get("pos", (0.0, 0.0, 0.0))), root_rot=tuple(float(x) for x in init.get("rot", (1.0, 0.0, 0.0, 0.0))),
+                   prim_path=ent.get("prim_path"))
+
+
 class SceneEntityResolver:
     """``SceneEntityCfg.resolve`` (isaaclab/managers/scene_entity_cfg.py:112-250) over a robot's name tables: the joint / body ids a
     ``SceneEntityCfg`` selects.  The term compiler resolves the fused terms' entities with it, the env those of Python-evaluated terms.
 
     ``scene``: the cfg's ``scene`` dict.  Its entries beyond the robot and the two sensors are learnt by ``class_type``: a ``RigidObject`` has
     one body, named after the last component of its ``prim_path``, and no joints (``self.rigid_objects``); a ``FrameTransformer`` is
-    resolved to its first target frame by :meth:`frame` (``self.frames`` holds the cfg entries)."""
+    resolved to its first target frame by :meth:`frame` and to its source and all its targets by :meth:`frame_table` (``self.frames``
+    holds the cfg entries); an ``Articulation`` other than ``robot`` is the scene's second articulation (``self.articulations``,
+    :class:`SecondArticulation`): its name tables come with the scene entry (``joint_names`` / ``body_names``: PhysX provides them in
+    the reference, a cfg fixture's side file here), its defaults from the entry's ``init_state``.  More than one is refused."""
 
     def __init__(self, robot: RobotSpec, scene: dict | None = None):
         self.joint_names = list(robot.joint_names)
         self.body_names = list(robot.body_names)
         self.rigid_objects: dict[str, str] = {}  # entity -> its one body's name
         self.frames: dict[str, dict] = {}
+        self.articulations: dict[str, SecondArticulation] = {}
         for name, ent in (scene or {}).items():
             cls = ent.get("class_type") if isinstance(ent, dict) else None
             cls = cls if isinstance(cls, str) or cls is None else f"{cls.__module__}:{cls.__qualname__}"
@@ -128,14 +206,61 @@ class SceneEntityResolver:
                 self.rigid_objects[name] = str(ent.get("prim_path", name)).rstrip("/").rsplit("/", 1)[-1]
             elif cls and cls.endswith(":FrameTransformer"):
                 self.frames[name] = ent
+            elif cls and cls.endswith(":Articulation") and name != "robot":
+                self.articulations[name] = SecondArticulation.from_scene_entry(name, ent)
+        if len(self.articulations) > 1:
+            raise NotImplementedError(f"the scene has {len(self.articulations)} articulations beside the robot {list(self.articulations)}; the "
+                                      "fused path carries the state of one second articulation")
+
+    @property
+    def second(self) -> "SecondArticulation | None":
+        """The scene's second articulation, or None."""
+        return next(iter(self.articulations.values()), None)
 
     def names(self, entity: str, kind: str) -> list[str]:
         if entity in ("robot", "contact_forces"):
             return self.joint_names if kind == "joint" else self.body_names
         if entity in self.rigid_objects:
             return [] if kind == "joint" else [self.rigid_objects[entity]]
+        if entity in self.articulations:
+            return self.articulations[entity].joint_names if kind == "joint" else self.articulations[entity].body_names
         raise ValueError(f"The scene entity '{entity}' does not exist. Available entities: "
-                         f"{['robot', 'contact_forces', 'height_scanner'] + list(self.rigid_objects) + list(self.frames)}.")
+                         f"{['robot', 'contact_forces', 'height_scanner'] + list(self.rigid_objects) + list(self.frames) + list(self.articulations)}.")
+
+    def frame_table(self, entity: str) -> "FrameTable":
+        """FrameTransformer ``entity`` resolved: its source frame and every target frame in cfg order, each on the body its ``prim_path``
+        ends in (frame_transformer.py:96-254), of the robot (asset word 0) or of the second articulation (asset word 1).  A frame whose
+        body belongs to neither is a ``ValueError`` naming it; a sensor whose frames span both assets is refused: one launch of the
+        sensor's kernel reads the body poses of one articulation."""
+        if entity not in self.frames:
+            raise ValueError(f"The scene entity '{entity}' is not a FrameTransformer of the scene (it has {list(self.frames)}).")
+        cfg = self.frames[entity]
+        second = self.second
+
+        def resolve(label: str, path: str, offset: dict | None) -> Frame:
+            body = str(path).rstrip("/").rsplit("/", 1)[-1]
+            prim = str(second.prim_path).rstrip("/") + "/" if second is not None and second.prim_path else None
+            if second is not None and body in second.body_names and (body not in self.body_names or (prim and str(path).startswith(prim))):
+                asset, bid = 1, second.body_names.index(body)
+            elif body in self.body_names:
+                asset, bid = 0, self.body_names.index(body)
+            else:
+                raise ValueError(f"FrameTransformer '{entity}': frame '{label}' sits on '{body}', which is a body neither of the robot "
+                                 f"({self.body_names}) nor of a second articulation ({second.body_names if second is not None else 'the scene has none'})")
+            off = offset or {}
+            return Frame(label, asset, body, bid, tuple(float(x) for x in off.get("pos", (0.0, 0.0, 0.0))),
+                         tuple(float(x) for x in off.get("rot", (1.0, 0.0, 0.0, 0.0))))
+
+        source = resolve("source", cfg["prim_path"], cfg.get("source_frame_offset"))
+        targets = [resolve(t.get("name") or str(t["prim_path"]).rstrip("/").rsplit("/", 1)[-1], t["prim_path"], t.get("offset"))
+                   for t in (cfg.get("target_frames") or [])]
+        if not targets:
+            raise ValueError(f"FrameTransformer '{entity}' has no target frames")
+        assets = {f.asset for f in [source] + targets}
+        if len(assets) > 1:
+            raise NotImplementedError(f"FrameTransformer '{entity}': its frames sit on bodies of the robot and of '{second.name}' "
+                                      f"({[(f.name, f.body) for f in [source] + targets]}); the sensor's kernel reads the body poses of one articulation")
+        return FrameTable(entity, assets.pop(), source, targets)
 
     def frame(self, entity: str) -> tuple[str, tuple, tuple]:
         """``target_frames[0]`` of FrameTransformer ``entity`` -> (robot body name, offset position, offset rotation w, x, y, z): the
@@ -307,4 +432,8 @@ ALLEGRO_HAND = RobotSpec(
     object_offset=(0.0, -0.19, 0.06),  # inhand_env_cfg.py: the cube's init pos (0, -0.19, 0.56) over the hand's (0, 0, 0.5)
 )
 
-ROBOTS = {r.name: r for r in (ANYMAL_C, G1, CARTPOLE, SPOT, ANT, HUMANOID, FRANKA_PANDA, UR10, ANYMAL_C_NAV, ALLEGRO_HAND)}
+# The Franka of the Open-Drawer task (manipulation/cabinet): the same articulation; the task has no command term, so the state feed
+# serves the 3-wide default command no term reads (command_dim = 3)
+FRANKA_PANDA_CABINET = dataclasses.replace(FRANKA_PANDA, name="franka_panda_cabinet", command_dim=3)
+
+ROBOTS = {r.name: r for r in (ANYMAL_C, G1, CARTPOLE, SPOT, ANT, HUMANOID, FRANKA_PANDA, UR10, ANYMAL_C_NAV, ALLEGRO_HAND, FRANKA_PANDA_CABINET)}

@@ -30,6 +30,10 @@ EXTRA = ("body_lin_acc_w", "command_time_left", "command_counter", "body_pos_w",
 # observations on the object): served on request only (StateFeed.ensure_object_state), from a generator of their own -- a feed that is
 # never asked allocates nothing and no other tensor changes by a bit
 OBJECT_STATE = ("object_root_quat_w", "object_root_lin_vel_w", "object_root_ang_vel_w", "command_consecutive_success")
+# the scene's second articulation (the Open-Drawer task's cabinet): ArticulationData.joint_pos / joint_vel / body_pos_w / body_quat_w of
+# that asset, (N, J2), (N, J2), (N, B2, 3), (N, B2, 4) -- served on request only (StateFeed.ensure_articulation_state), from a generator of
+# their own, like OBJECT_STATE.  The name without the prefix is the field of imx_articulation_state_t
+ARTICULATION_STATE = ("articulation_joint_pos", "articulation_joint_vel", "articulation_body_pos_w", "articulation_body_quat_w")
 # tensors fixed for the lifetime of the scene
 STATIC = ("default_joint_pos", "default_joint_vel", "soft_joint_pos_limits", "soft_joint_vel_limits", "env_origins")
 
@@ -198,6 +202,59 @@ def generate_object_state(num_envs: int, gen: torch.Generator) -> dict[str, torc
             "command_consecutive_success": torch.randint(0, 60, (num_envs,), generator=gen).to(torch.float32)}
 
 
+def _quat_apply(q: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """quat_apply (utils/math.py:546-566) in the dtype given: v + w t + xyz x t, t = 2 xyz x v."""
+    xyz, w = q[..., 1:], q[..., :1]
+    t = torch.linalg.cross(xyz, v) * 2
+    return v + w * t + torch.linalg.cross(xyz, t)
+
+
+def frame_positions(table, body_pos_w: torch.Tensor, body_quat_w: torch.Tensor) -> torch.Tensor:
+    """World positions (N, T, 3), float64, of the target frames of a resolved FrameTransformer (``robots.FrameTable``) on the body
+    poses given: body position + quat_apply(body quaternion, offset position)."""
+    ids = [f.body_id for f in table.targets]
+    off = torch.tensor([f.pos for f in table.targets], dtype=torch.float64, device=body_pos_w.device)
+    return body_pos_w[:, ids].double() + _quat_apply(body_quat_w[:, ids].double(), off.expand(body_pos_w.shape[0], -1, -1))
+
+
+def generate_articulation_state(spec, num_envs: int, gen: torch.Generator, root_pos_w: torch.Tensor, body_pos_w: torch.Tensor,
+                                body_quat_w: torch.Tensor, frame_tables: dict | None = None) -> dict[str, torch.Tensor]:
+    """The second articulation's tensors (``spec``: a ``robots.SecondArticulation``) beside a robot snapshot (CPU tensors): joint
+    positions = the defaults + U(-0.05, 0.45) (a drawer joint then lies on both sides of the Open-Drawer rewards' 0.01 / 0.2 / 0.3 m
+    stages), joint velocities ~ N(0, 0.5), body quaternions uniform on the sphere, body positions = the robot root + the asset's
+    initial root offset + N(0, 0.3) per body.  With ``frame_tables`` (the plan's resolved ``ee_frame`` / ``cabinet_frame``) the body
+    of the cabinet_frame's first target -- the drawer handle -- is placed against the robot's frames in half of the envs, so that every
+    branch of the cabinet rewards occurs at any env count: env e with e mod 4 == 0 has the handle frame within 0.06 m of the tool
+    centre point (both sides of grasp_handle's 0.03 m), e mod 4 == 1 has it 0.05 .. 0.35 m away horizontally (both sides of
+    approach_ee_handle's 0.2 m) at a height between the two fingertips' (graspable where the left fingertip is the upper one)."""
+    N, J2, B2 = num_envs, spec.num_joints, spec.num_bodies
+    f32 = torch.float32
+    jp = torch.tensor(spec.default_joint_pos, dtype=f32).repeat(N, 1) + (torch.rand(N, J2, generator=gen) * 0.5 - 0.05)
+    jv = torch.randn(N, J2, generator=gen) * 0.5
+    q = torch.randn(N, B2, 4, generator=gen)
+    q = (q / q.norm(dim=-1, keepdim=True).clamp_min(1e-12)).contiguous()
+    pos = (root_pos_w + torch.tensor(spec.root_pos, dtype=f32)).unsqueeze(1) + torch.randn(N, B2, 3, generator=gen) * 0.3
+    u = torch.rand(N, 4, generator=gen, dtype=torch.float64)
+    d = torch.nn.functional.normalize(torch.randn(N, 3, generator=gen, dtype=torch.float64), dim=-1)
+    ee, cab = ((frame_tables or {}).get(k) for k in ("ee_frame", "cabinet_frame"))
+    if ee is not None and cab is not None and ee.asset == 0 and cab.asset == 1 and len(ee.targets) >= 3:
+        tips = frame_positions(ee, body_pos_w, body_quat_w)  # tool centre point, left fingertip, right fingertip
+        handle = cab.targets[0]
+        cls = torch.arange(N) % 4
+        near = tips[:, 0] + d * (u[:, 0:1] * 0.06)
+        ang = u[:, 1] * (2.0 * math.pi)
+        rad = 0.05 + 0.3 * u[:, 2]
+        between = torch.stack([tips[:, 0, 0] + rad * torch.cos(ang), tips[:, 0, 1] + rad * torch.sin(ang),
+                               tips[:, 1, 2] + (0.1 + 0.8 * u[:, 3]) * (tips[:, 2, 2] - tips[:, 1, 2])], dim=-1)
+        want = torch.where((cls == 0).unsqueeze(-1), near, between)
+        # the handle body that puts the handle FRAME there: frame = body + quat_apply(body quaternion, offset)
+        body = want - _quat_apply(q[:, handle.body_id].double(), torch.tensor(handle.pos, dtype=torch.float64).expand(N, 3))
+        sel = cls < 2
+        pos[sel, handle.body_id] = body[sel].float()
+    return {"articulation_joint_pos": jp.contiguous(), "articulation_joint_vel": jv.contiguous(), "articulation_body_pos_w": pos.contiguous(),
+            "articulation_body_quat_w": q}
+
+
 def generate_jacobians(robot: RobotSpec, num_envs: int, gen: torch.Generator) -> torch.Tensor:
     """``root_physx_view.get_jacobians()`` (N, NB, 6, ND), world frame: NB = the bodies (without the root body of a fixed base), ND =
     the joints (after six root columns of a floating base).  Linear rows 0-2 ~ U(-0.8, 0.8), angular rows 3-5 ~ U(-1, 1): the size of
@@ -342,6 +399,24 @@ class StateFeed:
         for n in OBJECT_STATE:
             self._stack[n] = torch.stack([sn[n] for sn in snaps], dim=0).to(self.device).contiguous()
 
+    def ensure_articulation_state(self, spec, frame_tables: dict | None = None) -> None:
+        """Serve the :data:`ARTICULATION_STATE` tensors of the scene's second articulation ``spec`` (a ``robots.SecondArticulation``;
+        :func:`generate_articulation_state`): built on the first request from a generator of their own seeded off the feed's seed, like
+        the object state -- no other tensor changes by a bit and a feed that never asks allocates nothing.  ``frame_tables``: the plan's
+        resolved FrameTransformer sensors, against which the drawer handle is placed.  A recorded feed (``from_tensors``) has the
+        tensors only when its snapshots carried them."""
+        if all(n in self._stack for n in ARTICULATION_STATE):
+            return
+        seed = getattr(self, "seed", None)
+        if seed is None:
+            raise KeyError(f"this recorded feed carries no {[n for n in ARTICULATION_STATE if n not in self._stack]}")
+        gen = torch.Generator().manual_seed(seed + 0xCAB1)
+        cpu = lambda n, k: self._stack[n][k].cpu()  # noqa: E731
+        snaps = [generate_articulation_state(spec, self.num_envs, gen, cpu("root_pos_w", k), cpu("body_pos_w", k), cpu("body_quat_w", k), frame_tables)
+                 for k in range(self.num_snapshots)]
+        for n in ARTICULATION_STATE:
+            self._stack[n] = torch.stack([sn[n] for sn in snaps], dim=0).to(self.device).contiguous()
+
     @classmethod
     def from_tensors(cls, robot: RobotSpec, snapshots: list[dict[str, torch.Tensor]], device="cpu",
                      gravity_dir=(0.0, 0.0, -1.0)) -> "StateFeed":
@@ -354,7 +429,7 @@ class StateFeed:
         self.history = snapshots[0]["net_forces_w_history"].shape[1]
         self._stack = {
             n: torch.stack([torch.as_tensor(s[n]) for s in snapshots], 0).to(self.device).contiguous()
-            for n in DYNAMIC + EXTRA + ("jacobians",) + DYNAMICS + OBJECT_STATE if n in snapshots[0]
+            for n in DYNAMIC + EXTRA + ("jacobians",) + DYNAMICS + OBJECT_STATE + ARTICULATION_STATE if n in snapshots[0]
         }
         self._static = {n: torch.as_tensor(snapshots[0][n]).to(self.device).contiguous() for n in STATIC}
         self.gravity_dir = [float(x) for x in gravity_dir]

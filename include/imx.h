@@ -516,6 +516,18 @@ typedef struct imx_orch_manip imx_orch_manip_t;
 #include "imx_orch_manip.h" /* IMX_ORCH_MAX_WEIGHT_TERMS, imx_weight_term_t and the definition of imx_orch_manip_t */
 int imx_reset_orchestrate_manip(const imx_orch_t* orch, const imx_orch_manip_t* manip, imx_stream_t stream);
 
+/* ---- _reset_idx on a scene with a second articulation (Isaac-Open-Drawer-Franka-v0: the cabinet): imx_reset_orchestrate_scene ---
+ * What imx_reset_orchestrate_manip does, plus the second articulation (imx_orch_articulation.h, which this header includes;
+ * imx_event_term_t.asset = 2): reset_scene_to_default (envs/mdp/events.py:1096-1118) also writes its default root pose (+ env origin),
+ * root velocity and joint state, unclamped; reset_joints_by_offset / reset_joints_by_scale (:987-1049) on it draw 2 * J2 columns keyed
+ * as the robot's are and clamp to ITS soft position limits and +- velocity limits; reset_root_state_uniform (:823-868) on it writes its
+ * root pose and velocity.  All four go to the asset's own out buffers.  The limit tables are required only when a joint event acts on
+ * the asset.  Any other op with asset = 2 is refused, and so is a term with asset = 2 handed to imx_reset_orchestrate[_manip]. */
+typedef struct imx_orch_articulation imx_orch_articulation_t;
+#include "imx_orch_articulation.h" /* the definition of imx_orch_articulation_t */
+int imx_reset_orchestrate_scene(const imx_orch_t* orch, const imx_orch_manip_t* manip, const imx_orch_articulation_t* articulation,
+                                imx_stream_t stream);
+
 /* ---- the pose-2d command term (Isaac-Navigation-Flat-Anymal-C-v0): imx_pose2d_command, imx_reset_orchestrate_pose2d -------------
  * UniformPose2dCommand (isaaclab/envs/mdp/commands/pose_2d_command.py:26-143) and TerrainBasedPose2dCommand (:146-203) under
  * CommandTerm.reset / compute (isaaclab/managers/command_manager.py:120-187), one lane per env (pose2d_command_env).  The term travels
@@ -584,8 +596,9 @@ int imx_frame_transformer(int64_t N, int num_targets, int num_bodies, const floa
 const char* imx_version(void);
 /* sizeof of an ABI struct as this library was compiled (which: 0 imx_state_t, 1 imx_buffers_t, 2 imx_head_loss_t, 3 imx_rollout_slot_t, 4 imx_policy_act_t, 5 imx_orch_t, 6 imx_event_term_t,
  * 7 imx_diff_ik_t, 8 imx_osc_t, 10 imx_orch_manip_t, 11 imx_weight_term_t, 12 imx_pretrained_policy_t,
- * 13 imx_pose2d_command_t, 15 imx_inhand_command_t, 16 imx_object_state_t, 18 imx_articulation_state_t), 0 for an unknown index
- * (9, 14 and 17 are):
+ * 13 imx_pose2d_command_t, 15 imx_inhand_command_t, 16 imx_object_state_t, 18 imx_articulation_state_t,
+ * 20 imx_orch_articulation_t), 0 for an unknown index
+ * (9, 14, 17 and 19 are):
  * a binding checks its own layout against it at load time. */
 size_t imx_struct_size(int which);
 const char* imx_last_error(void);

@@ -181,5 +181,9 @@ try:
     ARTICULATION_STATE_HEADER = os.path.join(os.path.dirname(HEADER), "imx_articulation_state.h")
     with open(ARTICULATION_STATE_HEADER) as _f:
         _, _, ARTICULATION_STATE_STRUCTS, _ = parse(_f.read(), ARTICULATION_STATE_HEADER, DEFINES)
+    # imx_orch_articulation.h, likewise: imx_orch_articulation_t (imx_reset_orchestrate_scene)
+    ORCH_ARTICULATION_HEADER = os.path.join(os.path.dirname(HEADER), "imx_orch_articulation.h")
+    with open(ORCH_ARTICULATION_HEADER) as _f:
+        _, _, ORCH_ARTICULATION_STRUCTS, _ = parse(_f.read(), ORCH_ARTICULATION_HEADER, DEFINES)
 except OSError as e:
     raise AbiError(f"the ABI header {HEADER} cannot be read ({e}): the whole binding is derived from it") from e

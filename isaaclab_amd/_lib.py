@@ -103,6 +103,9 @@ OBJECT_STATE_FIELDS = tuple(field for field, _ in ImxObjectState._fields_)
 ImxArticulationState = type("ImxArticulationState", (ctypes.Structure,), {"_fields_": [(field, _abi.ctype(t, _STRUCTS))
                                                                                       for field, t in _abi.ARTICULATION_STATE_STRUCTS["imx_articulation_state_t"]]})
 ARTICULATION_STATE_FIELDS = tuple(field for field, _ in ImxArticulationState._fields_)
+# (imx_orch_articulation.h, the same way)
+ImxOrchArticulation = type("ImxOrchArticulation", (ctypes.Structure,), {"_fields_": [(field, _abi.ctype(t, _STRUCTS))
+                                                                                    for field, t in _abi.ORCH_ARTICULATION_STRUCTS["imx_orch_articulation_t"]]})
 FRAME_WORDS = _abi.DEFINES["IMX_FRAME_WORDS"]
 FT_HEADER_WORDS = _abi.DEFINES["IMX_FT_HEADER_WORDS"]
 if set(_STRUCTS) != set(_abi.STRUCTS):
@@ -119,7 +122,8 @@ _lib = None
 
 _BY_POINTER = {**_STRUCTS, "imx_pretrained_policy_t": ImxPretrainedPolicy, "imx_pose2d_command_t": ImxPose2dCommand,
                "imx_inhand_command_t": ImxInhandCommand, "imx_object_state_t": ImxObjectState,
-               "imx_articulation_state_t": ImxArticulationState}  # (a struct of an included header travels as POINTER(class) too)
+               "imx_articulation_state_t": ImxArticulationState,
+               "imx_orch_articulation_t": ImxOrchArticulation}  # (a struct of an included header travels as POINTER(class) too)
 _SIGNATURES = {name: (_abi.ctype(res, _BY_POINTER, ret=True), [_abi.ctype(t, _BY_POINTER) for t in args])
                for name, (res, args, _) in _abi.FUNCTIONS.items()}
 EXPORTS = tuple(_SIGNATURES)
@@ -148,7 +152,7 @@ def lib():
         fn.argtypes = args
     for which, cls in (*enumerate((ImxState, ImxBuffers, ImxHeadLoss, ImxRolloutSlot, ImxPolicyAct, ImxOrch, ImxEventTerm, ImxDiffIk, ImxOsc)),
                        (10, ImxOrchManip), (11, ImxWeightTerm), (12, ImxPretrainedPolicy), (13, ImxPose2dCommand), (15, ImxInhandCommand), (16, ImxObjectState),
-                       (18, ImxArticulationState)):  # the binding's struct layouts against the library's (indices 9, 14 and 17 are unknown)
+                       (18, ImxArticulationState), (20, ImxOrchArticulation)):  # the binding's struct layouts against the library's (indices 9, 14, 17 and 19 are unknown)
         if int(L.imx_struct_size(which)) != ctypes.sizeof(cls):
             raise ImxError(f"{LIB_PATH}: sizeof({cls.__name__}) is {int(L.imx_struct_size(which))} in the library, {ctypes.sizeof(cls)} in the "
                            "binding -- rebuild with `python -m isaaclab_amd.build`")

@@ -40,6 +40,7 @@ extern "C" size_t imx_struct_size(int which) {
         case 15: return sizeof(imx_inhand_command_t);
         case 16: return sizeof(imx_object_state_t);
         case 18: return sizeof(imx_articulation_state_t);
+        case 20: return sizeof(imx_orch_articulation_t);
         default: return 0;
     }
 }

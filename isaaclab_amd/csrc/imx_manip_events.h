@@ -27,6 +27,25 @@ IMX_HD void root_pose_uniform_env(const float* d, float ox, float oy, float oz, 
     pose[6] = qq - zz + (z1 + y1) * (w2 - x2);
 }
 
+// reset_joints_by_offset / reset_joints_by_scale (:987-1049) for one joint of one env of the scene's second articulation: up, uv the two
+// samples in [0,1) (columns j and J2 + j), r = {position lo, hi, velocity lo, hi}.  default (+ | *) sample, then clamp_(lo, hi) to the
+// soft position limits and to +- the soft velocity limit -- the arithmetic of the robot's path in orchestrate.hip, term by term
+IMX_HD void joint_reset_env(bool by_offset, float dp, float dv, float up, float uv, const float* r, float plo, float phi, float vlim, float* p,
+                            float* v) {
+    const float sp = up * (r[1] - r[0]) + r[0];
+    const float sv = uv * (r[3] - r[2]) + r[2];
+    const float pp = by_offset ? dp + sp : dp * sp;
+    const float vv = by_offset ? dv + sv : dv * sv;
+    *p = fminf(fmaxf(pp, plo), phi);
+    *v = fminf(fmaxf(vv, -vlim), vlim);
+}
+
+// reset_root_state_uniform's velocity (:857-865) for one env: vel (6) = default[7:] + sample, u6 the six samples in [0,1) (columns
+// 6..11), r the six velocity ranges lo, hi
+IMX_HD void root_vel_uniform_env(const float* d, const float* u6, const float* r, float* vel) {
+    for (int k = 0; k < 6; ++k) vel[k] = d[7 + k] + (u6[k] * (r[2 * k + 1] - r[2 * k]) + r[2 * k]);
+}
+
 // reset_scene_to_default (:1099-1113) for one asset of one env: pose (7) = default[:7] with the env origin added to the position,
 // vel (6) = default[7:]
 IMX_HD void root_state_default_env(const float* d, float ox, float oy, float oz, float* pose, float* vel) {

@@ -37,8 +37,12 @@ __device__ __forceinline__ float wsum(float v) {
 // with imx_orch_manip_t as a second kernel argument; again an instantiation of its own (k_reset_orchestrate_manip below)
 // P2D: the command term is a pose-2d command (imx_reset_orchestrate_pose2d; imx_pose2d_command_t as a second kernel argument, has_command
 // is 0): the third instantiation of its own (k_reset_orchestrate_pose2d below), no terrain curriculum
-template <bool POSE, bool MANIP, bool P2D = false>
-__device__ __forceinline__ void orch_body(const imx_orch_t& o, const imx_orch_manip_t* mp, const imx_pose2d_command_t* pc = nullptr) {
+// ART2: the MANIP launch on a scene with a second articulation (imx_reset_orchestrate_scene; imx_orch_articulation_t as a third kernel
+// argument, imx_event_term_t.asset = 2): the fourth instantiation of its own (k_reset_orchestrate_scene below).  Everything it adds sits
+// behind `if (ART2 ...)`, so the three older kernels keep their instruction streams (DESIGN.md has the resource table)
+template <bool POSE, bool MANIP, bool P2D = false, bool ART2 = false>
+__device__ __forceinline__ void orch_body(const imx_orch_t& o, const imx_orch_manip_t* mp, const imx_pose2d_command_t* pc = nullptr,
+                                          const imx_orch_articulation_t* ap = nullptr) {
     const int lane = threadIdx.x;
     const int64_t N = o.num_envs;
     const int64_t e0 = (int64_t)blockIdx.x * ORCH_BLOCK + lane;
@@ -152,6 +156,8 @@ __device__ __forceinline__ void orch_body(const imx_orch_t& o, const imx_orch_ma
                     root_state_default_env(mp->object_default_root_state_d + e * 13, ox, oy, oz, mp->object_root_pose_out_d + e * 7,
                                            mp->object_root_vel_out_d + e * 6);
                 root_state_default_env(o.default_root_state_d + e * 13, ox, oy, oz, o.root_pose_out_d + e * 7, o.root_vel_out_d + e * 6);
+                if (ART2)
+                    root_state_default_env(ap->default_root_state_d + e * 13, ox, oy, oz, ap->root_pose_out_d + e * 7, ap->root_vel_out_d + e * 6);
             }
             for (uint64_t m = __ballot(valid); m != 0ull; m &= m - 1ull) {  // the default joint state, unclamped: lane = joint
                 const int64_t er = (int64_t)blockIdx.x * ORCH_BLOCK + (__ffsll((long long)m) - 1);  // wave-uniform
@@ -160,6 +166,40 @@ __device__ __forceinline__ void orch_body(const imx_orch_t& o, const imx_orch_ma
                     o.joint_pos_out_d[q] = o.default_joint_pos_d[q];
                     o.joint_vel_out_d[q] = o.default_joint_vel_d[q];
                 }
+                if (ART2) {
+                    const int J2 = (int)ap->num_joints;
+                    for (int j = lane; j < J2; j += ORCH_BLOCK) {
+                        const size_t q = (size_t)er * J2 + j;
+                        ap->joint_pos_out_d[q] = ap->default_joint_pos_d[q];
+                        ap->joint_vel_out_d[q] = ap->default_joint_vel_d[q];
+                    }
+                }
+            }
+            continue;
+        }
+        if (ART2 && T.asset == 2) {  // an event on the second articulation: its defaults, its limits, its out buffers
+            if (T.op == IMX_E_RESET_JOINTS_BY_SCALE || T.op == IMX_E_RESET_JOINTS_BY_OFFSET) {  // lane = joint, as for the robot below
+                const int J2 = (int)ap->num_joints;
+                const bool by_offset = T.op == IMX_E_RESET_JOINTS_BY_OFFSET;
+                for (uint64_t m = __ballot(valid); m != 0ull; m &= m - 1ull) {
+                    const int64_t er = (int64_t)blockIdx.x * ORCH_BLOCK + (__ffsll((long long)m) - 1);  // wave-uniform
+                    for (int j = lane; j < J2; j += ORCH_BLOCK) {
+                        const size_t q = (size_t)er * J2 + j;
+                        joint_reset_env(by_offset, ap->default_joint_pos_d[q], ap->default_joint_vel_d[q], draw(U, 2 * (int64_t)J2, er, j, o.seed, t, step),
+                                        draw(U, 2 * (int64_t)J2, er, J2 + j, o.seed, t, step), T.ranges, ap->soft_joint_pos_limits_d[2 * q],
+                                        ap->soft_joint_pos_limits_d[2 * q + 1], ap->soft_joint_vel_limits_d[q], ap->joint_pos_out_d + q,
+                                        ap->joint_vel_out_d + q);
+                    }
+                }
+            } else if (valid && T.op == IMX_E_RESET_ROOT_STATE_UNIFORM) {  // as for the rigid object below
+                const float* d = ap->default_root_state_d + e * 13;
+                float rs[6], u6[6];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) rs[k] = draw(U, 12, e, k, o.seed, t, step) * (T.ranges[2 * k + 1] - T.ranges[2 * k]) + T.ranges[2 * k];
+                root_pose_uniform_env(d, ox, oy, oz, rs, ap->root_pose_out_d + e * 7);
+#pragma unroll
+                for (int k = 0; k < 6; ++k) u6[k] = draw(U, 12, e, 6 + k, o.seed, t, step);
+                root_vel_uniform_env(d, u6, T.ranges + 12, ap->root_vel_out_d + e * 6);
             }
             continue;
         }
@@ -334,12 +374,18 @@ __global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate_pose2d(imx_orc
     orch_body<false, false, true>(o, nullptr, &c);
 }
 
+__global__ void __launch_bounds__(ORCH_BLOCK) k_reset_orchestrate_scene(imx_orch_t o, imx_orch_manip_t m, imx_orch_articulation_t a) {
+    orch_body<true, true, false, true>(o, &m, nullptr, &a);
+}
+
 }  // namespace
 
 extern "C" size_t imx_orch_part_floats(int64_t num_envs) { return num_envs > 0 ? (size_t)((num_envs + ORCH_BLOCK - 1) / ORCH_BLOCK) * 4 : 0; }
 
-// the argument checks of the entry points (m = NULL and pc = NULL: imx_reset_orchestrate; pc: imx_reset_orchestrate_pose2d) and the launch
-static int orch_launch(const imx_orch_t* o, const imx_orch_manip_t* m, imx_stream_t stream, const imx_pose2d_command_t* pc = nullptr) {
+// the argument checks of the entry points (m = NULL and pc = NULL: imx_reset_orchestrate; pc: imx_reset_orchestrate_pose2d; m and a:
+// imx_reset_orchestrate_scene) and the launch
+static int orch_launch(const imx_orch_t* o, const imx_orch_manip_t* m, imx_stream_t stream, const imx_pose2d_command_t* pc = nullptr,
+                       const imx_orch_articulation_t* a = nullptr) {
     IMX_REQUIRE(o, "imx_reset_orchestrate: null descriptor");
     IMX_REQUIRE(o->num_envs > 0 && o->num_envs < (1ll << 31), "imx_reset_orchestrate: num_envs out of range");
     IMX_REQUIRE(o->num_terms >= 0 && o->num_terms <= IMX_ORCH_MAX_TERMS, "imx_reset_orchestrate: %d event terms (at most %d)", o->num_terms,
@@ -358,8 +404,27 @@ static int orch_launch(const imx_orch_t* o, const imx_orch_manip_t* m, imx_strea
             IMX_REQUIRE(T.op == IMX_E_PUSH_BY_SETTING_VELOCITY || T.op == IMX_E_APPLY_EXTERNAL_FORCE_TORQUE,
                         "imx_reset_orchestrate: interval term %d: op %d is not an interval event here", t, T.op);
         }
-        IMX_REQUIRE(T.asset == 0 || (T.asset == 1 && T.op == IMX_E_RESET_ROOT_STATE_UNIFORM),
-                    "imx_reset_orchestrate: term %d: asset %d with op %d (0 the robot; 1 the rigid object, reset_root_state_uniform only)", t, T.asset, T.op);
+        IMX_REQUIRE(T.asset == 0 || (T.asset == 1 && T.op == IMX_E_RESET_ROOT_STATE_UNIFORM) || (T.asset == 2 && a),
+                    "imx_reset_orchestrate: term %d: asset %d with op %d (0 the robot; 1 the rigid object, reset_root_state_uniform only; 2 the "
+                    "second articulation, which travels in imx_orch_articulation_t: that is imx_reset_orchestrate_scene)", t, T.asset, T.op);
+        if (T.asset == 2) {
+            const bool joints = T.op == IMX_E_RESET_JOINTS_BY_SCALE || T.op == IMX_E_RESET_JOINTS_BY_OFFSET;
+            IMX_REQUIRE(T.mode == 0 && (joints || T.op == IMX_E_RESET_ROOT_STATE_UNIFORM),
+                        "imx_reset_orchestrate_scene: term %d: op %d in mode %d on the second articulation has no kernel (the reset events "
+                        "reset_root_state_uniform, reset_joints_by_offset and reset_joints_by_scale have)", t, T.op, T.mode);
+            IMX_REQUIRE(a->default_root_state_d || joints, "imx_reset_orchestrate_scene: term %d acts on the second articulation, which lacks default_root_state", t);
+            IMX_REQUIRE(a->root_pose_out_d || joints, "imx_reset_orchestrate_scene: term %d acts on the second articulation, which lacks root_pose_out", t);
+            IMX_REQUIRE(a->root_vel_out_d || joints, "imx_reset_orchestrate_scene: term %d acts on the second articulation, which lacks root_vel_out", t);
+            if (joints) {
+                IMX_REQUIRE(a->default_joint_pos_d, "imx_reset_orchestrate_scene: term %d acts on the second articulation, which lacks default_joint_pos", t);
+                IMX_REQUIRE(a->default_joint_vel_d, "imx_reset_orchestrate_scene: term %d acts on the second articulation, which lacks default_joint_vel", t);
+                IMX_REQUIRE(a->soft_joint_pos_limits_d, "imx_reset_orchestrate_scene: term %d is a joint event on the second articulation, which lacks soft_joint_pos_limits", t);
+                IMX_REQUIRE(a->soft_joint_vel_limits_d, "imx_reset_orchestrate_scene: term %d is a joint event on the second articulation, which lacks soft_joint_vel_limits", t);
+                IMX_REQUIRE(a->joint_pos_out_d, "imx_reset_orchestrate_scene: term %d acts on the second articulation, which lacks joint_pos_out", t);
+                IMX_REQUIRE(a->joint_vel_out_d, "imx_reset_orchestrate_scene: term %d acts on the second articulation, which lacks joint_vel_out", t);
+            }
+            continue;
+        }
         if (T.asset == 1) {
             IMX_REQUIRE(m, "imx_reset_orchestrate: term %d acts on the rigid object: that is imx_reset_orchestrate_manip", t);
             IMX_REQUIRE(m->object_default_root_state_d && m->object_root_pose_out_d && m->object_root_vel_out_d,
@@ -375,6 +440,15 @@ static int orch_launch(const imx_orch_t* o, const imx_orch_manip_t* m, imx_strea
                             "imx_reset_orchestrate_manip: reset_scene_to_default needs the robot's default root and joint state and their outputs");
                 IMX_REQUIRE(!m->object_default_root_state_d || (m->object_root_pose_out_d && m->object_root_vel_out_d),
                             "imx_reset_orchestrate_manip: the rigid object lacks an out buffer");
+                if (a) {  // reset_scene_to_default walks every articulation of the scene
+                    IMX_REQUIRE(a->default_root_state_d, "imx_reset_orchestrate_scene: term %d (reset_scene_to_default): the second articulation lacks default_root_state", t);
+                    IMX_REQUIRE(a->default_joint_pos_d, "imx_reset_orchestrate_scene: term %d (reset_scene_to_default): the second articulation lacks default_joint_pos", t);
+                    IMX_REQUIRE(a->default_joint_vel_d, "imx_reset_orchestrate_scene: term %d (reset_scene_to_default): the second articulation lacks default_joint_vel", t);
+                    IMX_REQUIRE(a->root_pose_out_d, "imx_reset_orchestrate_scene: term %d (reset_scene_to_default): the second articulation lacks root_pose_out", t);
+                    IMX_REQUIRE(a->root_vel_out_d, "imx_reset_orchestrate_scene: term %d (reset_scene_to_default): the second articulation lacks root_vel_out", t);
+                    IMX_REQUIRE(a->joint_pos_out_d, "imx_reset_orchestrate_scene: term %d (reset_scene_to_default): the second articulation lacks joint_pos_out", t);
+                    IMX_REQUIRE(a->joint_vel_out_d, "imx_reset_orchestrate_scene: term %d (reset_scene_to_default): the second articulation lacks joint_vel_out", t);
+                }
                 break;
             case IMX_E_RESET_ROOT_STATE_UNIFORM:
                 IMX_REQUIRE(o->default_root_state_d && o->root_pose_out_d && o->root_vel_out_d, "imx_reset_orchestrate: reset_root_state_uniform needs "
@@ -454,7 +528,12 @@ static int orch_launch(const imx_orch_t* o, const imx_orch_manip_t* m, imx_strea
                         "imx_reset_orchestrate_manip: weight term %d has a step_reward column but no switch_step word or no step_reward_stride (%d)",
                         i, m->step_reward_stride);
         }
-        hipLaunchKernelGGL(k_reset_orchestrate_manip, dim3(grid), dim3(ORCH_BLOCK), 0, (hipStream_t)stream, *o, *m);
+        if (a) {
+            IMX_REQUIRE(a->num_joints > 0 && a->num_joints < (1ll << 20), "imx_reset_orchestrate_scene: the second articulation has %lld joints",
+                        (long long)a->num_joints);
+            hipLaunchKernelGGL(k_reset_orchestrate_scene, dim3(grid), dim3(ORCH_BLOCK), 0, (hipStream_t)stream, *o, *m, *a);
+        } else
+            hipLaunchKernelGGL(k_reset_orchestrate_manip, dim3(grid), dim3(ORCH_BLOCK), 0, (hipStream_t)stream, *o, *m);
     } else if (o->has_command == 2)
         hipLaunchKernelGGL(k_reset_orchestrate<true>, dim3(grid), dim3(ORCH_BLOCK), 0, (hipStream_t)stream, *o);
     else
@@ -473,4 +552,10 @@ extern "C" int imx_reset_orchestrate_manip(const imx_orch_t* o, const imx_orch_m
 extern "C" int imx_reset_orchestrate_pose2d(const imx_orch_t* o, const imx_pose2d_command_t* cmd, imx_stream_t stream) {
     IMX_REQUIRE(cmd, "imx_reset_orchestrate_pose2d: null imx_pose2d_command_t");
     return orch_launch(o, nullptr, stream, cmd);
+}
+
+extern "C" int imx_reset_orchestrate_scene(const imx_orch_t* o, const imx_orch_manip_t* m, const imx_orch_articulation_t* a, imx_stream_t stream) {
+    IMX_REQUIRE(m, "imx_reset_orchestrate_scene: null imx_orch_manip_t");
+    IMX_REQUIRE(a, "imx_reset_orchestrate_scene: null imx_orch_articulation_t");
+    return orch_launch(o, m, stream, nullptr, a);
 }

@@ -575,6 +575,19 @@ class _SecondArticulationData:
         dev, N = env.device, env.num_envs
         self.default_joint_pos = torch.tensor(spec.default_joint_pos, dtype=torch.float32, device=dev).repeat(N, 1)
         self.default_joint_vel = torch.tensor(spec.default_joint_vel, dtype=torch.float32, device=dev).repeat(N, 1)
+        self.default_root_state = torch.tensor(spec.default_root_state, dtype=torch.float32, device=dev).repeat(N, 1)
+        # the limit tables of the scene entry (PhysX provides them in the reference), soft limits as Articulation._process_cfg derives
+        # them: mean -+ 0.5 * range * factor, in fp32; None without the tables (only a joint reset event on this asset reads them)
+        self.joint_pos_limits = self.soft_joint_pos_limits = self.joint_vel_limits = self.soft_joint_vel_limits = None
+        if spec.joint_pos_limits is not None:
+            lim = torch.tensor(spec.joint_pos_limits, dtype=torch.float32)
+            mean, rng = (lim[..., 0] + lim[..., 1]) / 2, lim[..., 1] - lim[..., 0]
+            soft = torch.stack([mean - 0.5 * rng * spec.soft_joint_pos_limit_factor, mean + 0.5 * rng * spec.soft_joint_pos_limit_factor], dim=-1)
+            self.joint_pos_limits = lim.to(dev).repeat(N, 1, 1)
+            self.soft_joint_pos_limits = soft.to(dev).repeat(N, 1, 1).contiguous()
+        if spec.joint_vel_limits is not None:
+            self.joint_vel_limits = torch.tensor(spec.joint_vel_limits, dtype=torch.float32, device=dev).repeat(N, 1)
+            self.soft_joint_vel_limits = self.joint_vel_limits.clone()
 
     def __getattr__(self, name):
         if name in ("joint_pos", "joint_vel", "body_pos_w", "body_quat_w"):
@@ -786,12 +799,6 @@ class ManagerBasedRLEnv:
                 state_feed.ensure_articulation_state(self._entities.second, plan.frame_tables)
             except KeyError:
                 pass
-        if self._entities.second is not None and (events_cfg or own_managers):
-            # reset_scene_to_default writes every articulation's default root and joint state (envs/mdp/events.py:1096-1118): the
-            # orchestration launch's imx_orch_manip_t carries the robot and one rigid object only
-            raise NotImplementedError(f"the scene's second articulation '{self._entities.second.name}' has no place in the reset orchestration "
-                                      "(imx_orch_manip_t carries the robot and one rigid object): events_cfg= / own_managers=True "
-                                      "are not built for this cfg; the plain env steps it on the feed's state")
         self.step_dt = plan.step_dt
         self.physics_dt = float(env_dict["sim"]["dt"])
         self.max_episode_length = plan.max_episode_length
@@ -994,7 +1001,7 @@ class ManagerBasedRLEnv:
             from .producers import ArticulationRootState
 
             self.articulation = ArticulationRootState(N, plan.num_joints, self.device)
-        self._orch = self._orch_manip = self._orch_pose2d = None
+        self._orch = self._orch_manip = self._orch_pose2d = self._orch_articulation = None
         self._weight_switch_step = None  # one device word per modify_reward_weight term (imx_weight_term_t.switch_step_d)
         J = plan.num_joints
         if events_cfg:
@@ -1063,6 +1070,15 @@ class ManagerBasedRLEnv:
                 ors[:, 10:13] = torch.tensor(oinit.get("ang_vel", (0.0, 0.0, 0.0)), dtype=torch.float32, device=self.device)
                 self.default_object_root_state = ors
                 self.sim_writes.update(object_root_pose=torch.zeros(N, 7, device=self.device), object_root_vel=torch.zeros(N, 6, device=self.device))
+            # the scene's second articulation (Open-Drawer's cabinet): what its write_root_pose_to_sim / write_root_velocity_to_sim /
+            # write_joint_state_to_sim receive, under "<name>_root_pose" ...
+            second = self._entities.second
+            if second is not None:
+                J2 = second.num_joints
+                self.sim_writes.update({f"{second.name}_root_pose": torch.zeros(N, 7, device=self.device),
+                                        f"{second.name}_root_vel": torch.zeros(N, 6, device=self.device),
+                                        f"{second.name}_joint_pos": torch.zeros(N, J2, device=self.device),
+                                        f"{second.name}_joint_vel": torch.zeros(N, J2, device=self.device)})
             self._ev_part = torch.zeros(int(self._lib.imx_orch_part_floats(N)), device=self.device)
             self._orch_draws = {}  # parity runs: "command" -> (2,N,7) uniforms, "rand_levels" -> (N) int64
             self.defer_step_tail = True
@@ -1538,7 +1554,7 @@ class ManagerBasedRLEnv:
         ct = self.command_term
         self._orch_pose2d = None
         if ct is not None and self._pose2d_command:  # (has_command stays 0: imx_reset_orchestrate_pose2d takes the term's own struct)
-            if self.event_manager is not None and self.event_manager.needs_manip:
+            if self.event_manager is not None and (self.event_manager.needs_manip or self.event_manager.needs_scene):
                 raise NotImplementedError(f"command term '{self.command_term_name}': a pose-2d command beside an event on a rigid object or "
                                           "reset_scene_to_default is not built (those run in imx_reset_orchestrate_manip)")
             self._orch_pose2d = ct.struct()
@@ -1579,7 +1595,8 @@ class ManagerBasedRLEnv:
         self._orch_manip = None
         cm = self.curriculum_manager
         weights = cm.weight_terms if cm is not None else []
-        if weights or (self.event_manager is not None and self.event_manager.needs_manip):
+        scene = self.event_manager is not None and self.event_manager.needs_scene
+        if weights or scene or (self.event_manager is not None and self.event_manager.needs_manip):
             m = _lib.ImxOrchManip(num_weight_terms=len(weights), step_reward_stride=self._step_reward.shape[1])
             if self.default_object_root_state is not None:
                 m.object_default_root_state_d = p(self.default_object_root_state)
@@ -1592,6 +1609,18 @@ class ManagerBasedRLEnv:
                 W.step_reward_d = self._step_reward.data_ptr() + 4 * w["index"]
                 W.switch_step_d = self._weight_switch_step.data_ptr() + 4 * i
             self._orch_manip = m
+        # ... and on a scene with a second articulation (imx_reset_orchestrate_scene): its defaults, limits and out buffers.  Built once:
+        # the tensors live as long as the env, so a captured graph keeps valid pointers
+        self._orch_articulation = None
+        if scene:
+            second = self._entities.second
+            d, w = self.scene[second.name].data, self.sim_writes
+            self._orch_articulation = _lib.ImxOrchArticulation(
+                num_joints=second.num_joints, default_root_state_d=p(d.default_root_state), default_joint_pos_d=p(d.default_joint_pos),
+                default_joint_vel_d=p(d.default_joint_vel), soft_joint_pos_limits_d=p(d.soft_joint_pos_limits),
+                soft_joint_vel_limits_d=p(d.soft_joint_vel_limits), root_pose_out_d=p(w[f"{second.name}_root_pose"]),
+                root_vel_out_d=p(w[f"{second.name}_root_vel"]), joint_pos_out_d=p(w[f"{second.name}_joint_pos"]),
+                joint_vel_out_d=p(w[f"{second.name}_joint_vel"]))
         return o
 
     def _orchestrate(self, reset_mask, do_step: bool):
@@ -1619,6 +1648,9 @@ class ManagerBasedRLEnv:
             check(self._lib.imx_reset_orchestrate_pose2d(ctypes.byref(o), ctypes.byref(c), _lib.current_stream(self.device)))
             if do_step:
                 self.command_term.mark_computed()
+        elif self._orch_articulation is not None:
+            check(self._lib.imx_reset_orchestrate_scene(ctypes.byref(o), ctypes.byref(self._orch_manip), ctypes.byref(self._orch_articulation),
+                                                        _lib.current_stream(self.device)))
         elif self._orch_manip is not None:
             check(self._lib.imx_reset_orchestrate_manip(ctypes.byref(o), ctypes.byref(self._orch_manip), _lib.current_stream(self.device)))
         else:

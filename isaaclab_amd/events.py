@@ -166,13 +166,26 @@ class EventTermState:
         r = [0.0] * 24
         self.width = 0
         self.body_ids = None
-        # params["asset_cfg"].name -> the asset selector of imx_event_term_t: 0 the robot, 1 the scene's rigid object
+        # params["asset_cfg"].name -> the asset selector of imx_event_term_t: 0 the robot, 1 the scene's rigid object, 2 its second
+        # articulation (imx_reset_orchestrate_scene)
         ent = p.get("asset_cfg") or {}
         ent_name = (ent.get("name") if isinstance(ent, dict) else getattr(ent, "name", None)) or "robot"
         objects = list(entities.rigid_objects) if entities is not None else []
-        if ent_name != "robot" and ent_name not in objects:
-            raise ValueError(f"event term '{name}': asset_cfg names the scene entity '{ent_name}'; the scene has {['robot'] + objects}")
-        self.asset = 0 if ent_name == "robot" else 1
+        second = entities.second if entities is not None else None
+        if ent_name != "robot" and ent_name not in objects and (second is None or ent_name != second.name):
+            raise ValueError(f"event term '{name}': asset_cfg names the scene entity '{ent_name}'; the scene has "
+                             f"{['robot'] + objects + ([second.name] if second is not None else [])}")
+        self.asset = 0 if ent_name == "robot" else 1 if ent_name in objects else 2
+        if self.asset == 2:
+            if self.func not in ("reset_root_state_uniform", "reset_joints_by_offset", "reset_joints_by_scale") or self.mode != "reset":
+                raise NotImplementedError(f"event term '{name}': '{self.func}' ({self.mode}) on the second articulation '{ent_name}' has no "
+                                          "kernel (the reset events reset_root_state_uniform, reset_joints_by_offset and "
+                                          "reset_joints_by_scale have)")
+            if self.func.startswith("reset_joints"):
+                for table in ("joint_pos_limits", "joint_vel_limits"):
+                    if getattr(second, table) is None:
+                        raise ValueError(f"event term '{name}': '{self.func}' clamps to the limits of '{ent_name}', whose scene entry has no "
+                                         f"'{table}' table (PhysX provides it in the reference; here it comes with the scene entry)")
         if self.asset == 1 and len(objects) > 1:
             raise NotImplementedError(f"event term '{name}': the scene has {len(objects)} rigid objects {objects}; the orchestration "
                                       "launch carries one object's root state")
@@ -186,7 +199,7 @@ class EventTermState:
             self.width = 12
         elif self.func.startswith("reset_joints"):
             r[:4] = [float(x) for x in (*p["position_range"], *p["velocity_range"])]
-            self.width = 2 * robot.num_joints
+            self.width = 2 * (second.num_joints if self.asset == 2 else robot.num_joints)
         elif self.func == "push_by_setting_velocity":
             r[:12] = _axis_ranges(p.get("velocity_range"))
             self.width = 6
@@ -231,6 +244,7 @@ class EventManager:
         self.terms: list[EventTermState] = []
         self.skipped_terms: list[str] = []
         self.seed = int(seed)
+        self._second = entities.second if entities is not None else None
         for name, term in (events_cfg or {}).items():
             if term is None:
                 continue
@@ -262,6 +276,12 @@ class EventManager:
     def needs_manip(self) -> bool:
         """A term that only ``imx_reset_orchestrate_manip`` runs: ``reset_scene_to_default`` or an event on the rigid object."""
         return any(t.asset == 1 or t.func == "reset_scene_to_default" for t in self.terms)
+
+    @property
+    def needs_scene(self) -> bool:
+        """The scene has a second articulation and a term only ``imx_reset_orchestrate_scene`` runs: an event on that asset, or
+        ``reset_scene_to_default``, which walks every articulation."""
+        return self._second is not None and any(t.asset == 2 or t.func == "reset_scene_to_default" for t in self.terms)
 
     @property
     def available_modes(self) -> list:

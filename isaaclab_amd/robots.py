@@ -151,10 +151,30 @@ class SecondArticulation:
     root_pos: tuple
     root_rot: tuple  # w, x, y, z
     prim_path: str | None = None
+    # what PhysX reports in the reference (ArticulationData.joint_pos_limits / joint_vel_limits) and the cfg's soft_joint_pos_limit_factor:
+    # read from the scene entry when it carries them; only a joint reset event on this asset needs them
+    joint_pos_limits: list | None = None  # one (lower, upper) per joint
+    joint_vel_limits: list | None = None  # one float per joint
+    soft_joint_pos_limit_factor: float = 1.0
+    root_lin_vel: tuple = (0.0, 0.0, 0.0)
+    root_ang_vel: tuple = (0.0, 0.0, 0.0)
 
     @property
     def num_joints(self) -> int:
         return len(self.joint_names)
+
+    @property
+    def default_root_state(self) -> list:
+        """``ArticulationData.default_root_state`` of one env: position, w-x-y-z rotation, linear and angular velocity."""
+        return [*self.root_pos, *self.root_rot, *self.root_lin_vel, *self.root_ang_vel]
+
+    @property
+    def soft_joint_pos_limits(self) -> list | None:
+        """Articulation._process_cfg: mean +- 0.5 * range * factor per joint (None without ``joint_pos_limits``)."""
+        if self.joint_pos_limits is None:
+            return None
+        f = self.soft_joint_pos_limit_factor
+        return [(0.5 * (lo + hi) - 0.5 * (hi - lo) * f, 0.5 * (lo + hi) + 0.5 * (hi - lo) * f) for lo, hi in self.joint_pos_limits]
 
     @property
     def num_bodies(self) -> int:
@@ -177,9 +197,25 @@ class SecondArticulation:
                     out[i] = float(v)
             return out
 
+        def limits(key, width):  # a per-joint table of the scene entry: one row for every joint, or one row for all of them
+            v = ent.get(key)
+            if v is None:
+                return None
+            rows = list(v)
+            if width == 2 and len(rows) == 2 and not isinstance(rows[0], (list, tuple)):
+                rows = [rows] * len(jn)
+            elif width == 1 and len(rows) == 1:
+                rows = rows * len(jn)
+            if len(rows) != len(jn):
+                raise ValueError(f"scene entity '{name}': '{key}' has {len(rows)} rows, the articulation has {len(jn)} joints")
+            return [tuple(float(x) for x in r) for r in rows] if width == 2 else [float(r) for r in rows]
+
         return cls(name=name, joint_names=list(jn), body_names=list(bn), default_joint_pos=table("joint_pos"), default_joint_vel=table("joint_vel"),
                    root_pos=tuple(float(x) for x in init.get("pos", (0.0, 0.0, 0.0))), root_rot=tuple(float(x) for x in init.get("rot", (1.0, 0.0, 0.0, 0.0))),
-                   prim_path=ent.get("prim_path"))
+                   prim_path=ent.get("prim_path"), joint_pos_limits=limits("joint_pos_limits", 2), joint_vel_limits=limits("joint_vel_limits", 1),
+                   soft_joint_pos_limit_factor=float(ent.get("soft_joint_pos_limit_factor", 1.0)),
+                   root_lin_vel=tuple(float(x) for x in init.get("lin_vel", (0.0, 0.0, 0.0))),
+                   root_ang_vel=tuple(float(x) for x in init.get("ang_vel", (0.0, 0.0, 0.0))))
 
 
 class SceneEntityResolver:

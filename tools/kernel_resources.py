@@ -18,7 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
          "--cuda-device-only", "-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-KEYS = {"SGPRs": "sgpr", "VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy",
+KEYS = {"SGPRs": "sgpr", "TotalSGPRs": "sgpr", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill", "VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy",
         "LDS Size [bytes/block]": "lds"}
 
 

@@ -958,6 +958,17 @@ int imx_mlp_infer_act(int64_t M, const float* X_d, int64_t ldx, int nnets, const
                       const float* const* weights_d, const int* weight_pitch, const float* const* packed_weights_d,
                       const float* const* biases_d, const float* elu_alpha, float* const* out_d, const imx_policy_act_t* act,
                       imx_stream_t stream);
+/* The same launch for networks that do NOT share their input: an env with a privileged ("critic") observation group, where the actor
+ * reads the policy group and the critic its own.  X_d and ldx are HOST arrays of nnets entries: network k reads X_d[k] (M, width_k; pitch
+ * ldx[k] >= width_k), width_k = the first of its dims, and the widths may differ.  critic_obs_out_d (optional, nnets == 2 only): network
+ * 1's workgroups also store their input rows densely there, (M, width_1) -- storage.privileged_observations[t] -- on the way into LDS, as
+ * the actor's workgroups do for act->obs_out_d.  act == NULL and critic_obs_out_d == NULL: plain inference.  Everything else is
+ * imx_mlp_infer_act's: limits, weight layout, the rule between 16- and 32-row tiles, and -- on equal inputs -- its results, bit for bit.
+ * A refused argument is named in imx_last_error and nothing is launched. */
+int imx_mlp_infer_act2(int64_t M, const float* const* X_d, const int64_t* ldx, int nnets, const int* nlayers, const int* dims,
+                       const float* const* weights_d, const int* weight_pitch, const float* const* packed_weights_d,
+                       const float* const* biases_d, const float* elu_alpha, float* const* out_d, const imx_policy_act_t* act,
+                       float* critic_obs_out_d, imx_stream_t stream);
 /* Floats of the packed image of an (out_features x in_features) nn.Linear weight (both rounded up to multiples of 32), and the packing
  * itself (W_d row-major with row pitch ldw >= in_features; packed_d 16-byte aligned; to be repeated whenever the weights change). */
 size_t imx_mlp_packed_floats(int out_features, int in_features);

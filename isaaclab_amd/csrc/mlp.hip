@@ -1185,6 +1185,7 @@ __device__ __forceinline__ void act_epilogue(const ActArgs& c, const float* __re
 
 
 // (the kernel bodies are textual includes, see mlp_infer_body.inc: *_binary = for a plan with a binary joint term)
+#define IMX_INFER_TWO_INPUTS 0
 template <bool PACKED>
 __global__ void __launch_bounds__(256, 1) k_mlp_infer(InferArgs a, ActArgs act) {
 #define IMX_ACT_BINARY false
@@ -1209,6 +1210,41 @@ __global__ void __launch_bounds__(256, 2) k_mlp_infer16_binary(InferArgs a, ActA
 #include "mlp_infer16_body.inc"
 #undef IMX_ACT_BINARY
 }
+#undef IMX_INFER_TWO_INPUTS
+
+// imx_mlp_infer_act2: the same bodies for two networks that do NOT share their input (an env with a privileged "critic" observation
+// group).  A workgroup already serves one network on one row tile and takes its input width from its own net.dim[0]; here it also takes
+// the input pointer and pitch of its network, and network 1's workgroups may store their tile densely (storage.privileged_observations[t])
+// where the actor's store storage.observations[t].  Kernels of their own: the shared-input ones above keep their instruction streams.
+struct InferTwo {
+    const float* X1;   // network 1's input (M, net[1].dim[0]), pitch ldx1
+    int64_t ldx1;
+    float* obs_out1;   // (M, net[1].dim[0]) dense, or null
+};
+#define IMX_INFER_TWO_INPUTS 1
+template <bool PACKED>
+__global__ void __launch_bounds__(256, 1) k_mlp_infer2(InferArgs a, ActArgs act, InferTwo two) {
+#define IMX_ACT_BINARY false
+#include "mlp_infer_body.inc"
+#undef IMX_ACT_BINARY
+}
+template <bool PACKED>
+__global__ void __launch_bounds__(256, 1) k_mlp_infer2_binary(InferArgs a, ActArgs act, InferTwo two) {
+#define IMX_ACT_BINARY true
+#include "mlp_infer_body.inc"
+#undef IMX_ACT_BINARY
+}
+__global__ void __launch_bounds__(256, 2) k_mlp_infer2_16(InferArgs a, ActArgs act, InferTwo two) {
+#define IMX_ACT_BINARY false
+#include "mlp_infer16_body.inc"
+#undef IMX_ACT_BINARY
+}
+__global__ void __launch_bounds__(256, 2) k_mlp_infer2_16_binary(InferArgs a, ActArgs act, InferTwo two) {
+#define IMX_ACT_BINARY true
+#include "mlp_infer16_body.inc"
+#undef IMX_ACT_BINARY
+}
+#undef IMX_INFER_TWO_INPUTS
 
 extern "C" int imx_mlp_infer(int64_t M, const float* X_d, int64_t ldx, int nnets, const int* nlayers, const int* dims,
                              const float* const* weights_d, const int* weight_pitch, const float* const* biases_d, const float* elu_alpha,
@@ -1277,12 +1313,24 @@ extern "C" int imx_mlp_pack_weights(int out_features, int in_features, const flo
     return imx_mlp_pack_weights_batch(1, &out_features, &in_features, &W_d, &ldw, &packed_d, stream);
 }
 
-extern "C" int imx_mlp_infer_act(int64_t M, const float* X_d, int64_t ldx, int nnets, const int* nlayers, const int* dims,
-                                 const float* const* weights_d, const int* weight_pitch, const float* const* packed_weights_d,
-                                 const float* const* biases_d, const float* elu_alpha, float* const* out_d, const imx_policy_act_t* pa,
-                                 imx_stream_t stream) {
-    IMX_REQUIRE(M > 0 && X_d && nnets >= 1 && nnets <= 2 && nlayers && dims && weights_d && biases_d && elu_alpha && out_d,
-                "imx_mlp_infer: bad arguments");
+// Both entry points.  two_inputs false (imx_mlp_infer, imx_mlp_infer_act): every network reads X[0] with pitch ldx[0], and the checks and
+// messages are the ones those always had.  true (imx_mlp_infer_act2): network k reads X[k] with pitch ldx[k]; the messages name the argument.
+static int mlp_infer_launch(bool two_inputs, int64_t M, const float* const* X, const int64_t* ldxs, int nnets, const int* nlayers, const int* dims,
+                            const float* const* weights_d, const int* weight_pitch, const float* const* packed_weights_d,
+                            const float* const* biases_d, const float* elu_alpha, float* const* out_d, const imx_policy_act_t* pa,
+                            float* critic_obs_out_d, imx_stream_t stream) {
+    if (two_inputs) {
+        IMX_REQUIRE(M > 0 && nnets >= 1 && nnets <= 2, "imx_mlp_infer_act2: M = %lld, nnets = %d (M > 0 and 1 or 2 networks)", (long long)M, nnets);
+        IMX_REQUIRE(X && ldxs && nlayers && dims && weights_d && biases_d && elu_alpha && out_d,
+                    "imx_mlp_infer_act2: a null array among X_d, ldx, nlayers, dims, weights_d, biases_d, elu_alpha, out_d");
+        IMX_REQUIRE(!critic_obs_out_d || nnets == 2, "imx_mlp_infer_act2: critic_obs_out_d given with nnets == %d (network 1's rows: it needs 2)", nnets);
+        for (int k = 0; k < nnets; ++k) IMX_REQUIRE(X[k], "imx_mlp_infer_act2: X_d[%d] is null", k);
+    } else {
+        IMX_REQUIRE(M > 0 && X[0] && nnets >= 1 && nnets <= 2 && nlayers && dims && weights_d && biases_d && elu_alpha && out_d,
+                    "imx_mlp_infer: bad arguments");
+    }
+    const float* const X_d = X[0];
+    const int64_t ldx = ldxs[0];
     ActArgs act{};
     if (pa) {
         IMX_REQUIRE(pa->std_d && pa->actions_out_d && pa->logp_out_d && pa->mu_out_d && pa->sigma_out_d && pa->obs_out_d,
@@ -1315,13 +1363,23 @@ extern "C" int imx_mlp_infer_act(int64_t M, const float* X_d, int64_t ldx, int n
         IMX_REQUIRE(n.nlayers >= 1 && n.nlayers <= INF_MAXL, "imx_mlp_infer: network %d has %d layers (1..%d supported)", k, n.nlayers, INF_MAXL);
         for (int l = 0; l <= n.nlayers; ++l) {
             n.dim[l] = dims[di++];
+            if (two_inputs)
+                IMX_REQUIRE(n.dim[l] >= 1 && n.dim[l] <= INF_MAXD, "imx_mlp_infer_act2: dims: width %d of network %d (layer %d) outside 1..%d",
+                            n.dim[l], k, l, INF_MAXD);
             IMX_REQUIRE(n.dim[l] >= 1 && n.dim[l] <= INF_MAXD, "imx_mlp_infer: layer width %d outside 1..%d", n.dim[l], INF_MAXD);
         }
-        IMX_REQUIRE(n.dim[0] == a.net[0].dim[0] && ldx >= n.dim[0], "imx_mlp_infer: the networks must share the input (width %d, pitch %lld)",
-                    a.net[0].dim[0], (long long)ldx);
+        if (two_inputs)
+            IMX_REQUIRE(ldxs[k] >= n.dim[0], "imx_mlp_infer_act2: ldx[%d] = %lld is less than the input width %d of network %d",
+                        k, (long long)ldxs[k], n.dim[0], k);
+        else
+            IMX_REQUIRE(n.dim[0] == a.net[0].dim[0] && ldx >= n.dim[0], "imx_mlp_infer: the networks must share the input (width %d, pitch %lld)",
+                        a.net[0].dim[0], (long long)ldx);
         for (int l = 0; l < n.nlayers; ++l) {
             n.W[l] = weights_d[wi];
             n.Wp[l] = packed_weights_d ? packed_weights_d[wi] : nullptr;
+            if (two_inputs)
+                IMX_REQUIRE(!packed_weights_d || (n.Wp[l] && aligned16(n.Wp[l])),
+                            "imx_mlp_infer_act2: packed_weights_d[%d] is null or not 16-byte aligned (network %d, layer %d)", wi, k, l);
             IMX_REQUIRE(!packed_weights_d || (n.Wp[l] && aligned16(n.Wp[l])), "imx_mlp_infer: null / unaligned packed weights (network %d, layer %d)", k, l);
             n.b[l] = biases_d[wi];
             n.ldw[l] = weight_pitch ? weight_pitch[wi] : n.dim[l];
@@ -1351,6 +1409,32 @@ extern "C" int imx_mlp_infer_act(int64_t M, const float* X_d, int64_t ldx, int n
     }
     const bool binary = act.has_plan == 2;  // a plan with a binary joint term: the kernels with that path in the actor head's epilogue
     const dim3 bs(256);
+    if (two_inputs) {  // the same choice among the two-input kernels
+        static bool attr2_set = false;
+        if (!attr2_set) {
+            const void* big[] = {reinterpret_cast<const void*>(k_mlp_infer2<false>), reinterpret_cast<const void*>(k_mlp_infer2<true>),
+                                 reinterpret_cast<const void*>(k_mlp_infer2_binary<false>), reinterpret_cast<const void*>(k_mlp_infer2_binary<true>)};
+            for (const void* f : big) IMX_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2ull * INF_ROWS * INF_PITCH * sizeof(float))));
+            const void* small16[] = {reinterpret_cast<const void*>(k_mlp_infer2_16), reinterpret_cast<const void*>(k_mlp_infer2_16_binary)};
+            for (const void* f : small16) IMX_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2ull * INF16_ROWS * INF_PITCH * sizeof(float))));
+            attr2_set = true;
+        }
+        InferTwo two{};
+        if (nnets == 2) { two.X1 = X[1]; two.ldx1 = ldxs[1]; two.obs_out1 = critic_obs_out_d; }
+        if (small) {
+            a.tiles = (int)((M + INF16_ROWS - 1) / INF16_ROWS);
+            hipLaunchKernelGGL(binary ? k_mlp_infer2_16_binary : k_mlp_infer2_16, dim3((unsigned)(a.tiles * nnets)), bs,
+                               2ull * INF16_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act, two);
+        } else if (packed_weights_d) {
+            hipLaunchKernelGGL(binary ? k_mlp_infer2_binary<true> : k_mlp_infer2<true>, dim3((unsigned)(a.tiles * nnets)), bs,
+                               2ull * INF_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act, two);
+        } else {
+            hipLaunchKernelGGL(binary ? k_mlp_infer2_binary<false> : k_mlp_infer2<false>, dim3((unsigned)(a.tiles * nnets)), bs,
+                               2ull * INF_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act, two);
+        }
+        IMX_HIP(hipGetLastError());
+        return 0;
+    }
     if (small) {
         a.tiles = (int)((M + INF16_ROWS - 1) / INF16_ROWS);
         hipLaunchKernelGGL(binary ? k_mlp_infer16_binary : k_mlp_infer16, dim3((unsigned)(a.tiles * nnets)), bs,
@@ -1364,4 +1448,20 @@ extern "C" int imx_mlp_infer_act(int64_t M, const float* X_d, int64_t ldx, int n
     }
     IMX_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" int imx_mlp_infer_act(int64_t M, const float* X_d, int64_t ldx, int nnets, const int* nlayers, const int* dims,
+                                 const float* const* weights_d, const int* weight_pitch, const float* const* packed_weights_d,
+                                 const float* const* biases_d, const float* elu_alpha, float* const* out_d, const imx_policy_act_t* pa,
+                                 imx_stream_t stream) {
+    return mlp_infer_launch(false, M, &X_d, &ldx, nnets, nlayers, dims, weights_d, weight_pitch, packed_weights_d, biases_d, elu_alpha, out_d, pa,
+                            nullptr, stream);
+}
+
+extern "C" int imx_mlp_infer_act2(int64_t M, const float* const* X_d, const int64_t* ldx, int nnets, const int* nlayers, const int* dims,
+                                  const float* const* weights_d, const int* weight_pitch, const float* const* packed_weights_d,
+                                  const float* const* biases_d, const float* elu_alpha, float* const* out_d, const imx_policy_act_t* act,
+                                  float* critic_obs_out_d, imx_stream_t stream) {
+    return mlp_infer_launch(true, M, X_d, ldx, nnets, nlayers, dims, weights_d, weight_pitch, packed_weights_d, biases_d, elu_alpha, out_d, act,
+                            critic_obs_out_d, stream);
 }

@@ -1,6 +1,6 @@
 // The body of k_mlp_infer / k_mlp_infer_binary (mlp.hip), included once per kernel with IMX_ACT_BINARY = false (the kernel as it always was) or true (the actor
 // head's epilogue with the binary joint term's path).  A textual include, not a device function: the existing kernels then compile to the
-// instruction streams they had.
+// instruction streams they had.  Also the body of k_mlp_infer2 / k_mlp_infer2_binary (IMX_INFER_TWO_INPUTS = 1, below).
     extern __shared__ float smem[];  // two activation buffers of INF_ROWS x INF_PITCH floats
     float* buf0 = smem;
     float* buf1 = smem + INF_ROWS * INF_PITCH;
@@ -8,6 +8,23 @@
     const InferNet& net = a.net[which];
     const int64_t m0 = (int64_t)(blockIdx.x - which * a.tiles) * INF_ROWS;
     const bool act_here = act.enabled && which == 0;  // the actor's workgroups finish PPO.act + ActionManager.process_action themselves
+    // Where the input rows come from, and whether the tile is also stored densely on its way into LDS.  IMX_INFER_TWO_INPUTS = 0 are macros
+    // that spell what the body always said (same tokens, same kernels); 1 (k_mlp_infer2*, argument `two`): network 1 reads its own
+    // input and may keep its rows as well (storage.privileged_observations[t])
+#if IMX_INFER_TWO_INPUTS
+    const float* const x_in = which ? two.X1 : a.X;
+    const int64_t ldx_in = which ? two.ldx1 : a.ldx;
+    float* const obs_dst = which ? two.obs_out1 : (act.enabled ? act.obs_out : nullptr);
+#define IMX_INFER_X x_in
+#define IMX_INFER_LDX ldx_in
+#define IMX_INFER_OBS_ON (obs_dst != nullptr)
+#define IMX_INFER_OBS_DST obs_dst
+#else
+#define IMX_INFER_X a.X
+#define IMX_INFER_LDX a.ldx
+#define IMX_INFER_OBS_ON act_here
+#define IMX_INFER_OBS_DST act.obs_out
+#endif
     // input rows -> LDS (the 32 rows are one contiguous run when ldx == dim[0]); columns up to the next multiple of 32 are zeroed
     const int K0 = net.dim[0], K0p = (K0 + 31) & ~31;
     {
@@ -20,7 +37,7 @@
 #pragma unroll
         for (int rr = 0; rr < 8; ++rr) {
             const int row = w + 4 * rr;
-            const float* src = a.X + (m0 + row < a.M ? m0 + row : 0) * a.ldx;
+            const float* src = IMX_INFER_X + (m0 + row < a.M ? m0 + row : 0) * IMX_INFER_LDX;
 #pragma unroll
             for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
                 if (cc < ncc) {
@@ -39,7 +56,7 @@
             for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
                 const int c = lane + 64 * cc;
                 if (c < K0p) buf0[row * INF_PITCH + c] = v[rr][cc];
-                if (act_here && c < K0 && m0 + row < a.M) act.obs_out[(m0 + row) * (int64_t)K0 + c] = v[rr][cc];  // storage.observations[t]
+                if (IMX_INFER_OBS_ON && c < K0 && m0 + row < a.M) IMX_INFER_OBS_DST[(m0 + row) * (int64_t)K0 + c] = v[rr][cc];  // storage.observations[t]
             }
         }
     }
@@ -66,3 +83,7 @@
         float* t = in; in = out; out = t;
     }
     if (act_here) act_epilogue<INF_ROWS, IMX_ACT_BINARY>(act, in, out, m0, a.M);
+#undef IMX_INFER_X
+#undef IMX_INFER_LDX
+#undef IMX_INFER_OBS_ON
+#undef IMX_INFER_OBS_DST

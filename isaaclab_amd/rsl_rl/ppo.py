@@ -126,22 +126,25 @@ def _mlp_layers(seq: nn.Sequential):
 
 
 class FusedInference:
-    """``imx_mlp_infer`` bound to one or two Linear+ELU stacks (actor, critic) that share their input: argument arrays are
-    built once (the parameters live at fixed addresses in the flat bucket)."""
+    """``imx_mlp_infer`` bound to one or two Linear+ELU stacks (actor, critic): argument arrays are built once (the parameters live
+    at fixed addresses in the flat bucket).  Stacks whose first layers differ in ``in_features`` (an env with a "critic" observation
+    group) make a TWO-INPUT instance: ``__call__`` then takes the critic's rows as ``critic_x`` and runs ``imx_mlp_infer_act2``."""
 
     MAX_WIDTH, MAX_LAYERS = 512, 4
 
-    def __init__(self, *nets):
+    def __init__(self, *nets, two_inputs: bool | None = None):
+        """``two_inputs``: None = whenever the two first layers differ in ``in_features``; True = also when they agree (a critic group
+        as wide as the policy group is still another input)."""
         import ctypes
 
         self.ok = 1 <= len(nets) <= 2
+        self.two_inputs = False
         self._padded, self._wpk = [], None  # (a stack that does not fit returns below: refresh() must still be callable)
         dims, ws, bs, alphas, nl = [], [], [], [], []
         for layers in nets:
             acts = [a for _, a in layers[:-1]]
             if (len(layers) > self.MAX_LAYERS or layers[-1][1] is not None or any(not isinstance(a, nn.ELU) for a in acts)
-                    or any(max(lin.in_features, lin.out_features) > self.MAX_WIDTH for lin, _ in layers)
-                    or layers[0][0].in_features != nets[0][0][0].in_features):
+                    or any(max(lin.in_features, lin.out_features) > self.MAX_WIDTH for lin, _ in layers)):
                 self.ok = False
                 return
             nl.append(len(layers))
@@ -150,6 +153,8 @@ class FusedInference:
             bs += [lin.bias for lin, _ in layers]
             alphas.append(float(acts[0].alpha) if acts else 1.0)
         self.in_features = dims[0]
+        self.critic_in_features = nets[1][0][0].in_features if len(nets) == 2 else None
+        self.two_inputs = len(nets) == 2 and (bool(two_inputs) or self.critic_in_features != self.in_features)
         self.out_features = [layers[-1][0].out_features for layers in nets]
         # Layers whose in-features are not a multiple of 32 (235 observations) get a zero-padded copy of their weights with a
         # row pitch that is (the kernel issues unconditional 16-byte loads over whole 32-wide reduction groups);
@@ -197,12 +202,30 @@ class FusedInference:
         if self._wpk is not None:  # all layers in one launch
             check(lib().imx_mlp_pack_weights_batch(*self._pack_args, _lib.current_stream(self._packed[0].device)))
 
-    def __call__(self, x: torch.Tensor, *outs: torch.Tensor, act=None):
+    def __call__(self, x: torch.Tensor, *outs: torch.Tensor, act=None, critic_x: torch.Tensor | None = None,
+                 critic_obs_out: torch.Tensor | None = None):
         """``act``: an ``ImxPolicyAct`` -- the actor's workgroups then also sample the action, write the transition into the storage
-        slot it names and run the action through the env's action terms (``imx_mlp_infer_act``); ``outs[0]`` may be None then."""
+        slot it names and run the action through the env's action terms (``imx_mlp_infer_act``); ``outs[0]`` may be None then.
+        ``critic_x``: the second network's rows, for a two-input instance and only for one; ``critic_obs_out``: a dense (M, critic
+        width) buffer that then receives them too (``storage.privileged_observations[t]``)."""
         if x.stride(1) != 1 or x.shape[1] != self.in_features or any(o is not None and not o.is_contiguous() for o in outs):
             raise _lib.ImxError("imx_mlp_infer needs a row-major input and contiguous outputs")
         out_p = (self._ctypes.c_void_p * self._n)(*[None if o is None else o.data_ptr() for o in outs])
+        if self.two_inputs:
+            if critic_x is None:
+                raise _lib.ImxError("a two-input FusedInference needs critic_x: its critic does not read the actor's rows")
+            if critic_x.stride(1) != 1 or critic_x.shape != (x.shape[0], self.critic_in_features):
+                raise _lib.ImxError(f"critic_x must be row-major ({x.shape[0]}, {self.critic_in_features}), not {tuple(critic_x.shape)}")
+            if critic_obs_out is not None and (not critic_obs_out.is_contiguous() or critic_obs_out.shape != critic_x.shape):
+                raise _lib.ImxError(f"critic_obs_out must be contiguous {tuple(critic_x.shape)}")
+            xs = (self._ctypes.c_void_p * 2)(x.data_ptr(), critic_x.data_ptr())
+            ld = (self._ctypes.c_int64 * 2)(x.stride(0), critic_x.stride(0))
+            check(lib().imx_mlp_infer_act2(x.shape[0], xs, ld, self._n, self._nl, self._dims, self._w, self._pitch, self._wpk, self._b,
+                                           self._alpha, out_p, self._ctypes.byref(act) if act is not None else None,
+                                           None if critic_obs_out is None else critic_obs_out.data_ptr(), _lib.current_stream(x.device)))
+            return
+        if critic_x is not None or critic_obs_out is not None:
+            raise _lib.ImxError("critic_x / critic_obs_out given to a shared-input FusedInference: both networks read x")
         check(lib().imx_mlp_infer_act(x.shape[0], x.data_ptr(), x.stride(0), self._n, self._nl, self._dims, self._w, self._pitch, self._wpk,
                                       self._b, self._alpha, out_p, self._ctypes.byref(act) if act is not None else None,
                                       _lib.current_stream(x.device)))

@@ -43,13 +43,6 @@ class ScalarWriter:
         self._f.close()
 
 
-class _NoFusedInference:
-    ok = False
-
-    def refresh(self):
-        pass
-
-
 class OnPolicyRunner:
     def __init__(self, env, train_cfg: dict, log_dir: str | None = None, device="cpu", use_graph: bool = False):
         self.cfg = train_cfg
@@ -197,9 +190,11 @@ class OnPolicyRunner:
         """Per step THREE launches: ``imx_mlp_infer_act`` (both MLPs + PPO.act's sampling / log-prob / transition writes + the
         ActionManager's action processing in the actor head's epilogue), ``imx_terminations_rewards_rollout`` (terminations, rewards,
         resets + the wrapper's dones, the time-out bootstrap and the episode statistics into slot t) and ``imx_observations`` (+ the
-        step tail and the log accumulation).  Every transition is written straight into its storage slot.  Envs with a privileged
-        ("critic") observation group, Python-evaluated terms aside, take the split path (``fuse_launches = False``), which produces
-        bit-identical storage contents (tests/test_kernels_gpu.py)."""
+        step tail and the log accumulation).  Every transition is written straight into its storage slot.  An env with a privileged
+        ("critic") observation group takes the same three launches: the first is ``imx_mlp_infer_act2``, whose critic workgroups read
+        that group's rows and store them into ``privileged_observations[t]``.  The split path (``fuse_launches = False``) produces
+        bit-identical storage contents (tests/test_env_gpu.py, tests/test_infer_two_inputs_gpu.py); stacks that ``FusedInference``
+        does not take (a fifth layer, wider than 512, another activation) run as library GEMMs."""
         import ctypes
         import math
 
@@ -223,19 +218,22 @@ class OnPolicyRunner:
             if self._infer is None:
                 from .ppo import FusedInference
 
-                # one launch for both networks needs a shared input; with a critic group the two stacks run side by side instead
-                self._infer = FusedInference(alg._actor_layers, alg._critic_layers) if priv is None else _NoFusedInference()
+                # one launch for both networks; with a critic group each network reads its own rows (the two-input instance)
+                self._infer = FusedInference(alg._actor_layers, alg._critic_layers, two_inputs=priv is not None)
                 self._mu_buf = torch.empty(N, A, device=self.device)
                 self._value_buf = torch.empty(N, 1, device=self.device)
-            fused = self.fuse_launches and self._infer.ok and priv is None and obs.is_contiguous() and obs.shape[1] == D
+            fused = self.fuse_launches and self._infer.ok and obs.is_contiguous() and obs.shape[1] == D
             if fused:
-                # launch 1: actor + critic + PPO.act + ActionManager.process_action
+                # launch 1: actor + critic + PPO.act + ActionManager.process_action (+ the critic group's rows into their slot)
                 act = ImxPolicyAct(std_d=pol.std.data_ptr(), seed=self._act_seed, step_counter_d=step_ptr,
                                    actions_out_d=st.actions[t].data_ptr(), logp_out_d=st.actions_log_prob[t].data_ptr(),
                                    mu_out_d=st.mu[t].data_ptr(), sigma_out_d=st.sigma[t].data_ptr(), obs_out_d=st.observations[t].data_ptr(),
                                    plan=env._plan_h.value, state=ctypes.pointer(env._state()), buf=ctypes.pointer(env._bufs),
                                    pre_clip=math.inf if env.clip_actions is None else float(env.clip_actions))
-                self._infer(obs, None, st.values[t], act=act)
+                if priv is not None:
+                    self._infer(obs, None, st.values[t], act=act, critic_x=cobs, critic_obs_out=st.privileged_observations[t])
+                else:
+                    self._infer(obs, None, st.values[t], act=act)
                 # launch 2 (+ launch 3, the observations): the step kernel writes slot t itself; the log sum rides in the step tail
                 slot = ImxRolloutSlot(value_t=st.values[t].data_ptr(), rewards_out=st.rewards[t].data_ptr(), dones_out=st.dones[t].data_ptr(),
                                       cur_reward_sum=self._cur_reward_sum.data_ptr(), cur_ep_len=self._cur_episode_length.data_ptr(),
@@ -246,10 +244,14 @@ class OnPolicyRunner:
                 finally:
                     env._bufs.log_accum = None
                 obs = obs_dict["policy"]
+                cobs = obs_dict[priv] if priv is not None else obs
                 continue
             if self._infer.ok:  # both networks, all layers, one launch (activations stay in LDS)
                 mu, value = self._mu_buf, self._value_buf
-                self._infer(obs, mu, value)
+                if priv is not None:
+                    self._infer(obs, mu, value, critic_x=cobs)
+                else:
+                    self._infer(obs, mu, value)
             else:
                 side = alg._side_stream()
                 if side is not None:  # critic beside the actor (fork/join is capturable: both streams join the graph)

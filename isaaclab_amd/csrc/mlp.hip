@@ -85,18 +85,21 @@ __device__ __forceinline__ void dw_store(const float (&r)[16], float* __restrict
 
 // Eight waves per workgroup, two per SIMD, specialised: waves 0-3 only multiply (64 MFMAs per stage from LDS, operands
 // ping-ponged so the LDS latency hides behind the previous four MFMAs), waves 4-7 only move data (global -> registers one
-// stage ahead, registers -> the other LDS buffer).  One barrier per stage; the movers' ~1000 cycles of address
-// arithmetic, predicated loads and LDS writes run on the issue slots the 4096-cycle MFMA stream leaves free, instead of
-// in front of it (a single-role kernel measured 58 % of the f32 MFMA peak in its main loop for exactly that reason).
+// stage ahead, registers -> the other LDS buffer).  One barrier per stage; the movers' work runs beside the 4096-cycle
+// MFMA stream instead of in front of it (a single-role kernel measured 58 % of the f32 MFMA peak in its main loop for
+// exactly that reason).  It is not free there: a mover shares its SIMD with one multiplier wave and its VALU cycles come
+// off that wave's MFMA issue, so the steady state (dw_movers_steady) keeps only the result's own arithmetic in the loop.
+// The general path below (predicated per load) serves a ragged last stage and rows that are not 16-byte aligned.
+// `groups`: which of a thread's four row groups this workgroup stores (16-byte form; see the Dout comment in the kernel).
 template <bool VEC>
 __device__ __forceinline__ void dw_store_global(const float (&r)[16], float* __restrict__ dst, int64_t ld, int64_t row0, int64_t row_end,
-                                                int col0, int ncols, int t) {
+                                                int col0, int ncols, int t, unsigned groups) {
     if (VEC) {
         const int c = col0 + 4 * (t & 31);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int64_t row = row0 + (t >> 5) + 8 * i;
-            if (row < row_end && c < ncols)
+            if (((groups >> i) & 1u) && row < row_end && c < ncols)
                 *reinterpret_cast<float4*>(dst + row * ld + c) = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
         }
     } else {
@@ -106,6 +109,89 @@ __device__ __forceinline__ void dw_store_global(const float (&r)[16], float* __r
             const int64_t row = row0 + (t >> 7) + 2 * i;
             if (row < row_end && c < ncols) dst[row * ld + c] = r[i];
         }
+    }
+}
+
+// The movers' steady state (16-byte rows, every stage of the split a full 32 rows).  Only the row base moves from stage to stage, so
+// each operand gets a buffer descriptor of the split's rows, the stage's byte offset advances once per stage in a scalar register and
+// a lane's own part -- its row of the group and its column -- is a loop-invariant 32-bit offset: no 64-bit vector add per load, no
+// row or column compare in the loop.  A lane whose vector lies past the row re-reads the row's last vector: a dY column >= N only
+// reaches partial rows >= N and bias sums >= N, an X column >= K only partial columns >= K, and none of those is stored.  The Dout
+// stores keep their column guard.  Same loads, same arithmetic, same order as the general path.
+typedef float dw_f4 __attribute__((ext_vector_type(4)));
+typedef unsigned dw_u4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t dw_rsrc(const float* p, int64_t rows, int64_t ld, int ncols) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, (int)(((rows - 1) * ld + ncols) * 4), 0x00020000);
+}
+
+template <bool ACT>
+__device__ __forceinline__ void dw_movers_steady(const DwArgs& a, float* __restrict__ sY, float* __restrict__ sX, int t, int n0, int k0,
+                                                 int64_t m_begin, int nst, bool want_db, unsigned dgroups, float (&dbv)[4]) {
+    const int cl = 4 * (t & 31), rr = t >> 5;
+    const int kv = (a.K + 3) & ~3;  // X rows are read in whole vectors: the pitch covers the last one
+    const int rows = nst * DW_BM;
+    const int oy = (int)((rr * a.ldy + min(n0 + cl, a.N - 4)) * 4);
+    const int ox = (int)((rr * a.ldx + min(k0 + cl, kv - 4)) * 4);
+    const int oh = ACT ? (int)((rr * a.ldh + min(n0 + cl, a.N - 4)) * 4) : 0;
+    const int od = ACT ? (int)((rr * a.ldd + n0 + cl) * 4) : 0;
+    const bool d_ok = n0 + cl < a.N;
+    const __amdgpu_buffer_rsrc_t by = dw_rsrc(a.dY + m_begin * a.ldy, rows, a.ldy, a.N);
+    const __amdgpu_buffer_rsrc_t bx = dw_rsrc(a.X + m_begin * a.ldx, rows, a.ldx, kv);
+    const __amdgpu_buffer_rsrc_t bh = dw_rsrc(ACT ? a.H + m_begin * a.ldh : a.dY, rows, ACT ? a.ldh : a.ldy, a.N);
+    const __amdgpu_buffer_rsrc_t bd = dw_rsrc(ACT && dgroups != 0u ? a.Dout + m_begin * a.ldd : a.dY, rows, ACT ? a.ldd : a.ldy, a.N);
+    const int gy = (int)(32 * a.ldy), gx = (int)(32 * a.ldx), gh = (int)(32 * a.ldh), gd = (int)(32 * a.ldd);  // bytes between a thread's row groups (8 rows)
+    int sy = 0, sx = 0, sh = 0, sd = 0;  // byte offset of the stage to load next / to store next (wave-uniform)
+    dw_f4 ry[4], rx[4], rh[ACT ? 4 : 1];
+    auto load = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ry[i] = __builtin_bit_cast(dw_f4, __builtin_amdgcn_raw_buffer_load_b128(by, oy, sy + i * gy, 0));
+        if constexpr (ACT) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) rh[i] = __builtin_bit_cast(dw_f4, __builtin_amdgcn_raw_buffer_load_b128(bh, oh, sh + i * gh, 0));
+            sh += 4 * gh;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rx[i] = __builtin_bit_cast(dw_f4, __builtin_amdgcn_raw_buffer_load_b128(bx, ox, sx + i * gx, 0));
+        sy += 4 * gy;
+        sx += 4 * gx;
+    };
+    auto store = [&](int buf) __attribute__((always_inline)) {
+        if constexpr (ACT) {  // gradient through ELU from its saved output: y > 0 ? 1 : y + alpha
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) ry[i][j] *= rh[i][j] > 0.0f ? 1.0f : rh[i][j] + a.alpha;
+            if (dgroups != 0u) {
+                if (d_ok) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if ((dgroups >> i) & 1u) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(dw_u4, ry[i]), bd, od, sd + i * gd, 0);
+                }
+                sd += 4 * gd;
+            }
+        }
+        float* py = sY + buf * (DW_BM * DW_LD) + rr * DW_LD + cl;
+        float* px = sX + buf * (DW_BM * DW_LD) + rr * DW_LD + cl;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<dw_f4*>(py + 8 * i * DW_LD) = ry[i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<dw_f4*>(px + 8 * i * DW_LD) = rx[i];
+        if (want_db) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { dbv[0] += ry[i][0]; dbv[1] += ry[i][1]; dbv[2] += ry[i][2]; dbv[3] += ry[i][3]; }
+        }
+    };
+    load();  // (nst >= 1 here)
+    store(0);
+    if (nst > 1) load();
+    __syncthreads();  // stage 0 is in LDS
+    for (int st = 0; st < nst; ++st) {
+        if (st + 1 < nst) {
+            store((st + 1) & 1);  // that buffer was last read in stage st-1: every wave is past that barrier
+            if (st + 2 < nst) load();
+        }
+        __syncthreads();
     }
 }
 
@@ -136,7 +222,25 @@ __global__ void __launch_bounds__(512, 1) k_mlp_dw(DwArgs a) {
         float ry[16], rx[16], rh[ACT ? 16 : 1];
         float dbv[4] = {0.f, 0.f, 0.f, 0.f};  // column sums of the dY slab (YVEC: 4 columns x rows t>>5 + 8i; else 1 column)
         int64_t loaded_row0 = 0;
-        const bool write_d = ACT && a.Dout != nullptr && (tile % a.tk) == 0;
+        // Dout: the tk column tiles of an N-slab all hold the product; the 16-byte form spreads a thread's four row groups over them
+        // (group i goes with tile i % tk) so the stores do not pile on the workgroup that also carries the bias sums
+        unsigned dgroups = 0u;
+        if (ACT && a.Dout != nullptr) {
+            if (YVEC) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) dgroups |= (i % a.tk) == (tile % a.tk) ? 1u << i : 0u;
+            } else if ((tile % a.tk) == 0) {
+                dgroups = 15u;
+            }
+        }
+        const bool write_d = dgroups != 0u;
+        bool steady = false;
+        if constexpr (YVEC && XVEC) {
+            int64_t ld = std::max(a.ldy, a.ldx);
+            if (ACT) ld = std::max(ld, std::max(a.ldh, a.ldd));
+            steady = nst > 0 && (m_end - m_begin) % DW_BM == 0 && a.rps * ld < ((int64_t)1 << 28);  // a split's byte offsets fit 31 bits
+            if (steady) dw_movers_steady<ACT>(a, &sY[0][0], &sX[0][0], t, n0, k0, m_begin, nst, want_db, dgroups, dbv);
+        }
         auto load = [&](int st) {
             const int64_t row0 = m_begin + (int64_t)st * DW_BM;  // rows >= m_end load as zeros
             loaded_row0 = row0;
@@ -148,7 +252,7 @@ __global__ void __launch_bounds__(512, 1) k_mlp_dw(DwArgs a) {
             if constexpr (ACT) {  // gradient through ELU from its saved output: y > 0 ? 1 : y + alpha
 #pragma unroll
                 for (int q = 0; q < 16; ++q) ry[q] *= rh[q] > 0.0f ? 1.0f : rh[q] + a.alpha;
-                if (write_d) dw_store_global<YVEC>(ry, a.Dout, a.ldd, loaded_row0, m_end, n0, a.N, t);
+                if (write_d) dw_store_global<YVEC>(ry, a.Dout, a.ldd, loaded_row0, m_end, n0, a.N, t, dgroups);
             }
             dw_store<YVEC>(ry, sY[buf], t);
             dw_store<XVEC>(rx, sX[buf], t);
@@ -162,18 +266,20 @@ __global__ void __launch_bounds__(512, 1) k_mlp_dw(DwArgs a) {
                 }
             }
         };
-        if (nst > 0) {
-            load(0);
-            store(0);
-            if (nst > 1) load(1);
-        }
-        __syncthreads();  // stage 0 is in LDS
-        for (int st = 0; st < nst; ++st) {
-            if (st + 1 < nst) {
-                store((st + 1) & 1);  // that buffer was last read in stage st-1: every wave is past that barrier
-                if (st + 2 < nst) load(st + 2);
+        if (!steady) {
+            if (nst > 0) {
+                load(0);
+                store(0);
+                if (nst > 1) load(1);
             }
-            __syncthreads();
+            __syncthreads();  // stage 0 is in LDS
+            for (int st = 0; st < nst; ++st) {
+                if (st + 1 < nst) {
+                    store((st + 1) & 1);  // that buffer was last read in stage st-1: every wave is past that barrier
+                    if (st + 2 < nst) load(st + 2);
+                }
+                __syncthreads();
+            }
         }
         if (want_db) {  // fixed-order sum of the row groups through LDS (the tile buffers are free now)
             float* red = sY[0];

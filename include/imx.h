@@ -597,8 +597,8 @@ const char* imx_version(void);
 /* sizeof of an ABI struct as this library was compiled (which: 0 imx_state_t, 1 imx_buffers_t, 2 imx_head_loss_t, 3 imx_rollout_slot_t, 4 imx_policy_act_t, 5 imx_orch_t, 6 imx_event_term_t,
  * 7 imx_diff_ik_t, 8 imx_osc_t, 10 imx_orch_manip_t, 11 imx_weight_term_t, 12 imx_pretrained_policy_t,
  * 13 imx_pose2d_command_t, 15 imx_inhand_command_t, 16 imx_object_state_t, 18 imx_articulation_state_t,
- * 20 imx_orch_articulation_t), 0 for an unknown index
- * (9, 14, 17 and 19 are):
+ * 20 imx_orch_articulation_t, 22 imx_norm_group_t, 23 imx_infer_norm_t), 0 for an unknown index
+ * (9, 14, 17, 19 and 21 are):
  * a binding checks its own layout against it at load time. */
 size_t imx_struct_size(int which);
 const char* imx_last_error(void);
@@ -880,6 +880,20 @@ int imx_actuator_net_mlp(int64_t N, int64_t J, int num_dense, const int32_t* den
 int imx_empirical_normalization(int64_t N, int64_t D, const float* x_d, int update, float eps, float* mean_d, float* var_d,
                                 float* std_d, int64_t* count_d, float* out_d, imx_stream_t stream);
 
+/* The statistics half of EmpiricalNormalization.forward alone, for one or two normalisers in TWO wide launches (the fused rollout:
+ * the rows are normalised where they are read, imx_mlp_infer_act2n).  Launch A: row slabs x 64-column blocks of every group in one grid,
+ * each workgroup leaves its slab's (mean, M2) per column in partials_d (two-pass within the slab, the four waves merged in a fixed
+ * order; no atomics).  Launch B: one workgroup per group merges the slabs in slab order (Chan), applies the running update of
+ * imx_empirical_normalization (rate from the exact integer count) and, after a workgroup barrier, stores count + N.  Both launches read
+ * count_d on the device and do nothing when until >= 0 && count >= until (upstream's `until` gate without a host round trip: a captured
+ * rollout keeps it).  Results depend on (N, D, ldx) only. */
+typedef struct imx_norm_group imx_norm_group_t;
+typedef struct imx_infer_norm imx_infer_norm_t;
+#include "imx_normalization_struct.h" /* the definitions of imx_norm_group_t (struct-size index 22) and imx_infer_norm_t (23) */
+size_t imx_empirical_normalization_partials_bytes(int64_t N, int64_t D);
+/* groups: HOST array of ngroups (1 or 2) entries.  A refused argument is named in imx_last_error and nothing is launched. */
+int imx_empirical_normalization_update(int ngroups, const imx_norm_group_t* groups, imx_stream_t stream);
+
 /* ---- actor / critic MLP inside PPO.update (rsl_rl v2.3.1 ppo.py::update `loss.backward()` through the nn.Linear / nn.ELU
  * stacks of actor_critic.py; 3rd party, absent: PARITY UNPINNED, checked against torch autograd).  fp32 on the f32 MFMA.
  * The wide forward / dX GEMMs stay library calls; these are the shapes a library GEMM handles badly. */
@@ -969,6 +983,15 @@ int imx_mlp_infer_act2(int64_t M, const float* const* X_d, const int64_t* ldx, i
                        const float* const* weights_d, const int* weight_pitch, const float* const* packed_weights_d,
                        const float* const* biases_d, const float* elu_alpha, float* const* out_d, const imx_policy_act_t* act,
                        float* critic_obs_out_d, imx_stream_t stream);
+/* imx_mlp_infer_act2 that normalises its input rows where it loads them (EmpiricalNormalization in the fused rollout): every element of
+ * network k's rows becomes (x - mean_d[c]) / (std_d[c] + eps) -- the expression of imx_empirical_normalization, a true division -- before
+ * it goes to LDS and to act->obs_out_d / critic_obs_out_d, so outputs and stored rows are bit-identical to an apply launch followed by
+ * imx_mlp_infer_act2.  norm: HOST array of nnets entries; an entry whose mean_d and std_d are both NULL leaves that network's rows as
+ * they are.  An env without a critic group passes the policy rows and the policy statistics for both networks. */
+int imx_mlp_infer_act2n(int64_t M, const float* const* X_d, const int64_t* ldx, int nnets, const int* nlayers, const int* dims,
+                        const float* const* weights_d, const int* weight_pitch, const float* const* packed_weights_d,
+                        const float* const* biases_d, const float* elu_alpha, float* const* out_d, const imx_policy_act_t* act,
+                        float* critic_obs_out_d, const imx_infer_norm_t* norm, imx_stream_t stream);
 /* Floats of the packed image of an (out_features x in_features) nn.Linear weight (both rounded up to multiples of 32), and the packing
  * itself (W_d row-major with row pitch ldw >= in_features; packed_d 16-byte aligned; to be repeated whenever the weights change). */
 size_t imx_mlp_packed_floats(int out_features, int in_features);

@@ -185,5 +185,9 @@ try:
     ORCH_ARTICULATION_HEADER = os.path.join(os.path.dirname(HEADER), "imx_orch_articulation.h")
     with open(ORCH_ARTICULATION_HEADER) as _f:
         _, _, ORCH_ARTICULATION_STRUCTS, _ = parse(_f.read(), ORCH_ARTICULATION_HEADER, DEFINES)
+    # imx_normalization_struct.h, likewise: imx_norm_group_t (imx_empirical_normalization_update), imx_infer_norm_t (imx_mlp_infer_act2n)
+    NORMALIZATION_HEADER = os.path.join(os.path.dirname(HEADER), "imx_normalization_struct.h")
+    with open(NORMALIZATION_HEADER) as _f:
+        _, _, NORMALIZATION_STRUCTS, _ = parse(_f.read(), NORMALIZATION_HEADER, DEFINES)
 except OSError as e:
     raise AbiError(f"the ABI header {HEADER} cannot be read ({e}): the whole binding is derived from it") from e

@@ -106,6 +106,11 @@ ARTICULATION_STATE_FIELDS = tuple(field for field, _ in ImxArticulationState._fi
 # (imx_orch_articulation.h, the same way)
 ImxOrchArticulation = type("ImxOrchArticulation", (ctypes.Structure,), {"_fields_": [(field, _abi.ctype(t, _STRUCTS))
                                                                                     for field, t in _abi.ORCH_ARTICULATION_STRUCTS["imx_orch_articulation_t"]]})
+# (imx_normalization_struct.h, the same way)
+ImxNormGroup = type("ImxNormGroup", (ctypes.Structure,), {"_fields_": [(field, _abi.ctype(t, _STRUCTS))
+                                                                      for field, t in _abi.NORMALIZATION_STRUCTS["imx_norm_group_t"]]})
+ImxInferNorm = type("ImxInferNorm", (ctypes.Structure,), {"_fields_": [(field, _abi.ctype(t, _STRUCTS))
+                                                                      for field, t in _abi.NORMALIZATION_STRUCTS["imx_infer_norm_t"]]})
 FRAME_WORDS = _abi.DEFINES["IMX_FRAME_WORDS"]
 FT_HEADER_WORDS = _abi.DEFINES["IMX_FT_HEADER_WORDS"]
 if set(_STRUCTS) != set(_abi.STRUCTS):
@@ -123,7 +128,8 @@ _lib = None
 _BY_POINTER = {**_STRUCTS, "imx_pretrained_policy_t": ImxPretrainedPolicy, "imx_pose2d_command_t": ImxPose2dCommand,
                "imx_inhand_command_t": ImxInhandCommand, "imx_object_state_t": ImxObjectState,
                "imx_articulation_state_t": ImxArticulationState,
-               "imx_orch_articulation_t": ImxOrchArticulation}  # (a struct of an included header travels as POINTER(class) too)
+               "imx_orch_articulation_t": ImxOrchArticulation, "imx_norm_group_t": ImxNormGroup,
+               "imx_infer_norm_t": ImxInferNorm}  # (a struct of an included header travels as POINTER(class) too)
 _SIGNATURES = {name: (_abi.ctype(res, _BY_POINTER, ret=True), [_abi.ctype(t, _BY_POINTER) for t in args])
                for name, (res, args, _) in _abi.FUNCTIONS.items()}
 EXPORTS = tuple(_SIGNATURES)
@@ -152,7 +158,8 @@ def lib():
         fn.argtypes = args
     for which, cls in (*enumerate((ImxState, ImxBuffers, ImxHeadLoss, ImxRolloutSlot, ImxPolicyAct, ImxOrch, ImxEventTerm, ImxDiffIk, ImxOsc)),
                        (10, ImxOrchManip), (11, ImxWeightTerm), (12, ImxPretrainedPolicy), (13, ImxPose2dCommand), (15, ImxInhandCommand), (16, ImxObjectState),
-                       (18, ImxArticulationState), (20, ImxOrchArticulation)):  # the binding's struct layouts against the library's (indices 9, 14, 17 and 19 are unknown)
+                       (18, ImxArticulationState), (20, ImxOrchArticulation), (22, ImxNormGroup),
+                       (23, ImxInferNorm)):  # the binding's struct layouts against the library's (indices 9, 14, 17, 19 and 21 are unknown)
         if int(L.imx_struct_size(which)) != ctypes.sizeof(cls):
             raise ImxError(f"{LIB_PATH}: sizeof({cls.__name__}) is {int(L.imx_struct_size(which))} in the library, {ctypes.sizeof(cls)} in the "
                            "binding -- rebuild with `python -m isaaclab_amd.build`")

@@ -22,7 +22,7 @@ def _stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h) for h in ("imx.h", "imx_osc_struct.h", "imx_orch_manip.h", "imx_pretrained_policy_struct.h", "imx_pose2d_struct.h", "imx_inhand_command_struct.h", "imx_object_state.h", "imx_articulation_state.h", "imx_orch_articulation.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h) for h in ("imx.h", "imx_osc_struct.h", "imx_orch_manip.h", "imx_pretrained_policy_struct.h", "imx_pose2d_struct.h", "imx_inhand_command_struct.h", "imx_object_state.h", "imx_articulation_state.h", "imx_orch_articulation.h", "imx_normalization_struct.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -41,6 +41,8 @@ extern "C" size_t imx_struct_size(int which) {
         case 16: return sizeof(imx_object_state_t);
         case 18: return sizeof(imx_articulation_state_t);
         case 20: return sizeof(imx_orch_articulation_t);
+        case 22: return sizeof(imx_norm_group_t);
+        case 23: return sizeof(imx_infer_norm_t);
         default: return 0;
     }
 }

@@ -1291,6 +1291,7 @@ __device__ __forceinline__ void act_epilogue(const ActArgs& c, const float* __re
 
 
 // (the kernel bodies are textual includes, see mlp_infer_body.inc: *_binary = for a plan with a binary joint term)
+#define IMX_INFER_NORMALIZE 0
 #define IMX_INFER_TWO_INPUTS 0
 template <bool PACKED>
 __global__ void __launch_bounds__(256, 1) k_mlp_infer(InferArgs a, ActArgs act) {
@@ -1350,6 +1351,41 @@ __global__ void __launch_bounds__(256, 2) k_mlp_infer2_16_binary(InferArgs a, Ac
 #include "mlp_infer16_body.inc"
 #undef IMX_ACT_BINARY
 }
+#undef IMX_INFER_NORMALIZE
+
+// imx_mlp_infer_act2n: the two-input bodies once more, normalising the rows between their load and the LDS / dense stores
+// (EmpiricalNormalization in the fused rollout: (x - mean[c]) / (std[c] + eps), k_norm_apply's expression under this library's
+// -fno-fast-math -ffp-contract=off, so everything downstream is bit-identical to an apply launch followed by k_mlp_infer2*).  Kernels of
+// their own again: the twelve above keep their instruction streams.
+struct InferNorm {
+    const float* mean[2];  // per network; null = that network's rows as they are
+    const float* stdv[2];
+    float eps[2];
+};
+#define IMX_INFER_NORMALIZE 1
+template <bool PACKED>
+__global__ void __launch_bounds__(256, 1) k_mlp_infer2n(InferArgs a, ActArgs act, InferTwo two, InferNorm nrm) {
+#define IMX_ACT_BINARY false
+#include "mlp_infer_body.inc"
+#undef IMX_ACT_BINARY
+}
+template <bool PACKED>
+__global__ void __launch_bounds__(256, 1) k_mlp_infer2n_binary(InferArgs a, ActArgs act, InferTwo two, InferNorm nrm) {
+#define IMX_ACT_BINARY true
+#include "mlp_infer_body.inc"
+#undef IMX_ACT_BINARY
+}
+__global__ void __launch_bounds__(256, 2) k_mlp_infer2n_16(InferArgs a, ActArgs act, InferTwo two, InferNorm nrm) {
+#define IMX_ACT_BINARY false
+#include "mlp_infer16_body.inc"
+#undef IMX_ACT_BINARY
+}
+__global__ void __launch_bounds__(256, 2) k_mlp_infer2n_16_binary(InferArgs a, ActArgs act, InferTwo two, InferNorm nrm) {
+#define IMX_ACT_BINARY true
+#include "mlp_infer16_body.inc"
+#undef IMX_ACT_BINARY
+}
+#undef IMX_INFER_NORMALIZE
 #undef IMX_INFER_TWO_INPUTS
 
 extern "C" int imx_mlp_infer(int64_t M, const float* X_d, int64_t ldx, int nnets, const int* nlayers, const int* dims,
@@ -1424,13 +1460,26 @@ extern "C" int imx_mlp_pack_weights(int out_features, int in_features, const flo
 static int mlp_infer_launch(bool two_inputs, int64_t M, const float* const* X, const int64_t* ldxs, int nnets, const int* nlayers, const int* dims,
                             const float* const* weights_d, const int* weight_pitch, const float* const* packed_weights_d,
                             const float* const* biases_d, const float* elu_alpha, float* const* out_d, const imx_policy_act_t* pa,
-                            float* critic_obs_out_d, imx_stream_t stream) {
+                            float* critic_obs_out_d, imx_stream_t stream, const imx_infer_norm_t* norm = nullptr, bool normalize = false) {
+    // normalize (imx_mlp_infer_act2n): two_inputs with one {mean, std, eps} per network; the checks it shares with imx_mlp_infer_act2
+    // answer under the name of the entry point that was called (fn)
+    const char* const fn = normalize ? "imx_mlp_infer_act2n" : "imx_mlp_infer_act2";
+    InferNorm nrm{};
+    if (normalize) {
+        IMX_REQUIRE(norm, "imx_mlp_infer_act2n: norm is null (one imx_infer_norm_t per network; both pointers null = rows as they are)");
+        IMX_REQUIRE(nnets >= 1 && nnets <= 2, "imx_mlp_infer_act2n: nnets = %d (1 or 2 networks)", nnets);
+        for (int k = 0; k < nnets; ++k) {
+            IMX_REQUIRE((norm[k].mean_d == nullptr) == (norm[k].std_d == nullptr),
+                        "imx_mlp_infer_act2n: norm[%d]: null statistics (%s is null, the other is not)", k, norm[k].mean_d ? "std_d" : "mean_d");
+            nrm.mean[k] = norm[k].mean_d; nrm.stdv[k] = norm[k].std_d; nrm.eps[k] = norm[k].eps;
+        }
+    }
     if (two_inputs) {
-        IMX_REQUIRE(M > 0 && nnets >= 1 && nnets <= 2, "imx_mlp_infer_act2: M = %lld, nnets = %d (M > 0 and 1 or 2 networks)", (long long)M, nnets);
+        IMX_REQUIRE(M > 0 && nnets >= 1 && nnets <= 2, "%s: M = %lld, nnets = %d (M > 0 and 1 or 2 networks)", fn, (long long)M, nnets);
         IMX_REQUIRE(X && ldxs && nlayers && dims && weights_d && biases_d && elu_alpha && out_d,
-                    "imx_mlp_infer_act2: a null array among X_d, ldx, nlayers, dims, weights_d, biases_d, elu_alpha, out_d");
-        IMX_REQUIRE(!critic_obs_out_d || nnets == 2, "imx_mlp_infer_act2: critic_obs_out_d given with nnets == %d (network 1's rows: it needs 2)", nnets);
-        for (int k = 0; k < nnets; ++k) IMX_REQUIRE(X[k], "imx_mlp_infer_act2: X_d[%d] is null", k);
+                    "%s: a null array among X_d, ldx, nlayers, dims, weights_d, biases_d, elu_alpha, out_d", fn);
+        IMX_REQUIRE(!critic_obs_out_d || nnets == 2, "%s: critic_obs_out_d given with nnets == %d (network 1's rows: it needs 2)", fn, nnets);
+        for (int k = 0; k < nnets; ++k) IMX_REQUIRE(X[k], "%s: X_d[%d] is null", fn, k);
     } else {
         IMX_REQUIRE(M > 0 && X[0] && nnets >= 1 && nnets <= 2 && nlayers && dims && weights_d && biases_d && elu_alpha && out_d,
                     "imx_mlp_infer: bad arguments");
@@ -1470,12 +1519,12 @@ static int mlp_infer_launch(bool two_inputs, int64_t M, const float* const* X, c
         for (int l = 0; l <= n.nlayers; ++l) {
             n.dim[l] = dims[di++];
             if (two_inputs)
-                IMX_REQUIRE(n.dim[l] >= 1 && n.dim[l] <= INF_MAXD, "imx_mlp_infer_act2: dims: width %d of network %d (layer %d) outside 1..%d",
+                IMX_REQUIRE(n.dim[l] >= 1 && n.dim[l] <= INF_MAXD, "%s: dims: width %d of network %d (layer %d) outside 1..%d", fn,
                             n.dim[l], k, l, INF_MAXD);
             IMX_REQUIRE(n.dim[l] >= 1 && n.dim[l] <= INF_MAXD, "imx_mlp_infer: layer width %d outside 1..%d", n.dim[l], INF_MAXD);
         }
         if (two_inputs)
-            IMX_REQUIRE(ldxs[k] >= n.dim[0], "imx_mlp_infer_act2: ldx[%d] = %lld is less than the input width %d of network %d",
+            IMX_REQUIRE(ldxs[k] >= n.dim[0], "%s: ldx[%d] = %lld is less than the input width %d of network %d", fn,
                         k, (long long)ldxs[k], n.dim[0], k);
         else
             IMX_REQUIRE(n.dim[0] == a.net[0].dim[0] && ldx >= n.dim[0], "imx_mlp_infer: the networks must share the input (width %d, pitch %lld)",
@@ -1485,7 +1534,7 @@ static int mlp_infer_launch(bool two_inputs, int64_t M, const float* const* X, c
             n.Wp[l] = packed_weights_d ? packed_weights_d[wi] : nullptr;
             if (two_inputs)
                 IMX_REQUIRE(!packed_weights_d || (n.Wp[l] && aligned16(n.Wp[l])),
-                            "imx_mlp_infer_act2: packed_weights_d[%d] is null or not 16-byte aligned (network %d, layer %d)", wi, k, l);
+                            "%s: packed_weights_d[%d] is null or not 16-byte aligned (network %d, layer %d)", fn, wi, k, l);
             IMX_REQUIRE(!packed_weights_d || (n.Wp[l] && aligned16(n.Wp[l])), "imx_mlp_infer: null / unaligned packed weights (network %d, layer %d)", k, l);
             n.b[l] = biases_d[wi];
             n.ldw[l] = weight_pitch ? weight_pitch[wi] : n.dim[l];
@@ -1527,6 +1576,30 @@ static int mlp_infer_launch(bool two_inputs, int64_t M, const float* const* X, c
         }
         InferTwo two{};
         if (nnets == 2) { two.X1 = X[1]; two.ldx1 = ldxs[1]; two.obs_out1 = critic_obs_out_d; }
+        if (normalize) {  // the same choice once more, among the normalising kernels
+            static bool attr2n_set = false;
+            if (!attr2n_set) {
+                const void* big[] = {reinterpret_cast<const void*>(k_mlp_infer2n<false>), reinterpret_cast<const void*>(k_mlp_infer2n<true>),
+                                     reinterpret_cast<const void*>(k_mlp_infer2n_binary<false>), reinterpret_cast<const void*>(k_mlp_infer2n_binary<true>)};
+                for (const void* f : big) IMX_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2ull * INF_ROWS * INF_PITCH * sizeof(float))));
+                const void* small16[] = {reinterpret_cast<const void*>(k_mlp_infer2n_16), reinterpret_cast<const void*>(k_mlp_infer2n_16_binary)};
+                for (const void* f : small16) IMX_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2ull * INF16_ROWS * INF_PITCH * sizeof(float))));
+                attr2n_set = true;
+            }
+            if (small) {
+                a.tiles = (int)((M + INF16_ROWS - 1) / INF16_ROWS);
+                hipLaunchKernelGGL(binary ? k_mlp_infer2n_16_binary : k_mlp_infer2n_16, dim3((unsigned)(a.tiles * nnets)), bs,
+                                   2ull * INF16_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act, two, nrm);
+            } else if (packed_weights_d) {
+                hipLaunchKernelGGL(binary ? k_mlp_infer2n_binary<true> : k_mlp_infer2n<true>, dim3((unsigned)(a.tiles * nnets)), bs,
+                                   2ull * INF_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act, two, nrm);
+            } else {
+                hipLaunchKernelGGL(binary ? k_mlp_infer2n_binary<false> : k_mlp_infer2n<false>, dim3((unsigned)(a.tiles * nnets)), bs,
+                                   2ull * INF_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act, two, nrm);
+            }
+            IMX_HIP(hipGetLastError());
+            return 0;
+        }
         if (small) {
             a.tiles = (int)((M + INF16_ROWS - 1) / INF16_ROWS);
             hipLaunchKernelGGL(binary ? k_mlp_infer2_16_binary : k_mlp_infer2_16, dim3((unsigned)(a.tiles * nnets)), bs,
@@ -1570,4 +1643,12 @@ extern "C" int imx_mlp_infer_act2(int64_t M, const float* const* X_d, const int6
                                   float* critic_obs_out_d, imx_stream_t stream) {
     return mlp_infer_launch(true, M, X_d, ldx, nnets, nlayers, dims, weights_d, weight_pitch, packed_weights_d, biases_d, elu_alpha, out_d, act,
                             critic_obs_out_d, stream);
+}
+
+extern "C" int imx_mlp_infer_act2n(int64_t M, const float* const* X_d, const int64_t* ldx, int nnets, const int* nlayers, const int* dims,
+                                   const float* const* weights_d, const int* weight_pitch, const float* const* packed_weights_d,
+                                   const float* const* biases_d, const float* elu_alpha, float* const* out_d, const imx_policy_act_t* act,
+                                   float* critic_obs_out_d, const imx_infer_norm_t* norm, imx_stream_t stream) {
+    return mlp_infer_launch(true, M, X_d, ldx, nnets, nlayers, dims, weights_d, weight_pitch, packed_weights_d, biases_d, elu_alpha, out_d, act,
+                            critic_obs_out_d, stream, norm, true);
 }

@@ -27,6 +27,18 @@
     {
         const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
         float v[4][INF_MAXD / 64];  // wave w: rows w, w+4, w+8, w+12; all loads before the first LDS store
+#if IMX_INFER_NORMALIZE
+        // (k_mlp_infer2n_16*: as in mlp_infer_body.inc)
+        const float* const n_mean = nrm.mean[which];
+        const float* const n_std = nrm.stdv[which];
+        float nmu[INF_MAXD / 64], nsd[INF_MAXD / 64];
+#pragma unroll
+        for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
+            const int c = lane + 64 * cc;
+            nmu[cc] = n_mean ? n_mean[c < K0 ? c : 0] : 0.0f;
+            nsd[cc] = n_mean ? n_std[c < K0 ? c : 0] : 1.0f;
+        }
+#endif
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
             const int row = w + 4 * rr;
@@ -38,6 +50,20 @@
                 v[rr][cc] = (c < K0 && m0 + row < a.M) ? x : 0.0f;
             }
         }
+#if IMX_INFER_NORMALIZE
+        if (n_mean) {
+            const float n_eps = nrm.eps[which];
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int row = w + 4 * rr;
+#pragma unroll
+                for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
+                    const int c = lane + 64 * cc;
+                    if (c < K0 && m0 + row < a.M) v[rr][cc] = (v[rr][cc] - nmu[cc]) / (nsd[cc] + n_eps);
+                }
+            }
+        }
+#endif
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
             const int row = w + 4 * rr;

@@ -1,6 +1,7 @@
 // The body of k_mlp_infer / k_mlp_infer_binary (mlp.hip), included once per kernel with IMX_ACT_BINARY = false (the kernel as it always was) or true (the actor
 // head's epilogue with the binary joint term's path).  A textual include, not a device function: the existing kernels then compile to the
-// instruction streams they had.  Also the body of k_mlp_infer2 / k_mlp_infer2_binary (IMX_INFER_TWO_INPUTS = 1, below).
+// instruction streams they had.  Also the body of k_mlp_infer2 / k_mlp_infer2_binary (IMX_INFER_TWO_INPUTS = 1, below) and of
+// k_mlp_infer2n / k_mlp_infer2n_binary (IMX_INFER_NORMALIZE = 1 on top of it: the rows are normalised between load and LDS store).
     extern __shared__ float smem[];  // two activation buffers of INF_ROWS x INF_PITCH floats
     float* buf0 = smem;
     float* buf1 = smem + INF_ROWS * INF_PITCH;
@@ -34,6 +35,18 @@
         const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
         const int ncc = (K0 + 63) >> 6;  // (uniform)
         float v[8][INF_MAXD / 64];
+#if IMX_INFER_NORMALIZE
+        // (k_mlp_infer2n*, argument `nrm`) the lane's mean / std of its columns ride in the tile's load batch; a null pair (uniform): rows as they are
+        const float* const n_mean = nrm.mean[which];
+        const float* const n_std = nrm.stdv[which];
+        float nmu[INF_MAXD / 64], nsd[INF_MAXD / 64];
+#pragma unroll
+        for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
+            const int c = lane + 64 * cc;
+            nmu[cc] = (n_mean && cc < ncc) ? n_mean[c < K0 ? c : 0] : 0.0f;
+            nsd[cc] = (n_mean && cc < ncc) ? n_std[c < K0 ? c : 0] : 1.0f;
+        }
+#endif
 #pragma unroll
         for (int rr = 0; rr < 8; ++rr) {
             const int row = w + 4 * rr;
@@ -49,6 +62,20 @@
                 }
             }
         }
+#if IMX_INFER_NORMALIZE
+        if (n_mean) {  // k_norm_apply's expression (a true division): LDS and the dense store get what an apply launch would have left
+            const float n_eps = nrm.eps[which];
+#pragma unroll
+            for (int rr = 0; rr < 8; ++rr) {
+                const int row = w + 4 * rr;
+#pragma unroll
+                for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
+                    const int c = lane + 64 * cc;
+                    if (c < K0 && m0 + row < a.M) v[rr][cc] = (v[rr][cc] - nmu[cc]) / (nsd[cc] + n_eps);  // (padding and rows past M stay zero)
+                }
+            }
+        }
+#endif
 #pragma unroll
         for (int rr = 0; rr < 8; ++rr) {
             const int row = w + 4 * rr;

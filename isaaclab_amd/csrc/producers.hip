@@ -300,6 +300,133 @@ extern "C" int imx_empirical_normalization(int64_t N, int64_t D, const float* x_
     return 0;
 }
 
+// imx_empirical_normalization_update: the statistics alone, as two wide launches, for one or two normalisers (the fused rollout
+// normalises where the inference launch loads its rows).  k_norm_update above walks N / 4 rows twice per thread on D / 64 workgroups;
+// here a batch is cut into at most 64 row slabs (64 slabs of 64 rows at N = 4096: 256 workgroups for 235 columns) and every
+// (slab, 64-column block) workgroup leaves that slab's mean and M2 = sum (x - mean)^2 per column: two passes within the slab, the first
+// about the slab's first row (the shifted sum of k_norm_update, for the reason given there), the four waves merged in a fixed order.
+// k_norm_finalize, one workgroup per normaliser, merges the slabs in slab order -- the batch mean again as slab 0's mean plus the
+// weighted mean of the differences to it, so a mean of 1e3 is rounded once, not once per slab -- and applies k_norm_update's running
+// update.  One workgroup per normaliser is what lets it read `count` and, behind a barrier, store count + N in the same launch.  Both
+// kernels read `count` themselves and do nothing once it reached `until`: upstream's gate, on the device.  No atomics, no grid barrier.
+constexpr int NORM_MAX_SLABS = 64, NORM_MIN_SLAB_ROWS = 16;
+struct NormGroup {
+    int64_t N, ldx, until;
+    const float* x;
+    float *mean, *var, *stdv, *part;
+    int64_t* count;
+    int D, slab_rows, nslabs, ncb;  // ncb: 64-column blocks; part: [nslabs][2][ncb * 64]
+};
+struct NormArgs {
+    NormGroup g[2];
+    int n, blocks0;  // blocks0: workgroups of group 0 in k_norm_moments' grid
+};
+static int64_t norm_slab_rows(int64_t N) { return std::max<int64_t>((N + NORM_MAX_SLABS - 1) / NORM_MAX_SLABS, NORM_MIN_SLAB_ROWS); }
+
+__global__ void __launch_bounds__(256) k_norm_moments(NormArgs a) {
+    __shared__ float s_sum[4][64], s_sq[4][64];
+    const int gi = (a.n == 2 && (int)blockIdx.x >= a.blocks0) ? 1 : 0;
+    const NormGroup& g = a.g[gi];
+    if (g.until >= 0 && g.count[0] >= g.until) return;  // (uniform)
+    const int b = (int)blockIdx.x - (gi ? a.blocks0 : 0);
+    const int slab = b / g.ncb, cb = b - slab * g.ncb;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = cb * 64 + lane;
+    const bool on = c < g.D;
+    const int64_t r0 = (int64_t)slab * g.slab_rows, r1 = r0 + g.slab_rows < g.N ? r0 + g.slab_rows : g.N;
+    const float n = (float)(r1 - r0);
+    const float* __restrict__ x = g.x;
+    const float piv = on ? x[r0 * g.ldx + c] : 0.0f;
+    float s = 0.0f;
+    if (on)
+        for (int64_t r = r0 + w; r < r1; r += 4) s += x[r * g.ldx + c] - piv;
+    s_sum[w][lane] = s;
+    __syncthreads();
+    const float m = piv + ((s_sum[0][lane] + s_sum[1][lane]) + (s_sum[2][lane] + s_sum[3][lane])) / n;
+    float q = 0.0f;
+    if (on)
+        for (int64_t r = r0 + w; r < r1; r += 4) { const float d = x[r * g.ldx + c] - m; q += d * d; }
+    s_sq[w][lane] = q;
+    __syncthreads();
+    if (w == 0 && on) {
+        const int64_t Dp = (int64_t)g.ncb * 64;
+        g.part[(int64_t)(2 * slab) * Dp + c] = m;
+        g.part[(int64_t)(2 * slab + 1) * Dp + c] = (s_sq[0][lane] + s_sq[1][lane]) + (s_sq[2][lane] + s_sq[3][lane]);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_norm_finalize(NormArgs a) {
+    const NormGroup& g = a.g[blockIdx.x];
+    const int64_t count = g.count[0];
+    if (g.until >= 0 && count >= g.until) return;  // (uniform)
+    const int64_t Dp = (int64_t)g.ncb * 64;
+    const float* __restrict__ part = g.part;
+    for (int c = threadIdx.x; c < g.D; c += blockDim.x) {
+        // batch mean about slab 0's, then M2 = sum of the slabs' own plus their means' spread about the batch mean (Chan, all slabs at once)
+        const float m0 = part[c];
+        float acc = 0.0f;
+        for (int s = 1; s < g.nslabs; ++s) {
+            const int64_t r0 = (int64_t)s * g.slab_rows, r1 = r0 + g.slab_rows < g.N ? r0 + g.slab_rows : g.N;
+            acc += (float)(r1 - r0) * (part[(int64_t)(2 * s) * Dp + c] - m0);
+        }
+        const float bm = m0 + acc / (float)g.N;
+        float M2 = 0.0f;
+        for (int s = 0; s < g.nslabs; ++s) {
+            const int64_t r0 = (int64_t)s * g.slab_rows, r1 = r0 + g.slab_rows < g.N ? r0 + g.slab_rows : g.N;
+            const float d = part[(int64_t)(2 * s) * Dp + c] - bm;
+            M2 += part[(int64_t)(2 * s + 1) * Dp + c] + (float)(r1 - r0) * (d * d);
+        }
+        const float bv = M2 / (float)g.N;
+        // (the running update of k_norm_update)
+        const float rate = (float)((double)g.N / (double)(count + g.N));
+        const float delta = bm - g.mean[c];
+        const float m_new = g.mean[c] + rate * delta;
+        const float v_new = g.var[c] + rate * (bv - g.var[c] + delta * (bm - m_new));
+        g.mean[c] = m_new;
+        g.var[c] = v_new;
+        g.stdv[c] = sqrtf(v_new);
+    }
+    __syncthreads();  // every thread of the one workgroup has read `count`
+    if (threadIdx.x == 0) g.count[0] = count + g.N;
+}
+
+extern "C" size_t imx_empirical_normalization_partials_bytes(int64_t N, int64_t D) {
+    if (N <= 0 || D <= 0) return 0;
+    const int64_t rows = norm_slab_rows(N);
+    return (size_t)((N + rows - 1) / rows) * 2 * (size_t)((D + 63) / 64 * 64) * sizeof(float);
+}
+
+extern "C" int imx_empirical_normalization_update(int ngroups, const imx_norm_group_t* groups, imx_stream_t stream) {
+    IMX_REQUIRE(ngroups >= 1 && ngroups <= 2, "imx_empirical_normalization_update: ngroups = %d (1 or 2 groups per call)", ngroups);
+    IMX_REQUIRE(groups, "imx_empirical_normalization_update: groups is null");
+    NormArgs a{};
+    a.n = ngroups;
+    int blocks = 0;
+    for (int k = 0; k < ngroups; ++k) {
+        const imx_norm_group_t& h = groups[k];
+        IMX_REQUIRE(h.N > 0 && h.N <= (1ll << 36) && h.D > 0 && h.D <= 65536, "imx_empirical_normalization_update: groups[%d]: N = %lld, D = %lld (N in 1..2^36, D in 1..65536)",
+                    k, (long long)h.N, (long long)h.D);
+        IMX_REQUIRE(h.x_d, "imx_empirical_normalization_update: groups[%d].x_d is null", k);
+        IMX_REQUIRE(h.ldx >= h.D, "imx_empirical_normalization_update: groups[%d].ldx = %lld is less than D = %lld", k, (long long)h.ldx, (long long)h.D);
+        IMX_REQUIRE(h.mean_d && h.var_d && h.std_d && h.count_d,
+                    "imx_empirical_normalization_update: groups[%d]: null statistics (mean_d, var_d, std_d, count_d)", k);
+        IMX_REQUIRE(h.partials_d, "imx_empirical_normalization_update: groups[%d].partials_d is null (imx_empirical_normalization_partials_bytes)", k);
+        NormGroup& g = a.g[k];
+        g.N = h.N; g.ldx = h.ldx; g.until = h.until; g.x = h.x_d;
+        g.mean = h.mean_d; g.var = h.var_d; g.stdv = h.std_d; g.part = h.partials_d; g.count = h.count_d;
+        g.D = (int)h.D;
+        g.slab_rows = (int)norm_slab_rows(h.N);
+        g.nslabs = (int)((h.N + g.slab_rows - 1) / g.slab_rows);
+        g.ncb = (int)((h.D + 63) / 64);
+        if (k == 0) a.blocks0 = g.nslabs * g.ncb;
+        blocks += g.nslabs * g.ncb;
+    }
+    hipLaunchKernelGGL(k_norm_moments, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_norm_finalize, dim3((unsigned)ngroups), dim3(256), 0, (hipStream_t)stream, a);
+    IMX_HIP(hipGetLastError());
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------- explicit actuator models
 // IdealPDActuator.compute (isaaclab/isaaclab/actuators/actuator_pd.py:184-199; ImplicitActuator.compute :115-145 evaluates the
 // same law for reporting): computed = kp*(q_des - q) + kd*(qd_des - qd) + ff; applied = clip(computed, +-effort_limit)

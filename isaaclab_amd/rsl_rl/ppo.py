@@ -203,14 +203,41 @@ class FusedInference:
             check(lib().imx_mlp_pack_weights_batch(*self._pack_args, _lib.current_stream(self._packed[0].device)))
 
     def __call__(self, x: torch.Tensor, *outs: torch.Tensor, act=None, critic_x: torch.Tensor | None = None,
-                 critic_obs_out: torch.Tensor | None = None):
+                 critic_obs_out: torch.Tensor | None = None, norm=None):
         """``act``: an ``ImxPolicyAct`` -- the actor's workgroups then also sample the action, write the transition into the storage
         slot it names and run the action through the env's action terms (``imx_mlp_infer_act``); ``outs[0]`` may be None then.
         ``critic_x``: the second network's rows, for a two-input instance and only for one; ``critic_obs_out``: a dense (M, critic
-        width) buffer that then receives them too (``storage.privileged_observations[t]``)."""
+        width) buffer that then receives them too (``storage.privileged_observations[t]``).  ``norm``: ``(policy normaliser or None,
+        critic normaliser or None)`` -- the rows are RAW and each network's are normalised with its ``EmpiricalNormalization``'s
+        statistics where the launch loads them (``imx_mlp_infer_act2n``; None = as they are); a shared-input instance hands both
+        networks the policy rows."""
         if x.stride(1) != 1 or x.shape[1] != self.in_features or any(o is not None and not o.is_contiguous() for o in outs):
             raise _lib.ImxError("imx_mlp_infer needs a row-major input and contiguous outputs")
         out_p = (self._ctypes.c_void_p * self._n)(*[None if o is None else o.data_ptr() for o in outs])
+        if norm is not None:
+            if len(norm) != 2:
+                raise _lib.ImxError("norm is (policy normaliser or None, critic normaliser or None)")
+            if self.two_inputs:
+                if critic_x is None:
+                    raise _lib.ImxError("a two-input FusedInference needs critic_x: its critic does not read the actor's rows")
+                if critic_x.stride(1) != 1 or critic_x.shape != (x.shape[0], self.critic_in_features):
+                    raise _lib.ImxError(f"critic_x must be row-major ({x.shape[0]}, {self.critic_in_features}), not {tuple(critic_x.shape)}")
+                if critic_obs_out is not None and (not critic_obs_out.is_contiguous() or critic_obs_out.shape != critic_x.shape):
+                    raise _lib.ImxError(f"critic_obs_out must be contiguous {tuple(critic_x.shape)}")
+            elif critic_x is not None or critic_obs_out is not None:
+                raise _lib.ImxError("critic_x / critic_obs_out given to a shared-input FusedInference: both networks read x")
+            cx = critic_x if self.two_inputs else x
+            for n, width in zip(norm[:self._n], (x.shape[1], cx.shape[1])):
+                if n is not None and (n._mean.shape[-1] != width or n._mean.device != x.device):
+                    raise _lib.ImxError(f"norm: a normaliser of {n._mean.shape[-1]} columns on {n._mean.device} for rows of {width} on {x.device}")
+            xs =(self._ctypes.c_void_p * 2)(x.data_ptr(), cx.data_ptr())
+            ld = (self._ctypes.c_int64 * 2)(x.stride(0), cx.stride(0))
+            triples = (_lib.ImxInferNorm * 2)(*[_lib.ImxInferNorm() if n is None else n.infer_norm() for n in norm])
+            check(lib().imx_mlp_infer_act2n(x.shape[0], xs, ld, self._n, self._nl, self._dims, self._w, self._pitch, self._wpk, self._b,
+                                            self._alpha, out_p, self._ctypes.byref(act) if act is not None else None,
+                                            None if critic_obs_out is None else critic_obs_out.data_ptr(), triples,
+                                            _lib.current_stream(x.device)))
+            return
         if self.two_inputs:
             if critic_x is None:
                 raise _lib.ImxError("a two-input FusedInference needs critic_x: its critic does not read the actor's rows")

@@ -154,9 +154,24 @@ class OnPolicyRunner:
                 and self.alg.policy.noise_std_type == "scalar"
                 and self.device.type == "cuda" and not self.empirical_normalization)
 
+    fuse_normalization = True  # False: an agent with empirical_normalization=True rolls out step by step in Python, as upstream does
+
+    def _fusable_normalized(self) -> bool:
+        """``_fusable()``'s conditions for an agent WITH ``empirical_normalization``, both normalisers in training mode: the fused
+        rollout then also keeps the statistics (two launches per step) and normalises inside the inference launch."""
+        from ..env import ManagerBasedRLEnv
+        from .vecenv_wrapper import RslRlVecEnvWrapper
+
+        return (isinstance(self.env, RslRlVecEnvWrapper) and isinstance(self.env.unwrapped, ManagerBasedRLEnv)
+                and self.alg.policy.noise_std_type == "scalar"
+                and self.device.type == "cuda" and self.empirical_normalization
+                and self.obs_normalizer.training and self.privileged_obs_normalizer.training)
+
     def _rollout(self):
         if self._fusable():
             return self._rollout_fused()
+        if self.fuse_normalization and self._fusable_normalized():
+            return self._rollout_fused(normalized=True)
         obs, privileged_obs = self._obs, self._privileged_obs
         for _ in range(self.num_steps_per_env):
             actions = self.alg.act(obs, privileged_obs)
@@ -186,8 +201,18 @@ class OnPolicyRunner:
 
     fuse_launches = True  # False: the round-2 split (imx_mlp_infer, imx_policy_act, imx_action_process, ..., imx_rollout_post: 6 launches per step)
 
-    def _rollout_fused(self):
-        """Per step THREE launches: ``imx_mlp_infer_act`` (both MLPs + PPO.act's sampling / log-prob / transition writes + the
+    def _rollout_fused(self, normalized: bool = False):
+        """``normalized`` (an agent with ``empirical_normalization``; upstream: ``obs = obs_normalizer(obs)`` after every env step, the
+        first observation of a run stays raw): FIVE launches per step.  After launch 3 the two statistics launches
+        (``imx_empirical_normalization_update``: the raw policy rows and, with a critic group, the raw critic rows in the same call;
+        the ``until`` gate is taken on the device); the next step's inference launch is ``imx_mlp_infer_act2n``, which normalises the
+        raw rows where it loads them and stores the normalised rows into the slot.  Step 0 reads ``self._obs`` as it is (raw on the
+        first rollout of a run, normalised afterwards) through the plain launch; after the last step one apply launch per group leaves
+        the normalised last rows (``last_obs`` / ``last_critic_obs``, the next rollout's step 0).  ``fuse_launches = False``: the same
+        order of operations as separate launches -- ``update_rows`` + ``apply`` after each env step -- with bit-identical results
+        (tests/test_rollout_normalized_gpu.py).
+
+        Per step THREE launches: ``imx_mlp_infer_act`` (both MLPs + PPO.act's sampling / log-prob / transition writes + the
         ActionManager's action processing in the actor head's epilogue), ``imx_terminations_rewards_rollout`` (terminations, rewards,
         resets + the wrapper's dones, the time-out bootstrap and the episode statistics into slot t) and ``imx_observations`` (+ the
         step tail and the log accumulation).  Every transition is written straight into its storage slot.  An env with a privileged
@@ -212,6 +237,21 @@ class OnPolicyRunner:
         obs = self._obs
         priv = self.privileged_obs_type  # a "critic" observation group: the critic reads it, the storage keeps it
         cobs = self._privileged_obs if priv is not None else obs
+        is_raw = False  # normalized: obs / cobs are the env's raw rows (a fused step left them; the next launch normalises on load)
+        if normalized:
+            from .normalizer import update_rows_together
+
+            onorm = self.obs_normalizer
+            cnorm = self.privileged_obs_normalizer if priv is not None else onorm  # no critic group: the critic reads the policy rows
+            advance = not self._graph_capturing  # (a capture pass runs nothing: collect() advances the host counts per replay)
+            if self._graph_capturing:
+                self._graph_normalized = True
+
+            def update_stats(o, c):
+                if priv is not None:
+                    update_rows_together((onorm, o), (cnorm, c), advance_host=advance)
+                else:
+                    onorm.update_rows(o, advance_host=advance)
         if self._infer is not None:
             self._infer.refresh()  # the update changed the parameters: padded weight copies follow (inside the graph too)
         for t in range(self.num_steps_per_env):
@@ -230,10 +270,11 @@ class OnPolicyRunner:
                                    mu_out_d=st.mu[t].data_ptr(), sigma_out_d=st.sigma[t].data_ptr(), obs_out_d=st.observations[t].data_ptr(),
                                    plan=env._plan_h.value, state=ctypes.pointer(env._state()), buf=ctypes.pointer(env._bufs),
                                    pre_clip=math.inf if env.clip_actions is None else float(env.clip_actions))
+                nrm = (onorm, cnorm) if is_raw else None  # (step 0, or a plain agent: the rows as they are)
                 if priv is not None:
-                    self._infer(obs, None, st.values[t], act=act, critic_x=cobs, critic_obs_out=st.privileged_observations[t])
+                    self._infer(obs, None, st.values[t], act=act, critic_x=cobs, critic_obs_out=st.privileged_observations[t], norm=nrm)
                 else:
-                    self._infer(obs, None, st.values[t], act=act)
+                    self._infer(obs, None, st.values[t], act=act, norm=nrm)
                 # launch 2 (+ launch 3, the observations): the step kernel writes slot t itself; the log sum rides in the step tail
                 slot = ImxRolloutSlot(value_t=st.values[t].data_ptr(), rewards_out=st.rewards[t].data_ptr(), dones_out=st.dones[t].data_ptr(),
                                       cur_reward_sum=self._cur_reward_sum.data_ptr(), cur_ep_len=self._cur_episode_length.data_ptr(),
@@ -245,7 +286,14 @@ class OnPolicyRunner:
                     env._bufs.log_accum = None
                 obs = obs_dict["policy"]
                 cobs = obs_dict[priv] if priv is not None else obs
+                if normalized:  # launches 4 and 5: this step's raw rows into the statistics
+                    update_stats(obs, cobs)
+                    is_raw = True
                 continue
+            if is_raw:  # (a fused step before this one left raw rows)
+                obs = onorm.apply(obs)
+                cobs = cnorm.apply(cobs) if priv is not None else obs
+                is_raw = False
             if self._infer.ok:  # both networks, all layers, one launch (activations stay in LDS)
                 mu, value = self._mu_buf, self._value_buf
                 if priv is not None:
@@ -281,6 +329,22 @@ class OnPolicyRunner:
             # the critic reads this step's observations (its own group, or the policy's: the first step's input may be a copy -- the
             # captured graph's -- and is not the buffer env.step writes)
             cobs = obs_dict[priv] if priv is not None else obs
+            if normalized:  # upstream's order: statistics first, then the rows with the new statistics
+                update_stats(obs, cobs)
+                obs = onorm.apply(obs)
+                cobs = cnorm.apply(cobs) if priv is not None else obs
+        if is_raw:  # the normalised last rows: what compute_returns gets and the next rollout's step 0 reads
+            if self._graph_capturing:
+                obs = onorm.apply(obs, out=self._obs_out)
+                cobs = cnorm.apply(cobs, out=self._priv_out) if priv is not None else obs
+            else:
+                if self._norm_last is None:
+                    self._norm_last = (torch.empty_like(obs), torch.empty_like(cobs) if priv is not None else None)
+                obs = onorm.apply(obs, out=self._norm_last[0])
+                cobs = cnorm.apply(cobs, out=self._norm_last[1]) if priv is not None else obs
+            self._privileged_obs = cobs
+            st.step = self.num_steps_per_env
+            return obs
         self._privileged_obs = cobs if priv is not None else obs
         st.step = self.num_steps_per_env
         if self._graph_capturing:
@@ -290,6 +354,8 @@ class OnPolicyRunner:
         return obs
 
     _graph_capturing = False
+    _graph_normalized = False  # the captured rollout keeps normaliser statistics: a replay advances their host counts
+    _norm_last = None          # eager normalised rollout: the buffers its normalised last rows live in
     _infer = None
 
     def collect(self):
@@ -330,6 +396,11 @@ class OnPolicyRunner:
                 if self.privileged_obs_type is not None:
                     self._priv_in.copy_(self._priv_out)
             self._graph.replay()
+            if self._graph_normalized:  # once per step, by the rule the kernels apply to the device count
+                for _ in range(self.num_steps_per_env):
+                    self.obs_normalizer.advance_host_count(self.env.num_envs)
+                    if self.privileged_obs_type is not None:
+                        self.privileged_obs_normalizer.advance_host_count(self.env.num_envs)
             self.alg.storage.step = self.num_steps_per_env
             self.env.unwrapped.common_step_counter += self.num_steps_per_env
 

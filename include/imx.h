@@ -922,6 +922,9 @@ void imx_reduce_batch_destroy(imx_reduce_batch_t* batch);
 int imx_mlp_set_dw_cu_budget(int cus);
 int imx_reduce_batch_begin(imx_reduce_batch_t* batch);
 int imx_reduce_batch_flush(imx_reduce_batch_t* batch, imx_stream_t stream);
+/* Ends the open batch WITHOUT launching: what it holds stays queued, the host thread is free to open another network's batch, and a
+ * later begin + flush (or further defer_to = batch calls before that) launches everything in one kernel. */
+int imx_reduce_batch_end(imx_reduce_batch_t* batch);
 
 /* Same with the ELU backward of this layer fused in: dH_d is the gradient w.r.t. the layer's ACTIVATED output h = ELU(z),
  * H_d that saved output; dZ = dH * (h > 0 ? 1 : h + elu_alpha) (aten elu_backward with is_result) is formed on the way
@@ -930,6 +933,19 @@ int imx_reduce_batch_flush(imx_reduce_batch_t* batch, imx_stream_t stream);
 int imx_mlp_dw_elu(int64_t M, int N, int K, const float* dH_d, int64_t ldg, const float* H_d, int64_t ldh, float elu_alpha,
                    float* dZ_out_d, int64_t ldd, const float* X_d, int64_t ldx, float* dW_d, float* db_d, void* scratch_d,
                    size_t scratch_bytes, imx_stream_t stream);
+
+/* imx_mlp_dw_elu on a workgroup tile of 128 out-features x 256 in-features, for a layer with 128 < K <= 256 (anything else is refused):
+ * one tile column, so the ELU' of a dH / H tile is formed once instead of once per 128-wide column tile.  Meant for the first layers of
+ * actor and critic stacked into one launch when both read the same X: H_d is the stacked saved output (M, N; pitch ldh) and the
+ * incoming gradient arrives as n_seg (1..4) column segments -- dH_seg_d is a HOST array of device pointers, segment i holds columns
+ * [i * seg_cols, (i + 1) * seg_cols) of dH with the common pitch ldg; seg_cols a multiple of 128 when n_seg > 1 -- so the dX GEMMs
+ * of the two networks need no copy.  dW (N, K) and db are bit-identical to imx_mlp_dw_elu run on every segment's rows of the layer
+ * whenever both plan the same sample split (N / n_seg a multiple of 128 rows per segment).  No dZ output.  The reduction is queued
+ * on defer_to (may be a batch that is not open on this thread) or, when NULL, launched now.  Scratch: imx_mlp_dw_wide_scratch_bytes. */
+size_t imx_mlp_dw_wide_scratch_bytes(int64_t M, int out_features, int in_features);
+int imx_mlp_dw_elu_wide(int64_t M, int N, int K, int n_seg, const float* const* dH_seg_d, int seg_cols, int64_t ldg, const float* H_d,
+                        int64_t ldh, float elu_alpha, const float* X_d, int64_t ldx, float* dW_d, float* db_d, void* scratch_d,
+                        size_t scratch_bytes, imx_reduce_batch_t* defer_to, imx_stream_t stream);
 
 /* Rollout inference (rsl_rl actor_critic.py::act / evaluate): the whole Linear+ELU stack of up to two
  * networks sharing the input X (M, dims[0]; pitch ldx) in ONE launch, 32 samples per workgroup, activations in LDS.

@@ -23,6 +23,10 @@ namespace {
 constexpr int DW_T = 128;          // output tile: 128 out-features x 128 in-features per workgroup (4 waves, 64x64 each)
 constexpr int DW_BM = 32;          // samples per stage
 constexpr int DW_LD = DW_T + 32;   // LDS row pitch (floats): the two half-waves (sample m, m+1) land on disjoint banks
+// WK: in-feature width of the workgroup tile in units of DW_T (1: 128 x 128; 2: 128 out-features x 256 in-features, the wide tile of
+// imx_mlp_dw_elu_wide).  The X stage of the wide tile keeps the 32-float pad: 288 = 32 mod 64 banks, like 160.
+constexpr int dw_ldx(int wk) { return DW_T * wk + 32; }
+constexpr int DW_MAX_SEG = 4;      // column segments of the incoming gradient (wide tile only)
 
 struct DwArgs {
     int64_t M;
@@ -42,6 +46,12 @@ struct DwArgs {
     float* Dout;
     int64_t ldd;
     float alpha;
+};
+// wide tile only: the incoming gradient as column segments of segw columns (a multiple of DW_T, so an N-slab lies in one segment) with
+// one base pointer each and the common pitch ldy; segw = 0: dY as above
+struct DwSeg {
+    int segw;
+    const float* yseg[DW_MAX_SEG];
 };
 
 // one [32 x 128] stage of a row-major matrix -> 16 registers per thread (zero beyond row_end / ncols)
@@ -69,17 +79,17 @@ __device__ __forceinline__ void dw_load(float (&r)[16], const float* __restrict_
     }
 }
 
-template <bool VEC>
+template <bool VEC, int LD = DW_LD>
 __device__ __forceinline__ void dw_store(const float (&r)[16], float* __restrict__ s, int t) {
     if (VEC) {
         const int c = 4 * (t & 31), rr = t >> 5;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            *reinterpret_cast<float4*>(s + (rr + 8 * i) * DW_LD + c) = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
+            *reinterpret_cast<float4*>(s + (rr + 8 * i) * LD + c) = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
     } else {
         const int c = t & 127, rr = t >> 7;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) s[(rr + 2 * i) * DW_LD + c] = r[i];
+        for (int i = 0; i < 16; ++i) s[(rr + 2 * i) * LD + c] = r[i];
     }
 }
 
@@ -125,24 +135,30 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t dw_rsrc(const float* p, int64_
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, (int)(((rows - 1) * ld + ncols) * 4), 0x00020000);
 }
 
-template <bool ACT>
-__device__ __forceinline__ void dw_movers_steady(const DwArgs& a, float* __restrict__ sY, float* __restrict__ sX, int t, int n0, int k0,
-                                                 int64_t m_begin, int nst, bool want_db, unsigned dgroups, float (&dbv)[4]) {
+// Wide tile (WK = 2): X is two 128-column halves per thread (the second half's lanes past the row re-read its last vector too); dY may
+// be a column segment (dYb, its yN columns, the slab at its column yn0) -- H, Dout and the bias sums keep the layer's own columns.
+template <bool ACT, int WK>
+__device__ __forceinline__ void dw_movers_steady(const DwArgs& a, const float* __restrict__ dYb, int yn0, int yN, float* __restrict__ sY,
+                                                 float* __restrict__ sX, int t, int n0, int k0, int64_t m_begin, int nst, bool want_db,
+                                                 unsigned dgroups, float (&dbv)[4]) {
+    constexpr int LDX = dw_ldx(WK);
     const int cl = 4 * (t & 31), rr = t >> 5;
     const int kv = (a.K + 3) & ~3;  // X rows are read in whole vectors: the pitch covers the last one
     const int rows = nst * DW_BM;
-    const int oy = (int)((rr * a.ldy + min(n0 + cl, a.N - 4)) * 4);
-    const int ox = (int)((rr * a.ldx + min(k0 + cl, kv - 4)) * 4);
+    const int oy = (int)((rr * a.ldy + min(yn0 + cl, yN - 4)) * 4);
+    int ox[WK];
+#pragma unroll
+    for (int h = 0; h < WK; ++h) ox[h] = (int)((rr * a.ldx + min(k0 + h * DW_T + cl, kv - 4)) * 4);
     const int oh = ACT ? (int)((rr * a.ldh + min(n0 + cl, a.N - 4)) * 4) : 0;
     const int od = ACT ? (int)((rr * a.ldd + n0 + cl) * 4) : 0;
     const bool d_ok = n0 + cl < a.N;
-    const __amdgpu_buffer_rsrc_t by = dw_rsrc(a.dY + m_begin * a.ldy, rows, a.ldy, a.N);
+    const __amdgpu_buffer_rsrc_t by = dw_rsrc(dYb + m_begin * a.ldy, rows, a.ldy, yN);
     const __amdgpu_buffer_rsrc_t bx = dw_rsrc(a.X + m_begin * a.ldx, rows, a.ldx, kv);
     const __amdgpu_buffer_rsrc_t bh = dw_rsrc(ACT ? a.H + m_begin * a.ldh : a.dY, rows, ACT ? a.ldh : a.ldy, a.N);
     const __amdgpu_buffer_rsrc_t bd = dw_rsrc(ACT && dgroups != 0u ? a.Dout + m_begin * a.ldd : a.dY, rows, ACT ? a.ldd : a.ldy, a.N);
     const int gy = (int)(32 * a.ldy), gx = (int)(32 * a.ldx), gh = (int)(32 * a.ldh), gd = (int)(32 * a.ldd);  // bytes between a thread's row groups (8 rows)
     int sy = 0, sx = 0, sh = 0, sd = 0;  // byte offset of the stage to load next / to store next (wave-uniform)
-    dw_f4 ry[4], rx[4], rh[ACT ? 4 : 1];
+    dw_f4 ry[4], rx[WK][4], rh[ACT ? 4 : 1];
     auto load = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) ry[i] = __builtin_bit_cast(dw_f4, __builtin_amdgcn_raw_buffer_load_b128(by, oy, sy + i * gy, 0));
@@ -152,7 +168,9 @@ __device__ __forceinline__ void dw_movers_steady(const DwArgs& a, float* __restr
             sh += 4 * gh;
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) rx[i] = __builtin_bit_cast(dw_f4, __builtin_amdgcn_raw_buffer_load_b128(bx, ox, sx + i * gx, 0));
+        for (int h = 0; h < WK; ++h)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) rx[h][i] = __builtin_bit_cast(dw_f4, __builtin_amdgcn_raw_buffer_load_b128(bx, ox[h], sx + i * gx, 0));
         sy += 4 * gy;
         sx += 4 * gx;
     };
@@ -172,11 +190,13 @@ __device__ __forceinline__ void dw_movers_steady(const DwArgs& a, float* __restr
             }
         }
         float* py = sY + buf * (DW_BM * DW_LD) + rr * DW_LD + cl;
-        float* px = sX + buf * (DW_BM * DW_LD) + rr * DW_LD + cl;
+        float* px = sX + buf * (DW_BM * LDX) + rr * LDX + cl;
 #pragma unroll
         for (int i = 0; i < 4; ++i) *reinterpret_cast<dw_f4*>(py + 8 * i * DW_LD) = ry[i];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) *reinterpret_cast<dw_f4*>(px + 8 * i * DW_LD) = rx[i];
+        for (int h = 0; h < WK; ++h)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) *reinterpret_cast<dw_f4*>(px + h * DW_T + 8 * i * LDX) = rx[h][i];
         if (want_db) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) { dbv[0] += ry[i][0]; dbv[1] += ry[i][1]; dbv[2] += ry[i][2]; dbv[3] += ry[i][3]; }
@@ -195,10 +215,11 @@ __device__ __forceinline__ void dw_movers_steady(const DwArgs& a, float* __restr
     }
 }
 
-template <bool YVEC, bool XVEC, bool ACT>
-__global__ void __launch_bounds__(512, 1) k_mlp_dw(DwArgs a) {
+template <bool YVEC, bool XVEC, bool ACT, int WK>
+__device__ __forceinline__ void dw_tile(const DwArgs& a, const DwSeg& g) {
+    constexpr int LDX = dw_ldx(WK), DW_TK = DW_T * WK;
     __shared__ float sY[2][DW_BM * DW_LD];
-    __shared__ float sX[2][DW_BM * DW_LD];
+    __shared__ float sX[2][DW_BM * LDX];
     // XCD-aware order: consecutive workgroup ids go round-robin over the 8 XCDs, so give every XCD whole splits -- the
     // tn*tk tiles of one split read the same [rps x (N + K)] slab of dY and X and share it through that XCD's L2
     const int T = a.tn * a.tk;
@@ -211,7 +232,17 @@ __global__ void __launch_bounds__(512, 1) k_mlp_dw(DwArgs a) {
         tile = blockIdx.x % T;
         s = blockIdx.x / T;
     }
-    const int n0 = (tile / a.tk) * DW_T, k0 = (tile % a.tk) * DW_T;
+    const int n0 = (tile / a.tk) * DW_T, k0 = (tile % a.tk) * DW_TK;
+    const float* dYb = a.dY;  // the incoming gradient of this N-slab: the matrix itself, or (wide tile) the column segment that holds it
+    int yn0 = n0, yN = a.N;
+    if constexpr (WK == 2) {
+        if (g.segw > 0) {
+            const int sg = n0 / g.segw;
+            dYb = sg == 0 ? g.yseg[0] : sg == 1 ? g.yseg[1] : sg == 2 ? g.yseg[2] : g.yseg[3];
+            yn0 = n0 - sg * g.segw;
+            yN = min(g.segw, a.N - sg * g.segw);
+        }
+    }
     const int64_t m_begin = (int64_t)s * a.rps, m_end = std::min<int64_t>(m_begin + a.rps, a.M);
     const int nst = (int)((m_end - m_begin + DW_BM - 1) / DW_BM);
     const bool want_db = a.part_db != nullptr && (tile % a.tk) == 0;
@@ -219,7 +250,7 @@ __global__ void __launch_bounds__(512, 1) k_mlp_dw(DwArgs a) {
     if (threadIdx.x >= 256) {
         // ------------------------------------------------------------------------------------------------ movers
         const int t = threadIdx.x - 256;
-        float ry[16], rx[16], rh[ACT ? 16 : 1];
+        float ry[16], rx[WK][16], rh[ACT ? 16 : 1];
         float dbv[4] = {0.f, 0.f, 0.f, 0.f};  // column sums of the dY slab (YVEC: 4 columns x rows t>>5 + 8i; else 1 column)
         int64_t loaded_row0 = 0;
         // Dout: the tk column tiles of an N-slab all hold the product; the 16-byte form spreads a thread's four row groups over them
@@ -239,14 +270,15 @@ __global__ void __launch_bounds__(512, 1) k_mlp_dw(DwArgs a) {
             int64_t ld = std::max(a.ldy, a.ldx);
             if (ACT) ld = std::max(ld, std::max(a.ldh, a.ldd));
             steady = nst > 0 && (m_end - m_begin) % DW_BM == 0 && a.rps * ld < ((int64_t)1 << 28);  // a split's byte offsets fit 31 bits
-            if (steady) dw_movers_steady<ACT>(a, &sY[0][0], &sX[0][0], t, n0, k0, m_begin, nst, want_db, dgroups, dbv);
+            if (steady) dw_movers_steady<ACT, WK>(a, dYb, yn0, yN, &sY[0][0], &sX[0][0], t, n0, k0, m_begin, nst, want_db, dgroups, dbv);
         }
         auto load = [&](int st) {
             const int64_t row0 = m_begin + (int64_t)st * DW_BM;  // rows >= m_end load as zeros
             loaded_row0 = row0;
-            dw_load<YVEC>(ry, a.dY, a.ldy, row0, m_end, n0, a.N, t);
+            dw_load<YVEC>(ry, dYb, a.ldy, row0, m_end, yn0, yN, t);
             if constexpr (ACT) dw_load<YVEC>(rh, a.H, a.ldh, row0, m_end, n0, a.N, t);
-            dw_load<XVEC>(rx, a.X, a.ldx, row0, m_end, k0, a.K, t);
+            dw_load<XVEC>(rx[0], a.X, a.ldx, row0, m_end, k0, a.K, t);
+            if constexpr (WK == 2) dw_load<XVEC>(rx[1], a.X, a.ldx, row0, m_end, k0 + DW_T, a.K, t);
         };
         auto store = [&](int buf) {
             if constexpr (ACT) {  // gradient through ELU from its saved output: y > 0 ? 1 : y + alpha
@@ -255,7 +287,8 @@ __global__ void __launch_bounds__(512, 1) k_mlp_dw(DwArgs a) {
                 if (write_d) dw_store_global<YVEC>(ry, a.Dout, a.ldd, loaded_row0, m_end, n0, a.N, t, dgroups);
             }
             dw_store<YVEC>(ry, sY[buf], t);
-            dw_store<XVEC>(rx, sX[buf], t);
+            dw_store<XVEC, LDX>(rx[0], sX[buf], t);
+            if constexpr (WK == 2) dw_store<XVEC, LDX>(rx[1], sX[buf] + DW_T, t);
             if (want_db) {
                 if (YVEC) {
 #pragma unroll
@@ -304,52 +337,94 @@ __global__ void __launch_bounds__(512, 1) k_mlp_dw(DwArgs a) {
     const int t = threadIdx.x;
     const int lane = t & 63, w = t >> 6, r = lane & 31, half = lane >> 5;
     const int wn = w & 1, wk = w >> 1;
-    f32x16 acc[2][2];
+    constexpr int NBK = 2 * WK;  // 32-column blocks of in-features per wave: a wave owns 64 out-features x 64 (wide tile: 128) in-features
+    f32x16 acc[2][NBK];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int j = 0; j < NBK; ++j)
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.0f;
     __syncthreads();
-    for (int st = 0; st < nst; ++st) {
-        const float* py = sY[st & 1] + half * DW_LD + wn * 64 + r;
-        const float* px = sX[st & 1] + half * DW_LD + wk * 64 + r;
-        // Operand ping-pong (P, Q): the LDS reads of step kk+1 are issued BEFORE the four MFMAs of step kk and waited
-        // for after them; the scheduling barriers keep the compiler from sinking the reads behind the MFMAs again.
-        float p0 = py[0], p1 = py[32], p2 = px[0], p3 = px[32], q0, q1, q2, q3;
+    if constexpr (WK == 2) {
+        // Wide tile: 2 dY reads and 4 X reads ahead of each group of 8 MFMAs, the same ping-pong and scheduling barriers as below.  Every
+        // accumulator still sees the samples in the same order through the same chain: the bits of the 128-wide tiles.
+        for (int st = 0; st < nst; ++st) {
+            const float* py = sY[st & 1] + half * DW_LD + wn * 64 + r;
+            const float* px = sX[st & 1] + half * LDX + wk * 128 + r;
+            float p0 = py[0], p1 = py[32], p2 = px[0], p3 = px[32], p4 = px[64], p5 = px[96], q0, q1, q2, q3, q4, q5;
 #pragma unroll
-        for (int kk = 0; kk < DW_BM / 2; kk += 2) {
-            q0 = py[(kk + 1) * 2 * DW_LD]; q1 = py[(kk + 1) * 2 * DW_LD + 32];
-            q2 = px[(kk + 1) * 2 * DW_LD]; q3 = px[(kk + 1) * 2 * DW_LD + 32];
-            __builtin_amdgcn_sched_barrier(0);
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(p0, p2, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(p0, p3, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(p1, p2, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(p1, p3, acc[1][1], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (kk + 2 < DW_BM / 2) {
-                p0 = py[(kk + 2) * 2 * DW_LD]; p1 = py[(kk + 2) * 2 * DW_LD + 32];
-                p2 = px[(kk + 2) * 2 * DW_LD]; p3 = px[(kk + 2) * 2 * DW_LD + 32];
+            for (int kk = 0; kk < DW_BM / 2; kk += 2) {
+                q0 = py[(kk + 1) * 2 * DW_LD]; q1 = py[(kk + 1) * 2 * DW_LD + 32];
+                q2 = px[(kk + 1) * 2 * LDX]; q3 = px[(kk + 1) * 2 * LDX + 32]; q4 = px[(kk + 1) * 2 * LDX + 64]; q5 = px[(kk + 1) * 2 * LDX + 96];
+                __builtin_amdgcn_sched_barrier(0);
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(p0, p2, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(p0, p3, acc[0][1], 0, 0, 0);
+                acc[0][2] = __builtin_amdgcn_mfma_f32_32x32x2f32(p0, p4, acc[0][2], 0, 0, 0);
+                acc[0][3] = __builtin_amdgcn_mfma_f32_32x32x2f32(p0, p5, acc[0][3], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(p1, p2, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(p1, p3, acc[1][1], 0, 0, 0);
+                acc[1][2] = __builtin_amdgcn_mfma_f32_32x32x2f32(p1, p4, acc[1][2], 0, 0, 0);
+                acc[1][3] = __builtin_amdgcn_mfma_f32_32x32x2f32(p1, p5, acc[1][3], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                if (kk + 2 < DW_BM / 2) {
+                    p0 = py[(kk + 2) * 2 * DW_LD]; p1 = py[(kk + 2) * 2 * DW_LD + 32];
+                    p2 = px[(kk + 2) * 2 * LDX]; p3 = px[(kk + 2) * 2 * LDX + 32]; p4 = px[(kk + 2) * 2 * LDX + 64]; p5 = px[(kk + 2) * 2 * LDX + 96];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(q0, q2, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(q0, q3, acc[0][1], 0, 0, 0);
+                acc[0][2] = __builtin_amdgcn_mfma_f32_32x32x2f32(q0, q4, acc[0][2], 0, 0, 0);
+                acc[0][3] = __builtin_amdgcn_mfma_f32_32x32x2f32(q0, q5, acc[0][3], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(q1, q2, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(q1, q3, acc[1][1], 0, 0, 0);
+                acc[1][2] = __builtin_amdgcn_mfma_f32_32x32x2f32(q1, q4, acc[1][2], 0, 0, 0);
+                acc[1][3] = __builtin_amdgcn_mfma_f32_32x32x2f32(q1, q5, acc[1][3], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
             }
-            __builtin_amdgcn_sched_barrier(0);
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(q0, q2, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(q0, q3, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(q1, q2, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(q1, q3, acc[1][1], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();
         }
-        __syncthreads();
+    } else {
+        for (int st = 0; st < nst; ++st) {
+            const float* py = sY[st & 1] + half * DW_LD + wn * 64 + r;
+            const float* px = sX[st & 1] + half * DW_LD + wk * 64 + r;
+            // Operand ping-pong (P, Q): the LDS reads of step kk+1 are issued BEFORE the four MFMAs of step kk and waited
+            // for after them; the scheduling barriers keep the compiler from sinking the reads behind the MFMAs again.
+            float p0 = py[0], p1 = py[32], p2 = px[0], p3 = px[32], q0, q1, q2, q3;
+#pragma unroll
+            for (int kk = 0; kk < DW_BM / 2; kk += 2) {
+                q0 = py[(kk + 1) * 2 * DW_LD]; q1 = py[(kk + 1) * 2 * DW_LD + 32];
+                q2 = px[(kk + 1) * 2 * DW_LD]; q3 = px[(kk + 1) * 2 * DW_LD + 32];
+                __builtin_amdgcn_sched_barrier(0);
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(p0, p2, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(p0, p3, acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(p1, p2, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(p1, p3, acc[1][1], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                if (kk + 2 < DW_BM / 2) {
+                    p0 = py[(kk + 2) * 2 * DW_LD]; p1 = py[(kk + 2) * 2 * DW_LD + 32];
+                    p2 = px[(kk + 2) * 2 * DW_LD]; p3 = px[(kk + 2) * 2 * DW_LD + 32];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(q0, q2, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(q0, q3, acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(q1, q2, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(q1, q3, acc[1][1], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __syncthreads();
+        }
     }
     // partial tile of this split (rows = out-features on the accumulator registers, columns = in-features on the lanes)
     float* part = a.part + (size_t)s * a.N * a.K;
-    const bool interior = n0 + DW_T <= a.N && k0 + DW_T <= a.K;  // unconditional stores: no wait between them
+    const bool interior = n0 + DW_T <= a.N && k0 + DW_TK <= a.K;  // unconditional stores: no wait between them
 #pragma unroll
     for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
-        for (int bj = 0; bj < 2; ++bj) {
-            const int k = k0 + wk * 64 + bj * 32 + r;
-            if (interior) {
+        for (int bj = 0; bj < NBK; ++bj) {
+            const int k = k0 + wk * (32 * NBK) + bj * 32 + r;
+            // (wide tile: K < 256 makes no tile interior, so the test is per 32-column block -- only the block that holds column K is guarded)
+            if (WK == 2 ? (n0 + DW_T <= a.N && k0 + wk * (32 * NBK) + bj * 32 + 32 <= a.K) : interior) {
 #pragma unroll
                 for (int q = 0; q < 16; ++q) part[(size_t)(n0 + wn * 64 + bi * 32 + acc_row(q, half)) * a.K + k] = acc[bi][bj][q];
             } else {
@@ -361,6 +436,17 @@ __global__ void __launch_bounds__(512, 1) k_mlp_dw(DwArgs a) {
             }
         }
     __syncthreads();  // pairs with the movers' barrier before their bias-gradient sum
+}
+
+// The tile width is a parameter of the body; the two kernels keep their own names (and the 128-wide one its resource figures).
+template <bool YVEC, bool XVEC, bool ACT>
+__global__ void __launch_bounds__(512, 1) k_mlp_dw(DwArgs a) {
+    dw_tile<YVEC, XVEC, ACT, 1>(a, DwSeg{});
+}
+
+template <bool YVEC, bool XVEC, bool ACT>
+__global__ void __launch_bounds__(512, 1) k_mlp_dw_wide(DwArgs a, DwSeg g) {
+    dw_tile<YVEC, XVEC, ACT, 2>(a, g);
 }
 
 // out[i] = sum_s part[s][i]: 64 consecutive outputs x 16 interleaved slices of the S partials per workgroup, slices
@@ -474,7 +560,8 @@ struct DwPlan {
 int g_num_cu = 0;
 int g_dw_cu_budget = 0;  // imx_mlp_set_dw_cu_budget: workgroups (= CUs) one imx_mlp_dw launch may spread its sample splits over; 0 = all
 
-DwPlan dw_plan(int64_t M, int N, int K) {
+// wide: the 128 x 256 tile (one tile column, K <= 256) -- only imx_mlp_dw_elu_wide asks for it; every other entry point plans 128 x 128
+DwPlan dw_plan(int64_t M, int N, int K, bool wide = false) {
     if (g_num_cu == 0) {
         int dev = 0, cu = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu <= 0)
@@ -483,7 +570,7 @@ DwPlan dw_plan(int64_t M, int N, int K) {
     }
     DwPlan p;
     p.tn = (N + DW_T - 1) / DW_T;
-    p.tk = (K + DW_T - 1) / DW_T;
+    p.tk = wide ? 1 : (K + DW_T - 1) / DW_T;
     const int T = p.tn * p.tk;
     const int cus = g_dw_cu_budget > 0 ? std::min(g_dw_cu_budget, g_num_cu) : g_num_cu;
     int64_t S = std::max<int64_t>(1, (int64_t)cus / T);  // one 8-wave workgroup (80 KB of LDS) per CU
@@ -1061,6 +1148,12 @@ extern "C" int imx_reduce_batch_begin(imx_reduce_batch_t* b) {
     return 0;
 }
 
+extern "C" int imx_reduce_batch_end(imx_reduce_batch_t* b) {
+    IMX_REQUIRE(b && t_batch == b, "imx_reduce_batch_end: this batch is not the one open on this thread");
+    t_batch = nullptr;  // what is queued stays queued: a later begin + flush launches it
+    return 0;
+}
+
 extern "C" int imx_reduce_batch_flush(imx_reduce_batch_t* b, imx_stream_t stream) {
     IMX_REQUIRE(b && t_batch == b, "imx_reduce_batch_flush: this batch is not the one open on this thread");
     t_batch = nullptr;
@@ -1084,6 +1177,57 @@ extern "C" int imx_mlp_dw_elu(int64_t M, int N, int K, const float* dH_d, int64_
     IMX_REQUIRE(H_d, "imx_mlp_dw_elu: the saved activation output is required");
     return mlp_dw_launch("imx_mlp_dw_elu", M, N, K, dH_d, ldg, H_d, ldh, elu_alpha, dZ_out_d, ldd, X_d, ldx, dW_d, db_d, scratch_d,
                          scratch_bytes, stream);
+}
+
+extern "C" size_t imx_mlp_dw_wide_scratch_bytes(int64_t M, int out_features, int in_features) {
+    if (M <= 0 || out_features <= 0 || in_features <= DW_T || in_features > 2 * DW_T) return 0;
+    const DwPlan p = dw_plan(M, out_features, in_features, true);
+    return ((size_t)p.S * out_features * in_features + (size_t)p.S * out_features) * sizeof(float) + 256;
+}
+
+extern "C" int imx_mlp_dw_elu_wide(int64_t M, int N, int K, int n_seg, const float* const* dH_seg_d, int seg_cols, int64_t ldg,
+                                   const float* H_d, int64_t ldh, float elu_alpha, const float* X_d, int64_t ldx, float* dW_d, float* db_d,
+                                   void* scratch_d, size_t scratch_bytes, imx_reduce_batch_t* defer_to, imx_stream_t stream) {
+    const char* who = "imx_mlp_dw_elu_wide";
+    IMX_REQUIRE(M > 0 && N > 0 && dH_seg_d && H_d && X_d && dW_d && scratch_d, "%s: bad arguments", who);
+    IMX_REQUIRE(K > DW_T && K <= 2 * DW_T, "%s: %d in-features (the 128 x 256 tile serves 129..256; imx_mlp_dw_elu serves the rest)", who, K);
+    IMX_REQUIRE(n_seg >= 1 && n_seg <= DW_MAX_SEG, "%s: %d gradient segments (1..%d)", who, n_seg, DW_MAX_SEG);
+    IMX_REQUIRE(n_seg == 1 ? seg_cols >= N : (seg_cols % DW_T == 0 && (int64_t)(n_seg - 1) * seg_cols < N && (int64_t)n_seg * seg_cols >= N),
+                "%s: %d segments of %d columns do not cover %d out-features in whole 128-row slabs", who, n_seg, seg_cols, N);
+    for (int i = 0; i < n_seg; ++i) IMX_REQUIRE(dH_seg_d[i], "%s: gradient segment %d is null", who, i);
+    const int widest = n_seg == 1 ? N : seg_cols;
+    IMX_REQUIRE(ldg >= widest && ldh >= N && ldx >= K, "%s: row pitch smaller than the row (ldg=%lld, ldh=%lld N=%d, ldx=%lld K=%d)", who,
+                (long long)ldg, (long long)ldh, N, (long long)ldx, K);
+    const DwPlan p = dw_plan(M, N, K, true);
+    const size_t need = ((size_t)p.S * N * K + (size_t)p.S * N) * sizeof(float);
+    IMX_REQUIRE(scratch_bytes >= need, "%s: scratch too small (%zu < %zu bytes; see imx_mlp_dw_wide_scratch_bytes)", who, scratch_bytes, need);
+    DwArgs a;
+    a.M = M; a.N = N; a.K = K;
+    a.dY = dH_seg_d[0]; a.ldy = ldg; a.X = X_d; a.ldx = ldx;
+    a.part = (float*)scratch_d;
+    a.part_db = db_d ? a.part + (size_t)p.S * N * K : nullptr;
+    a.tn = p.tn; a.tk = p.tk; a.S = p.S; a.rps = p.rps;
+    a.H = H_d; a.ldh = ldh; a.Dout = nullptr; a.ldd = 0; a.alpha = elu_alpha;
+    DwSeg g;
+    g.segw = n_seg > 1 ? seg_cols : 0;
+    bool yvec = (N % 4 == 0) && (ldg % 4 == 0) && (ldh % 4 == 0) && aligned16(H_d);
+    for (int i = 0; i < DW_MAX_SEG; ++i) {
+        g.yseg[i] = i < n_seg ? dH_seg_d[i] : nullptr;
+        if (i < n_seg) yvec = yvec && aligned16(dH_seg_d[i]);
+    }
+    const bool xvec = (ldx % 4 == 0) && aligned16(X_d) && (K % 4 == 0 || ldx >= ((K + 3) & ~3));
+    const dim3 grid((unsigned)(p.tn * p.tk * p.S)), block(512);
+    hipStream_t st = (hipStream_t)stream;
+    if (yvec && xvec) hipLaunchKernelGGL((k_mlp_dw_wide<true, true, true>), grid, block, 0, st, a, g);
+    else if (yvec) hipLaunchKernelGGL((k_mlp_dw_wide<true, false, true>), grid, block, 0, st, a, g);
+    else if (xvec) hipLaunchKernelGGL((k_mlp_dw_wide<false, true, true>), grid, block, 0, st, a, g);
+    else hipLaunchKernelGGL((k_mlp_dw_wide<false, false, true>), grid, block, 0, st, a, g);
+    IMX_HIP(hipGetLastError());
+    imx_reduce_batch* saved = t_batch;  // the reduction goes to the batch NAMED here (null: launched now), whatever is open on this thread
+    t_batch = defer_to;
+    const int rc = reduce_or_defer(who, (int64_t)N * K, p.S, a.part, dW_d, N, a.part_db, db_d, st);
+    t_batch = saved;
+    return rc;
 }
 
 static int head_fwd_launch(int64_t M, int K, int A, float* h_d, int64_t ldh, const float* W_d, const float* b_d, float* y_d,

@@ -272,6 +272,7 @@ FUSED_FIRST_LAYER_MAX_K = 256  # imx_mlp_fwd_elu keeps a column's weights in reg
 FUSED_L0 = os.getenv("IMX_FUSED_L0", "1") != "0"        # first Linear + ELU as one imx_mlp_fwd_elu launch (off: library GEMM + ELU pass)
 FUSED_HEAD = os.getenv("IMX_FUSED_HEAD", "0")           # "1" / "a" / "c": output layer forward + loss + backward in one launch (slower in situ)
 LOSS_ON_SIDE = os.getenv("IMX_LOSS_ON_SIDE", "1") == "1"  # loss-value kernels behind the critic's backward pass (off: a third stream)
+WIDE_DW0 = os.getenv("IMX_WIDE_DW0", "1") != "0"        # stacked first layer: dW / db of both networks as ONE imx_mlp_dw_elu_wide launch (off: one each)
 
 
 def fused_first_layer_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
@@ -397,11 +398,14 @@ def mlp_forward(layers, x, out=None, head_loss=None, first=None):
     return h, saved
 
 
-def mlp_backward(layers, saved, dout, scratch=None, head_dprev=None):
+def mlp_backward(layers, saved, dout, scratch=None, head_dprev=None, stop_above_first=False, flush=True):
     """Writes dW/db of every layer straight into ``param.grad`` (views of the flat bucket).  dW / db: ``imx_mlp_dw``
     (split over the samples on the f32 MFMA); output layer: ``imx_mlp_head_bwd`` (dW, db, dX and the ELU' of the layer
     below in one pass); the wide dX GEMMs stay in the library, and the ELU backward of a hidden layer is folded into that
-    layer's ``imx_mlp_dw_elu`` (no separate elementwise pass)."""
+    layer's ``imx_mlp_dw_elu`` (no separate elementwise pass).  ``stop_above_first``: the walk ends with layer 1's dX GEMM and
+    returns its result, the gradient w.r.t. layer 0's ELU output (``wide_dw0_ok`` says when that is what the walk produces); layer
+    0 is the caller's (``imx_mlp_dw_elu_wide``).  ``flush`` false (deferred reductions only): the batch is ended, not launched --
+    its reductions stay queued for a later begin + flush."""
     L = lib()
     M = dout.shape[0]
     if scratch is None:
@@ -411,19 +415,36 @@ def mlp_backward(layers, saved, dout, scratch=None, head_dprev=None):
     if deferred is not None:
         check(L.imx_reduce_batch_begin(deferred.handle))
     try:
-        _mlp_backward_layers(L, layers, saved, dout, M, scratch, deferred, stream, head_dprev)
+        return _mlp_backward_layers(L, layers, saved, dout, M, scratch, deferred, stream, head_dprev, 1 if stop_above_first else 0)
     finally:
-        if deferred is not None:
+        if deferred is not None and flush:
             check(L.imx_reduce_batch_flush(deferred.handle, stream))
+        elif deferred is not None:
+            check(L.imx_reduce_batch_end(deferred.handle))
 
 
-def _mlp_backward_layers(L, layers, saved, dout, M, scratch, deferred, stream, head_dprev=None):
+def wide_dw0_ok(layers, x: torch.Tensor) -> bool:
+    """Whether ``mlp_backward(..., stop_above_first=True)`` hands back the gradient w.r.t. layer 0's ELU output and
+    ``imx_mlp_dw_elu_wide`` serves layer 0: an ELU layer with 128 < K <= 256 and whole 128-row slabs of out-features that reads
+    16-byte aligned rows, and a layer 1 whose backward is the dW kernel + library dX GEMM (the head kernel applies the ELU' below it
+    itself)."""
+    if len(layers) < 2 or not isinstance(layers[0][1], nn.ELU):
+        return False
+    lin0, lin1 = layers[0][0], layers[1][0]
+    if not 128 < lin0.in_features <= 256 or lin0.out_features % 128 != 0:  # (each network's gradient is a segment of whole 128-row slabs)
+        return False
+    if lin1.out_features <= HEAD_MAX_OUT and lin1.in_features % 32 == 0 and lin1.in_features <= 256:  # (_is_head: imx_mlp_head_bwd territory)
+        return False
+    return x.dtype == torch.float32 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
+
+
+def _mlp_backward_layers(L, layers, saved, dout, M, scratch, deferred, stream, head_dprev=None, lowest=0):
     d = dout          # gradient w.r.t. the pre-activation output of layer i ...
     pending = None    # ... or (gradient w.r.t. its ELU output, that output, alpha): resolved inside imx_mlp_dw_elu
     top = len(layers) - 1
     if head_dprev is not None:  # the output layer's backward already ran inside imx_mlp_head_fwd_bwd (mlp_forward)
         d, top = head_dprev, top - 1
-    for i in range(top, -1, -1):
+    for i in range(top, lowest - 1, -1):
         lin, _ = layers[i]
         x = saved[i] if not isinstance(saved[i], tuple) else saved[i][1]
         prev_act = layers[i - 1][1] if i > 0 else None
@@ -451,6 +472,8 @@ def _mlp_backward_layers(L, layers, saved, dout, M, scratch, deferred, stream, h
                                lin.bias.grad.data_ptr(), scr.data_ptr(), scr.numel(), stream))
         if i > 0:
             dx = torch.mm(d, lin.weight)
+            if i == lowest:
+                return dx  # (stop_above_first) ELU' of layer 0 is the caller's
             if isinstance(prev_act, nn.ELU) and dx.stride(1) == 1 and saved[i].stride(1) == 1:
                 pending = (dx, saved[i], prev_act.alpha)  # ELU'(z) from the saved output: y > 0 ? 1 : y + alpha
             elif isinstance(prev_act, nn.ELU):
@@ -716,6 +739,10 @@ class PPO:
                       scratch=torch.empty(int(lib().imx_ppo_scratch_bytes(M)), dtype=torch.uint8, device=dev),
                       colsum=torch.empty(int(lib().imx_colsum_scratch_bytes()), dtype=torch.uint8, device=dev),
                       mlp_a=DeferredReductions(self._actor_layers, M, dev), mlp_c=DeferredReductions(self._critic_layers, M, dev))
+            if self._joint0 is not None and WIDE_DW0:
+                w0 = self._joint0[0]
+                n = int(lib().imx_mlp_dw_wide_scratch_bytes(M, w0.shape[0], w0.shape[1]))  # 0: not a shape of the wide tile
+                ws["dw0"] = torch.empty(n, dtype=torch.uint8, device=dev) if n else None
             self._ws[(M, A)] = ws
         return ws
 
@@ -805,6 +832,25 @@ class PPO:
                 z0 = torch.addmm(b0, obs, w0.t())
                 joint_elu = alpha0  # the ELU of each half is applied on ITS network's stream, after the fork
             first_a, first_c = z0[:, :H0], z0[:, H0:]
+        # ... and backward: dW / db of both first layers as ONE launch on a 128 x 256 tile (imx_mlp_dw_elu_wide; same bits).  Both walks
+        # stop above layer 0 and hand back dh0; the stacked launch runs on main once the critic's dX GEMM is done, its reduction rides in
+        # the actor's batch, and the critic's reduction and the loss values run beside it on the side stream.
+        wide0 = (z0 is not None and ws.get("dw0") is not None and obs.shape[1] == self._joint0[0].shape[1]
+                 and wide_dw0_ok(self._actor_layers, obs) and wide_dw0_ok(self._critic_layers, obs))
+
+        def stacked_dw0(dh_a, dh_c, st):
+            w0, _b0, H0, alpha0 = self._joint0
+            la = self._actor_layers[0][0]
+            if dh_a.stride(0) != dh_c.stride(0) or dh_a.stride(1) != 1 or dh_c.stride(1) != 1:
+                raise _lib.ImxError("PPO.minibatch_step: the two first-layer gradients do not share a row pitch")
+            segs = (ctypes.c_void_p * 2)(dh_a.data_ptr(), dh_c.data_ptr())
+            batch = ws["mlp_a"].handle
+            check(L.imx_mlp_dw_elu_wide(M, 2 * H0, obs.shape[1], 2, segs, H0, dh_a.stride(0), z0.data_ptr(), z0.stride(0), alpha0,
+                                        obs.data_ptr(), obs.stride(0), la.weight.grad.data_ptr(), la.bias.grad.data_ptr(),
+                                        ws["dw0"].data_ptr(), ws["dw0"].numel(), batch, st))
+            check(L.imx_reduce_batch_begin(batch))  # the actor's walk ended its batch unflushed: everything in it goes out now
+            check(L.imx_reduce_batch_flush(batch, st))
+
         side = self._side_stream()
         main = torch.cuda.current_stream(self.device)
         if side is not None:
@@ -830,15 +876,26 @@ class PPO:
             if not loss_on_side:
                 aux.wait_stream(main)
                 aux.wait_event(value_ready)
-            mlp_backward(self._actor_layers, saved_a, ws["dmu"], ws["mlp_a"], head_dprev=heads["a"])
+            dh_a = mlp_backward(self._actor_layers, saved_a, ws["dmu"], ws["mlp_a"], head_dprev=heads["a"], stop_above_first=wide0,
+                                flush=not wide0)
             with torch.cuda.stream(side):
-                mlp_backward(self._critic_layers, saved_c, ws["dvalue"], ws["mlp_c"], head_dprev=heads["c"])
+                dh_c = mlp_backward(self._critic_layers, saved_c, ws["dvalue"], ws["mlp_c"], head_dprev=heads["c"], stop_above_first=wide0,
+                                    flush=not wide0)
+                if wide0:
+                    dh0_ready = torch.cuda.Event()
+                    dh0_ready.record(side)  # behind the critic's dX GEMM: the stacked launch does not wait for the critic's reduction
+                    dh_c.record_stream(main)
+                    check(L.imx_reduce_batch_begin(ws["mlp_c"].handle))
+                    check(L.imx_reduce_batch_flush(ws["mlp_c"].handle, side.cuda_stream))
                 if loss_on_side:
                     side.wait_event(mu_ready)
                     loss_values(mu, value, side.cuda_stream)
             if not loss_on_side:
                 with torch.cuda.stream(aux):
                     loss_values(mu, value, aux.cuda_stream)
+            if wide0:
+                main.wait_event(dh0_ready)  # directly in front of the launch that needs it: nothing else queues behind the wait
+                stacked_dw0(dh_a, dh_c, stream)
             main.wait_stream(side)
             if not loss_on_side:
                 main.wait_stream(aux)
@@ -854,8 +911,11 @@ class PPO:
             mu, saved_a = actor_pass(stream)
             value, saved_c = critic_pass(stream)
             loss_values(mu, value, stream)
-            mlp_backward(self._actor_layers, saved_a, ws["dmu"], ws["mlp_a"], head_dprev=heads["a"])
-            mlp_backward(self._critic_layers, saved_c, ws["dvalue"], ws["mlp_c"], head_dprev=heads["c"])
+            dh_a = mlp_backward(self._actor_layers, saved_a, ws["dmu"], ws["mlp_a"], head_dprev=heads["a"], stop_above_first=wide0,
+                                flush=not wide0)
+            dh_c = mlp_backward(self._critic_layers, saved_c, ws["dvalue"], ws["mlp_c"], head_dprev=heads["c"], stop_above_first=wide0)
+            if wide0:
+                stacked_dw0(dh_a, dh_c, stream)
         return self._out8
 
     update_graph = False  # set by the runner (use_graph=True): the update may run as one hipGraph replay, see update()

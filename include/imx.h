@@ -592,13 +592,30 @@ int imx_frame_transformer(int64_t N, int num_targets, int num_bodies, const floa
                           float* target_pos_w_d, float* target_quat_w_d, float* target_pos_source_d, float* target_quat_source_d,
                           imx_stream_t stream);
 
+/* ---- RayCaster (sensors/ray_caster/ray_caster.py, sensors/sensor_base.py): imx_ray_caster ---------------------------------------
+ * One launch, one block per env, for a sensor with any ray pattern and the full orientation of the body it sits on.  The sensor
+ * travels in imx_ray_caster_t (imx_ray_caster_struct.h, which this header includes).  Per env, in the reference's order: reset (the envs
+ * of reset_mask_d: clocks to zero, outdated, a new drift), the clocks (substeps times timestamp += dt, outdated once the update period
+ * has passed), and with `refresh` the cast for the outdated envs only -- pos_w = body_pos + drift, quat_w, ray_hits_w (+inf on a miss)
+ * and the optional range image and world rays; the other envs keep what they had.  The rays go through the z-pruned grid walk of
+ * csrc/imx_ray_walk.h, whose hit is the closest one of ALL triangles with t in [0, max_distance], bit for bit what imx_raycast gives.
+ *   imx_mesh_build_ray_bounds: the walk's z-bounds (8 bytes per grid cell and per 8x8 tile), built once per mesh on the device from the
+ *   cell records, reference lists and triangle records; synchronises and allocates, so not inside a stream capture.  imx_ray_caster
+ *   builds them itself on a mesh that has none (same restriction for that first call).  info4 (may be NULL) = bytes of the bounds, build
+ *   time in nanoseconds (host clock around the build, 0 when they existed), grid cells, tiles.
+ * Every NULL pointer or out-of-range value is refused and named in imx_last_error before any launch. */
+typedef struct imx_ray_caster imx_ray_caster_t;
+#include "imx_ray_caster_struct.h" /* the definition of imx_ray_caster_t */
+int imx_mesh_build_ray_bounds(imx_mesh_t* mesh, imx_stream_t stream, int64_t* info4);
+int imx_ray_caster(const imx_ray_caster_t* sensor, int64_t N, imx_mesh_t* mesh, imx_stream_t stream);
+
 /* ---- library ---------------------------------------------------------------------------------------------------- */
 const char* imx_version(void);
 /* sizeof of an ABI struct as this library was compiled (which: 0 imx_state_t, 1 imx_buffers_t, 2 imx_head_loss_t, 3 imx_rollout_slot_t, 4 imx_policy_act_t, 5 imx_orch_t, 6 imx_event_term_t,
  * 7 imx_diff_ik_t, 8 imx_osc_t, 10 imx_orch_manip_t, 11 imx_weight_term_t, 12 imx_pretrained_policy_t,
  * 13 imx_pose2d_command_t, 15 imx_inhand_command_t, 16 imx_object_state_t, 18 imx_articulation_state_t,
- * 20 imx_orch_articulation_t, 22 imx_norm_group_t, 23 imx_infer_norm_t), 0 for an unknown index
- * (9, 14, 17, 19 and 21 are):
+ * 20 imx_orch_articulation_t, 22 imx_norm_group_t, 23 imx_infer_norm_t, 25 imx_ray_caster_t), 0 for an unknown index
+ * (9, 14, 17, 19, 21 and 24 are):
  * a binding checks its own layout against it at load time. */
 size_t imx_struct_size(int which);
 const char* imx_last_error(void);

@@ -189,5 +189,9 @@ try:
     NORMALIZATION_HEADER = os.path.join(os.path.dirname(HEADER), "imx_normalization_struct.h")
     with open(NORMALIZATION_HEADER) as _f:
         _, _, NORMALIZATION_STRUCTS, _ = parse(_f.read(), NORMALIZATION_HEADER, DEFINES)
+    # imx_ray_caster_struct.h, likewise: imx_ray_caster_t (imx_ray_caster)
+    RAY_CASTER_HEADER = os.path.join(os.path.dirname(HEADER), "imx_ray_caster_struct.h")
+    with open(RAY_CASTER_HEADER) as _f:
+        _, _, RAY_CASTER_STRUCTS, _ = parse(_f.read(), RAY_CASTER_HEADER, DEFINES)
 except OSError as e:
     raise AbiError(f"the ABI header {HEADER} cannot be read ({e}): the whole binding is derived from it") from e

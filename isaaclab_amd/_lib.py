@@ -111,6 +111,9 @@ ImxNormGroup = type("ImxNormGroup", (ctypes.Structure,), {"_fields_": [(field, _
                                                                       for field, t in _abi.NORMALIZATION_STRUCTS["imx_norm_group_t"]]})
 ImxInferNorm = type("ImxInferNorm", (ctypes.Structure,), {"_fields_": [(field, _abi.ctype(t, _STRUCTS))
                                                                       for field, t in _abi.NORMALIZATION_STRUCTS["imx_infer_norm_t"]]})
+# (imx_ray_caster_struct.h, the same way)
+ImxRayCaster = type("ImxRayCaster", (ctypes.Structure,), {"_fields_": [(field, _abi.ctype(t, _STRUCTS))
+                                                                      for field, t in _abi.RAY_CASTER_STRUCTS["imx_ray_caster_t"]]})
 FRAME_WORDS = _abi.DEFINES["IMX_FRAME_WORDS"]
 FT_HEADER_WORDS = _abi.DEFINES["IMX_FT_HEADER_WORDS"]
 if set(_STRUCTS) != set(_abi.STRUCTS):
@@ -129,7 +132,7 @@ _BY_POINTER = {**_STRUCTS, "imx_pretrained_policy_t": ImxPretrainedPolicy, "imx_
                "imx_inhand_command_t": ImxInhandCommand, "imx_object_state_t": ImxObjectState,
                "imx_articulation_state_t": ImxArticulationState,
                "imx_orch_articulation_t": ImxOrchArticulation, "imx_norm_group_t": ImxNormGroup,
-               "imx_infer_norm_t": ImxInferNorm}  # (a struct of an included header travels as POINTER(class) too)
+               "imx_infer_norm_t": ImxInferNorm, "imx_ray_caster_t": ImxRayCaster}  # (a struct of an included header travels as POINTER(class) too)
 _SIGNATURES = {name: (_abi.ctype(res, _BY_POINTER, ret=True), [_abi.ctype(t, _BY_POINTER) for t in args])
                for name, (res, args, _) in _abi.FUNCTIONS.items()}
 EXPORTS = tuple(_SIGNATURES)
@@ -159,7 +162,7 @@ def lib():
     for which, cls in (*enumerate((ImxState, ImxBuffers, ImxHeadLoss, ImxRolloutSlot, ImxPolicyAct, ImxOrch, ImxEventTerm, ImxDiffIk, ImxOsc)),
                        (10, ImxOrchManip), (11, ImxWeightTerm), (12, ImxPretrainedPolicy), (13, ImxPose2dCommand), (15, ImxInhandCommand), (16, ImxObjectState),
                        (18, ImxArticulationState), (20, ImxOrchArticulation), (22, ImxNormGroup),
-                       (23, ImxInferNorm)):  # the binding's struct layouts against the library's (indices 9, 14, 17, 19 and 21 are unknown)
+                       (23, ImxInferNorm), (25, ImxRayCaster)):  # the binding's struct layouts against the library's (indices 9, 14, 17, 19, 21 and 24 are unknown)
         if int(L.imx_struct_size(which)) != ctypes.sizeof(cls):
             raise ImxError(f"{LIB_PATH}: sizeof({cls.__name__}) is {int(L.imx_struct_size(which))} in the library, {ctypes.sizeof(cls)} in the "
                            "binding -- rebuild with `python -m isaaclab_amd.build`")

@@ -43,6 +43,7 @@ extern "C" size_t imx_struct_size(int which) {
         case 20: return sizeof(imx_orch_articulation_t);
         case 22: return sizeof(imx_norm_group_t);
         case 23: return sizeof(imx_infer_norm_t);
+        case 25: return sizeof(imx_ray_caster_t);
         default: return 0;
     }
 }

@@ -122,6 +122,12 @@ struct imx_mesh {
     int64_t num_refs = 0;  // general cell references
     int32_t max_refs = 0;
     int64_t n_lattice = 0, n_general = 0, n_flat = 0;  // n_general counts QH (n_flat) and GENERAL cells
+    // z-bounds of the general-ray walk (imx_ray_walk.h: RayBoundsView), built on first use by imx_mesh_build_ray_bounds (ray_caster.hip);
+    // a view of their own: MeshView, which every existing ray kernel takes by value, stays as it is
+    float* d_ray_cell_z = nullptr;  // (ntx*nty*64, 2)
+    float* d_ray_tile_z = nullptr;  // (ntx*nty, 2)
+    float ray_zmin = 0.0f, ray_zmax = 0.0f;
+    int64_t ray_bounds_ns = 0;      // what the build took
 };
 // linear index of cell (ix, iy) in the 8x8-tiled layout
 static __host__ __device__ __forceinline__ int imx_cell_index(int ix, int iy, int ntx) {

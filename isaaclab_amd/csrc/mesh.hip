@@ -532,6 +532,8 @@ extern "C" void imx_mesh_destroy(imx_mesh_t* m) {
     if (m->d_gx) (void)hipFree(m->d_gx);
     if (m->d_gy) (void)hipFree(m->d_gy);
     if (m->d_refs) (void)hipFree(m->d_refs);
+    if (m->d_ray_cell_z) (void)hipFree(m->d_ray_cell_z);
+    if (m->d_ray_tile_z) (void)hipFree(m->d_ray_tile_z);
     delete m;
 }
 

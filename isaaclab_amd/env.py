@@ -630,6 +630,55 @@ class _FrameSensor:
         return self._sensor.data
 
 
+class _RaySensor:
+    """``env.scene[<RayCaster>]`` for a ray caster that no ``height_scan`` term of the plan reads (a lidar): a ``producers.RayCaster`` on
+    the terrain mesh, fed the pose of the body its ``prim_path`` ends in (the root pose for the articulation root) from the state feed.
+    The env advances its clocks ``decimation`` times ``physics_dt`` per step and resets it with its own reset mask; ``data`` refreshes the
+    outdated envs lazily (``SensorBase.data``) -- on the eager path only: it is no part of a captured rollout."""
+
+    def __init__(self, env, entity):
+        from .producers import RayCaster
+
+        cfg = env._entities.ray_casters[entity]
+        self._env, self.cfg = env, cfg
+        body = str(cfg.get("prim_path", "")).rstrip("/").rsplit("/", 1)[-1]
+        names = list(env.plan.robot.body_names)
+        if body in ("Robot", "robot") or (names and body == names[0]):
+            self._body = None  # the articulation root
+        elif body in names:
+            self._body = names.index(body)
+        else:
+            raise ValueError(f"RayCaster '{entity}': its prim_path ends in '{body}', which is no body of the robot ({names})")
+        self._sensor = RayCaster(cfg, env.num_envs, env.device, env._ray_mesh(entity), seed=env._noise_seed)
+        N = env.num_envs
+        self._bp, self._bq = torch.zeros(N, 3, device=env.device), torch.zeros(N, 4, device=env.device)
+        self.num_rays, self.ray_starts, self.ray_directions = self._sensor.num_rays, self._sensor.ray_starts, self._sensor.ray_directions
+
+    def _pose(self):
+        f = self._env.feed
+        if self._body is None:
+            return f["root_pos_w"].contiguous(), f["root_quat_w"].contiguous()
+        self._bp.copy_(f["body_pos_w"][:, self._body])
+        self._bq.copy_(f["body_quat_w"][:, self._body])
+        return self._bp, self._bq
+
+    def _step(self):  # scene.update(physics_dt), decimation times, after the physics of an env step
+        env = self._env
+        self._sensor.update(env.physics_dt, *self._pose(), substeps=int(env.cfg_decimation))
+
+    def _reset(self, env_ids=None):  # scene.reset(env_ids)
+        self._sensor.reset(env_ids)
+
+    @property
+    def data(self):
+        self._sensor._pose = self._pose()
+        return self._sensor.data
+
+    def ranges(self, range_clip: float):
+        self._sensor._pose = self._pose()
+        return self._sensor.ranges(range_clip)
+
+
 class _Scene:
     def __init__(self, env):
         r = env.plan.robot
@@ -639,6 +688,8 @@ class _Scene:
         for name, spec in env._entities.articulations.items():  # the second articulation (the Open-Drawer task's cabinet)
             self._e[name] = _SecondArticulation(env, spec)
         self._frame_names = list(env._entities.frames)  # FrameTransformer sensors: built on first access (a scene that is never asked launches nothing)
+        # RayCaster sensors that no height_scan term reads (the plan's scanner is fused into the observation kernel): likewise on first access
+        self._ray_names = [k for k in env._entities.ray_casters if not (k == "height_scanner" and env.plan.num_rays > 0)]
         self._env = env
         self.num_envs = env.num_envs
 
@@ -647,11 +698,14 @@ class _Scene:
         return self._env.feed["env_origins"]
 
     def keys(self):
-        return list(self._e) + [k for k in self._frame_names if k not in self._e]
+        return list(self._e) + [k for k in self._frame_names + self._ray_names if k not in self._e]
 
     def __getitem__(self, k):
         if k not in self._e and k in self._frame_names:
             self._e[k] = self.sensors[k] = _FrameSensor(self._env, k)
+        elif k not in self._e and k in self._ray_names:
+            self._e[k] = self.sensors[k] = _RaySensor(self._env, k)
+            self._env._ray_sensors.append(self._e[k])
         return self._e[k]
 
 
@@ -770,6 +824,8 @@ class ManagerBasedRLEnv:
         self.num_envs = N
         extent = None
         self.terrain: TerrainMesh | None = None
+        self._terrain_arg, self._terrain_cell = terrain, terrain_cell  # (a RayCaster of the scene other than the height scanner builds its mesh on first access)
+        self._ray_sensors: list = []  # the scene's _RaySensor objects built so far (scene[...]): stepped and reset with the env
         if plan.num_rays > 0:
             if terrain is None:
                 raise ValueError("this config has a height scanner: pass terrain=(vertices, triangles)")
@@ -1687,6 +1743,8 @@ class ManagerBasedRLEnv:
             self.contact_sensor.reset(None if env_ids is None else env_ids)
         if self.actuator_net is not None:
             self.actuator_net.reset(None if env_ids is None else env_ids)
+        for rs in self._ray_sensors:
+            rs._reset(None if env_ids is None else env_ids)
         if self._has_orchestration:
             # _reset_idx(env_ids) (manager_based_rl_env.py:347-392): curriculum, scene.reset, reset events, manager resets with their
             # log entries -- no command compute, no interval events (those belong to step()).  Host-side reductions are fine here
@@ -1752,6 +1810,8 @@ class ManagerBasedRLEnv:
         if self.contact_sensor is not None:
             # scene.update -> ContactSensor.update: the feed delivers one force sample per env step (history slot 0)
             self.contact_sensor.update(self.feed["net_forces_w_history"][:, 0], self.step_dt)
+        for rs in self._ray_sensors:  # scene.update -> RayCaster.update: the clocks only, the cast waits for `data`
+            rs._step()
         self.common_step_counter += 1
         # -- post-physics: counters, terminations, rewards, reset bookkeeping (one kernel)
         if self._ext_funcs["rew"] or self._ext_funcs["term"]:
@@ -1769,6 +1829,8 @@ class ManagerBasedRLEnv:
                                                          _lib.current_stream(self.device)))
         # (the resets of this step log the metrics as they stand before this step's CommandManager.compute)
         self.extras["log"] = self._log_views if not self._pose2d_command or "error_pos_2d" in self.command_term.metrics else self._log_views_before_compute
+        for rs in self._ray_sensors:  # _reset_idx -> scene.reset(env_ids): on the device, by the reset mask
+            rs._reset(self.reset_buf)
         if self._class_terms:
             # _reset_idx reaches the class terms between the reward and the observation pass (manager_based_rl_env.py:215-218 ->
             # RewardManager.reset / ObservationManager.reset).  This route is Python-evaluated anyway: the ids are read like the
@@ -1786,6 +1848,16 @@ class ManagerBasedRLEnv:
         #    this state snapshot behind (the feed's root state is not rewritten by the reset events: they go to sim_writes)
         self._compute_observations(frame_current=True, finish_step_tail=self.defer_step_tail)
         return self.observation_manager.shaped(), self._reward_buf, self.reset_terminated, self.reset_time_outs, self.extras
+
+    def _ray_mesh(self, entity: str) -> TerrainMesh:
+        """The mesh a RayCaster of the scene casts against: the env's terrain (``terrain=``)."""
+        if self.terrain is None:
+            t = self._terrain_arg
+            if t is None:
+                raise NotImplementedError(f"RayCaster '{entity}': the env has no terrain mesh (a plane terrain, or terrain= was not given): "
+                                          "the sensor casts against a TerrainMesh")
+            self.terrain = t if isinstance(t, TerrainMesh) else TerrainMesh(t[0], t[1], self._terrain_cell)
+        return self.terrain
 
     @property
     def cfg_decimation(self) -> int:

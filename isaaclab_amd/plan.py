@@ -521,6 +521,74 @@ def grid_pattern(resolution: float, size, direction=(0.0, 0.0, -1.0), ordering: 
     return starts, dirs
 
 
+def _pattern_field(cfg, name, default=None):
+    v = cfg.get(name, default) if isinstance(cfg, dict) else getattr(cfg, name, default)
+    if v is None or (isinstance(v, str) and v == "MISSING") or type(v).__name__ == "_MISSING_TYPE":
+        raise ValueError(f"ray pattern cfg: '{name}' is missing")
+    return v
+
+
+_BPEARL_VERTICAL_RAY_ANGLES = (  # BpearlPatternCfg.vertical_ray_angles (patterns_cfg.py:188-192): the sensor's 32 unevenly spaced rings
+    89.5, 86.6875, 83.875, 81.0625, 78.25, 75.4375, 72.625, 69.8125, 67.0, 64.1875, 61.375, 58.5625, 55.75, 52.9375, 50.125, 47.3125, 44.5,
+    41.6875, 38.875, 36.0625, 33.25, 30.4375, 27.625, 24.8125, 22, 19.1875, 16.375, 13.5625, 10.75, 7.9375, 5.125, 2.3125)
+
+
+def bpearl_pattern(cfg):
+    """``bpearl_pattern`` (isaaclab/sensors/ray_caster/patterns/patterns.py:106-133) of a ``BpearlPatternCfg`` or its dict form, the same
+    torch ops in the same order on the CPU: (starts, directions), (R, 3) float32 arrays; the vertical angle runs fastest."""
+    import torch
+
+    fov, res = _pattern_field(cfg, "horizontal_fov", 360.0), _pattern_field(cfg, "horizontal_res", 10.0)
+    h = torch.arange(-fov / 2, fov / 2, res)
+    v = torch.tensor(list(_pattern_field(cfg, "vertical_ray_angles", _BPEARL_VERTICAL_RAY_ANGLES)))
+    pitch, yaw = torch.meshgrid(v, h, indexing="xy")
+    pitch, yaw = torch.deg2rad(pitch.reshape(-1)), torch.deg2rad(yaw.reshape(-1))
+    pitch += torch.pi / 2
+    x = torch.sin(pitch) * torch.cos(yaw)
+    y = torch.sin(pitch) * torch.sin(yaw)
+    z = torch.cos(pitch)
+    dirs = -torch.stack([x, y, z], dim=1)
+    return torch.zeros_like(dirs).numpy(), dirs.numpy()
+
+
+def lidar_pattern(cfg):
+    """``lidar_pattern`` (patterns.py:136-179) of a ``LidarPatternCfg`` or its dict form: a full 360 degree range drops its last azimuth,
+    the azimuth count is ``math.ceil(span / horizontal_res)``; the azimuth runs fastest."""
+    import torch
+
+    vr, hr = _pattern_field(cfg, "vertical_fov_range"), _pattern_field(cfg, "horizontal_fov_range")
+    vertical_angles = torch.linspace(vr[0], vr[1], int(_pattern_field(cfg, "channels")))
+    up_to = -1 if abs(abs(hr[0] - hr[1]) - 360.0) < 1e-6 else None
+    n = math.ceil((hr[1] - hr[0]) / _pattern_field(cfg, "horizontal_res"))
+    horizontal_angles = torch.linspace(hr[0], hr[1], n)[:up_to]
+    v_angles, h_angles = torch.meshgrid(torch.deg2rad(vertical_angles), torch.deg2rad(horizontal_angles), indexing="ij")
+    x = torch.cos(v_angles) * torch.cos(h_angles)
+    y = torch.cos(v_angles) * torch.sin(h_angles)
+    z = torch.sin(v_angles)
+    dirs = torch.stack([x, y, z], dim=-1).reshape(-1, 3)
+    return torch.zeros_like(dirs).numpy(), dirs.numpy()
+
+
+def ray_pattern(pattern_cfg):
+    """(starts, directions) of a ray-caster ``pattern_cfg`` (object or ``to_dict()`` form, ``func`` a callable or its
+    ``module:function`` name): ``grid_pattern``, ``bpearl_pattern`` or ``lidar_pattern``.  ``pinhole_camera_pattern`` is refused by name."""
+    func = pattern_cfg.get("func") if isinstance(pattern_cfg, dict) else getattr(pattern_cfg, "func", None)
+    if func is None:
+        raise ValueError("ray pattern cfg: 'func' is missing")
+    name = _short(func_name(func))[1].rsplit(".", 1)[-1]
+    if name == "pinhole_camera_pattern":
+        raise NotImplementedError("pinhole_camera_pattern belongs to the camera sensors (RayCasterCamera), which are out of scope: "
+                                  "the RayCaster takes grid_pattern, bpearl_pattern and lidar_pattern")
+    if name == "bpearl_pattern":
+        return bpearl_pattern(pattern_cfg)
+    if name == "lidar_pattern":
+        return lidar_pattern(pattern_cfg)
+    if name == "grid_pattern":
+        return grid_pattern(_pattern_field(pattern_cfg, "resolution"), _pattern_field(pattern_cfg, "size"),
+                            tuple(_pattern_field(pattern_cfg, "direction", (0.0, 0.0, -1.0))), _pattern_field(pattern_cfg, "ordering", "xy"))
+    raise NotImplementedError(f"ray pattern '{name}' is not known (grid_pattern, bpearl_pattern, lidar_pattern)")
+
+
 def _quat_apply_np(q, v):
     w, xyz = np.float32(q[0]), np.asarray(q[1:], np.float32)
     t = np.cross(xyz, v).astype(np.float32) * np.float32(2)

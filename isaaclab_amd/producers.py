@@ -12,6 +12,8 @@
   (isaaclab_tasks .../manipulation/inhand/mdp/commands/orientation_command.py:22-124), stand-alone: no env runs it yet
 * :class:`FrameTransformer` -- the sensor's six data tensors from an articulation's body poses
   (isaaclab/sensors/frame_transformer/frame_transformer.py:337-384)
+* :class:`RayCaster` -- the ray-caster sensor with any ray pattern (grid, Bpearl, lidar) and the full orientation of its body, one
+  launch per update (isaaclab/sensors/ray_caster/ray_caster.py:107-114,201-260; isaaclab/sensors/sensor_base.py:182-205,287-296)
 
 Attribute names follow the reference so that term functions reading ``sensor.data.*`` / ``command_manager`` keep working.
 """
@@ -732,3 +734,149 @@ class FrameTransformer:
                                           self._frames_h.ctypes.data, p(d.source_pos_w), p(d.source_quat_w), p(d.target_pos_w), p(d.target_quat_w),
                                           p(d.target_pos_source), p(d.target_quat_source), _lib.current_stream(self.device)))
         return d
+
+
+def _cfg_field(cfg, name, default=None):
+    return cfg.get(name, default) if isinstance(cfg, dict) else getattr(cfg, name, default)
+
+
+class RayCaster:
+    """``RayCaster`` (isaaclab/sensors/ray_caster/ray_caster.py under ``SensorBase``, sensors/sensor_base.py:182-205,287-296) with any of
+    the ray patterns of ``plan.ray_pattern`` (grid, Bpearl, lidar) and the full orientation of the body it sits on, in one launch
+    (``imx_ray_caster``): reset, clocks, and for the outdated envs the pose, the world rays, the cast through the z-pruned grid walk and
+    the optional range image.
+
+    ``cfg``: the ``RayCasterCfg`` as object or dict -- ``pattern_cfg``, ``offset.pos`` / ``.rot``, ``attach_yaw_only``, ``max_distance``,
+    ``drift_range``, ``update_period``, ``mesh_prim_paths`` (at most one).  ``mesh``: the ``TerrainMesh`` the rays are cast against.
+    ``keep_world_rays``: also store the world-frame starts and directions of the last cast (``ray_starts_w`` / ``ray_directions_w``).
+
+    ``update(dt, body_pos_w, body_quat_w)`` is ``SensorBase.update``: without ``force_recompute`` only the clocks and flags advance;
+    ``data`` refreshes the outdated envs lazily, from the poses given last, and has ``pos_w`` (N, 3), ``quat_w`` (N, 4) and ``ray_hits_w``
+    (N, R, 3; +inf on a miss).  ``ranges(clip)`` is the (N, R) range image ``min(||ray_hits_w - pos_w||, clip)``."""
+
+    def __init__(self, cfg, num_envs: int, device, mesh, seed: int = 0, keep_world_rays: bool = False):
+        from .plan import ray_pattern
+
+        pc = _cfg_field(cfg, "pattern_cfg")
+        if pc is None:
+            raise ValueError("RayCaster: cfg.pattern_cfg is missing")
+        starts, dirs = ray_pattern(pc)  # (refuses the pinhole pattern by name)
+        paths = _cfg_field(cfg, "mesh_prim_paths")
+        if paths is not None and not isinstance(paths, str) and len(paths) != 1:
+            raise NotImplementedError(f"RayCaster currently only supports one mesh prim. Received: {len(paths)}")  # ray_caster.py:153-156
+        if mesh is None:
+            raise NotImplementedError("RayCaster: the terrain has no mesh (a plane): the rays are cast against a TerrainMesh; a ground plane "
+                                      "as an infinite mesh is not built")
+        N, dev = int(num_envs), torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        off = _cfg_field(cfg, "offset") or {}
+        off_pos = torch.tensor(list(_cfg_field(off, "pos", (0.0, 0.0, 0.0))), dtype=torch.float32)
+        off_rot = torch.tensor(list(_cfg_field(off, "rot", (1.0, 0.0, 0.0, 0.0))), dtype=torch.float32)
+        # _initialize_rays_impl (ray_caster.py:201-212): directions through quat_apply(offset.rot), starts + offset.pos, in fp32 on the host
+        d = torch.from_numpy(np.ascontiguousarray(dirs, np.float32))
+        xyz = off_rot[1:].repeat(len(d), 1)
+        t = xyz.cross(d, dim=-1) * 2
+        d = d + off_rot[0] * t + xyz.cross(t, dim=-1)
+        s = torch.from_numpy(np.ascontiguousarray(starts, np.float32)) + off_pos
+        self.num_envs, self.device, self.mesh, self.seed = N, dev, mesh, int(seed)
+        self.num_rays = R = int(d.shape[0])
+        self.ray_starts, self.ray_directions = s.contiguous().to(dev), d.contiguous().to(dev)  # (R, 3): every env has the same pattern
+        dr = tuple(float(x) for x in _cfg_field(cfg, "drift_range", (0.0, 0.0)))
+        self.cfg = types.SimpleNamespace(attach_yaw_only=bool(_cfg_field(cfg, "attach_yaw_only", False)),
+                                         max_distance=float(_cfg_field(cfg, "max_distance", 1.0e6)), drift_range=dr,
+                                         update_period=float(_cfg_field(cfg, "update_period", 0.0)), pattern_cfg=pc)
+        if dr[0] > dr[1]:
+            raise ValueError(f"RayCaster: drift_range {dr}: the lower bound exceeds the upper")
+        z = lambda *sh, dtype=torch.float32: torch.zeros(*sh, dtype=dtype, device=dev)  # noqa: E731
+        self._timestamp, self._timestamp_last_update = z(N), z(N)
+        self._is_outdated = torch.ones(N, dtype=torch.bool, device=dev)  # sensor_base.py:_initialize_impl
+        self.drift = z(N, 3)
+        self._reset_count = z(N, dtype=torch.int32)
+        self._all = torch.ones(N, dtype=torch.bool, device=dev)
+        self._data = types.SimpleNamespace(pos_w=z(N, 3), quat_w=z(N, 4), ray_hits_w=z(N, R, 3))
+        self._ranges = z(N, R)
+        self.ray_starts_w = z(N, R, 3) if keep_world_rays else None
+        self.ray_directions_w = z(N, R, 3) if keep_world_rays else None
+        self._pose = None
+        self.bounds_info = None
+        if dev.type == "cuda":  # the walk's z-bounds, once per mesh (allocates and synchronises: here, not in a launch that may be captured)
+            info = (ctypes.c_int64 * 4)()
+            check(lib().imx_mesh_build_ray_bounds(mesh.handle, _lib.current_stream(dev), info))
+            self.bounds_info = {"bytes": int(info[0]), "build_ns": int(info[1]), "cells": int(info[2]), "tiles": int(info[3])}
+        p = _lib.ptr
+        self._c = _lib.ImxRayCaster(num_rays=R, attach_yaw_only=int(self.cfg.attach_yaw_only), max_distance=self.cfg.max_distance,
+                                    update_period=self.cfg.update_period, drift_lo=dr[0], drift_hi=dr[1], seed=self.seed & (2 ** 64 - 1),
+                                    ray_starts_d=p(self.ray_starts), ray_directions_d=p(self.ray_directions), reset_count_d=p(self._reset_count),
+                                    timestamp_d=p(self._timestamp), timestamp_last_update_d=p(self._timestamp_last_update),
+                                    is_outdated_d=p(self._is_outdated), drift_d=p(self.drift), pos_w_d=p(self._data.pos_w),
+                                    quat_w_d=p(self._data.quat_w), ray_hits_w_d=p(self._data.ray_hits_w),
+                                    ray_starts_w_d=p(self.ray_starts_w), ray_directions_w_d=p(self.ray_directions_w))
+
+    def _check_pose(self, body_pos_w, body_quat_w):
+        N = self.num_envs
+        if tuple(body_pos_w.shape) != (N, 3) or tuple(body_quat_w.shape) != (N, 4):
+            raise ValueError(f"RayCaster: body_pos_w / body_quat_w must be ({N}, 3) / ({N}, 4), got {tuple(body_pos_w.shape)} / {tuple(body_quat_w.shape)}")
+        for t in (body_pos_w, body_quat_w):
+            if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"RayCaster: body poses must be contiguous float32 tensors on {self.device}")
+
+    def _launch(self, dt=0.0, substeps=0, refresh=False, reset_mask=None, uniforms=None, range_clip=None):
+        if self._pose is None:
+            raise RuntimeError("RayCaster: no body pose yet: call update(dt, body_pos_w, body_quat_w) first")
+        c = self._c
+        c.dt, c.substeps, c.refresh = float(dt), int(substeps), int(bool(refresh))
+        c.body_pos_w_d, c.body_quat_w_d = _lib.ptr(self._pose[0]), _lib.ptr(self._pose[1])
+        c.reset_mask_d, c.uniforms_d = _lib.ptr(reset_mask), _lib.ptr(uniforms)
+        c.ranges_d, c.range_clip = (_lib.ptr(self._ranges), float(range_clip)) if range_clip is not None else (None, 0.0)
+        check(lib().imx_ray_caster(ctypes.byref(c), self.num_envs, self.mesh.handle, _lib.current_stream(self.device)))
+
+    def _mask(self, env_ids):
+        N = self.num_envs
+        if env_ids is None or isinstance(env_ids, slice) and env_ids == slice(None):
+            return self._all
+        ids = torch.as_tensor(env_ids, device=self.device)
+        if ids.dtype in (torch.bool, torch.uint8) and tuple(ids.shape) == (N,):
+            return ids.contiguous()
+        m = torch.zeros(N, dtype=torch.bool, device=self.device)
+        m[ids.long()] = True
+        return m
+
+    def _uniforms(self, uniforms):
+        if uniforms is None:
+            return None
+        if tuple(uniforms.shape) != (self.num_envs, 3) or uniforms.dtype != torch.float32 or uniforms.device != self.device:
+            raise ValueError(f"RayCaster: uniforms must be a ({self.num_envs}, 3) float32 tensor on {self.device}")
+        return uniforms.contiguous()
+
+    def reset(self, env_ids=None, uniforms=None):
+        """``SensorBase.reset`` + ``RayCaster.reset`` for ``env_ids`` (None = all; indices or an (N,) mask): clocks to zero, outdated, a new
+        drift from the counter-based generator or from ``uniforms`` (N, 3) in [0, 1)."""
+        if self._pose is None:  # (a reset before the first update reads no pose: the launch only needs valid pointers)
+            self._pose = (self._data.pos_w, self._data.quat_w)
+            try:
+                self._launch(reset_mask=self._mask(env_ids), uniforms=self._uniforms(uniforms))
+            finally:
+                self._pose = None
+            return
+        self._launch(reset_mask=self._mask(env_ids), uniforms=self._uniforms(uniforms))
+
+    def update(self, dt: float, body_pos_w: torch.Tensor, body_quat_w: torch.Tensor, force_recompute: bool = False, substeps: int = 1,
+               reset_mask=None, uniforms=None):
+        """``SensorBase.update(dt)``, ``substeps`` times, on the pose of the body the sensor sits on (kept by reference for ``data``);
+        ``reset_mask`` (N,): those envs are reset first, in the same launch.  With ``force_recompute`` the outdated envs are refreshed."""
+        self._check_pose(body_pos_w, body_quat_w)
+        self._pose = (body_pos_w, body_quat_w)
+        self._launch(dt=dt, substeps=substeps, refresh=force_recompute, reset_mask=None if reset_mask is None else self._mask(reset_mask),
+                     uniforms=self._uniforms(uniforms))
+
+    @property
+    def data(self):
+        """``SensorBase.data``: ``_update_outdated_buffers`` first (one launch; an env that is not outdated leaves it at once)."""
+        self._launch(refresh=True)
+        return self._data
+
+    def ranges(self, range_clip: float) -> torch.Tensor:
+        """(N, R) ``min(||ray_hits_w - pos_w||, range_clip)``, a miss = ``range_clip``, after the refresh of ``data`` (same launch)."""
+        self._launch(refresh=True, range_clip=range_clip)
+        return self._ranges

@@ -234,6 +234,7 @@ class SceneEntityResolver:
         self.body_names = list(robot.body_names)
         self.rigid_objects: dict[str, str] = {}  # entity -> its one body's name
         self.frames: dict[str, dict] = {}
+        self.ray_casters: dict[str, dict] = {}  # RayCaster entries (the env serves those no height_scan term reads through producers.RayCaster)
         self.articulations: dict[str, SecondArticulation] = {}
         for name, ent in (scene or {}).items():
             cls = ent.get("class_type") if isinstance(ent, dict) else None
@@ -242,6 +243,8 @@ class SceneEntityResolver:
                 self.rigid_objects[name] = str(ent.get("prim_path", name)).rstrip("/").rsplit("/", 1)[-1]
             elif cls and cls.endswith(":FrameTransformer"):
                 self.frames[name] = ent
+            elif cls and cls.endswith(":RayCaster"):
+                self.ray_casters[name] = ent
             elif cls and cls.endswith(":Articulation") and name != "robot":
                 self.articulations[name] = SecondArticulation.from_scene_entry(name, ent)
         if len(self.articulations) > 1:

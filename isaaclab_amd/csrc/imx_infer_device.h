@@ -1,6 +1,5 @@
-// The MFMA inference layers shared by the rollout inference kernels (mlp.hip) and the fused low-level policy step
-// (pretrained_policy.hip).  Moved here from mlp.hip unchanged: every kernel that used them compiles to the instruction stream it had
-// ("Low-level policy step").
+// The MFMA inference layers and the loop over them (infer_layers, at the end), shared by the rollout inference kernels (mlp.hip) and the
+// fused low-level policy step (pretrained_policy.hip) ("Low-level policy step").
 #pragma once
 
 #include "imx_internal.h"
@@ -224,4 +223,50 @@ __device__ __forceinline__ void infer_layer16(const float* __restrict__ sIn, int
             }
         }
     }
+}
+
+// The layers of one tile of ROWS (16 or 32) samples: what the rollout inference kernels and k_pretrained_policy do between their input
+// tile and their epilogue.  The activations ping-pong between the LDS buffers `in` and `out`; per layer: zero the padding columns the
+// next layer's 32-wide reduction groups will read, pick the column blocks per wave, run the layer, barrier, swap.  Returns the pair after
+// the last swap: `in` is the buffer the last layer wrote (if it wrote to LDS), `out` the other one.
+//   net       a struct with nlayers, dim[], ldw[], b[], alpha (InferNet, PolicyArgs)
+//   W         the row layouts, or for <32, true> the packed images
+//   last_to_lds / gout()   the last layer's output stays in LDS, or goes to the global rows gout() ((M, dim[nlayers]), rows past M dropped)
+// How the arguments are passed is part of the kernels' register figures (NOTES.md, "One tile body for the inference kernels"): the
+// buffers by value and returned (as float*& every caller's allocation moved), the global output as a callable read at each dispatch
+// (as a float* read once before the loop, all 18 inference kernels moved).
+struct InferBufs {
+    float *in, *out;
+};
+template <int ROWS, bool PACKED, class Net, class GOut>
+__device__ __forceinline__ InferBufs infer_layers(float* in, float* out, const Net& net, const float* const* W, bool last_to_lds, GOut gout,
+                                                  int64_t m0, int64_t M) {
+    static_assert(ROWS == INF_ROWS || (ROWS == INF16_ROWS && !PACKED), "16- or 32-row tiles; only the 32-row layer reads packed weights");
+    for (int l = 0; l < net.nlayers; ++l) {
+        const int K = net.dim[l], N = net.dim[l + 1];
+        const bool last = l == net.nlayers - 1;
+        float* so = (last && !last_to_lds) ? nullptr : out;
+        if (!last) {
+            const int Np = (N + 31) & ~31;
+            for (int i = threadIdx.x; i < ROWS * (Np - N); i += blockDim.x) {
+                const int row = i / (Np - N), col = N + i - row * (Np - N);
+                out[row * INF_PITCH + col] = 0.0f;
+            }
+        }
+        if constexpr (ROWS == INF16_ROWS) {
+            const int nbw = ((N + 15) / 16 + 3) / 4;  // 16-column blocks per wave
+            if (nbw <= 1) infer_layer16<1>(in, K, W[l], net.ldw[l], net.b[l], N, !last, net.alpha, so, gout(), m0, M);
+            else if (nbw == 2) infer_layer16<2>(in, K, W[l], net.ldw[l], net.b[l], N, !last, net.alpha, so, gout(), m0, M);
+            else if (nbw <= 4) infer_layer16<4>(in, K, W[l], net.ldw[l], net.b[l], N, !last, net.alpha, so, gout(), m0, M);
+            else infer_layer16<8>(in, K, W[l], net.ldw[l], net.b[l], N, !last, net.alpha, so, gout(), m0, M);
+        } else {
+            const int nbw = ((N + 31) / 32 + 3) / 4;  // 32-column blocks per wave
+            if (nbw <= 1) infer_layer<1, PACKED>(in, K, W[l], net.ldw[l], net.b[l], N, !last, net.alpha, so, gout(), m0, M);
+            else if (nbw == 2) infer_layer<2, PACKED>(in, K, W[l], net.ldw[l], net.b[l], N, !last, net.alpha, so, gout(), m0, M);
+            else infer_layer<4, PACKED>(in, K, W[l], net.ldw[l], net.b[l], N, !last, net.alpha, so, gout(), m0, M);
+        }
+        __syncthreads();
+        float* t = in; in = out; out = t;
+    }
+    return {in, out};
 }

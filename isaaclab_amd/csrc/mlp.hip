@@ -1434,103 +1434,135 @@ __device__ __forceinline__ void act_epilogue(const ActArgs& c, const float* __re
 }
 
 
-// (the kernel bodies are textual includes, see mlp_infer_body.inc: *_binary = for a plan with a binary joint term)
-#define IMX_INFER_NORMALIZE 0
-#define IMX_INFER_TWO_INPUTS 0
-template <bool PACKED>
-__global__ void __launch_bounds__(256, 1) k_mlp_infer(InferArgs a, ActArgs act) {
-#define IMX_ACT_BINARY false
-#include "mlp_infer_body.inc"
-#undef IMX_ACT_BINARY
-}
-template <bool PACKED>
-__global__ void __launch_bounds__(256, 1) k_mlp_infer_binary(InferArgs a, ActArgs act) {
-#define IMX_ACT_BINARY true
-#include "mlp_infer_body.inc"
-#undef IMX_ACT_BINARY
-}
-
-
-__global__ void __launch_bounds__(256, 2) k_mlp_infer16(InferArgs a, ActArgs act) {
-#define IMX_ACT_BINARY false
-#include "mlp_infer16_body.inc"
-#undef IMX_ACT_BINARY
-}
-__global__ void __launch_bounds__(256, 2) k_mlp_infer16_binary(InferArgs a, ActArgs act) {
-#define IMX_ACT_BINARY true
-#include "mlp_infer16_body.inc"
-#undef IMX_ACT_BINARY
-}
-#undef IMX_INFER_TWO_INPUTS
-
-// imx_mlp_infer_act2: the same bodies for two networks that do NOT share their input (an env with a privileged "critic" observation
-// group).  A workgroup already serves one network on one row tile and takes its input width from its own net.dim[0]; here it also takes
-// the input pointer and pitch of its network, and network 1's workgroups may store their tile densely (storage.privileged_observations[t])
-// where the actor's store storage.observations[t].  Kernels of their own: the shared-input ones above keep their instruction streams.
+// imx_mlp_infer_act2: two networks that do NOT share their input (an env with a privileged "critic" observation group).  A workgroup
+// already serves one network on one row tile and takes its input width from its own net.dim[0]; here it also takes the input pointer
+// and pitch of its network, and network 1's workgroups may store their tile densely (storage.privileged_observations[t]) where the
+// actor's store storage.observations[t].
 struct InferTwo {
     const float* X1;   // network 1's input (M, net[1].dim[0]), pitch ldx1
     int64_t ldx1;
     float* obs_out1;   // (M, net[1].dim[0]) dense, or null
 };
-#define IMX_INFER_TWO_INPUTS 1
-template <bool PACKED>
-__global__ void __launch_bounds__(256, 1) k_mlp_infer2(InferArgs a, ActArgs act, InferTwo two) {
-#define IMX_ACT_BINARY false
-#include "mlp_infer_body.inc"
-#undef IMX_ACT_BINARY
-}
-template <bool PACKED>
-__global__ void __launch_bounds__(256, 1) k_mlp_infer2_binary(InferArgs a, ActArgs act, InferTwo two) {
-#define IMX_ACT_BINARY true
-#include "mlp_infer_body.inc"
-#undef IMX_ACT_BINARY
-}
-__global__ void __launch_bounds__(256, 2) k_mlp_infer2_16(InferArgs a, ActArgs act, InferTwo two) {
-#define IMX_ACT_BINARY false
-#include "mlp_infer16_body.inc"
-#undef IMX_ACT_BINARY
-}
-__global__ void __launch_bounds__(256, 2) k_mlp_infer2_16_binary(InferArgs a, ActArgs act, InferTwo two) {
-#define IMX_ACT_BINARY true
-#include "mlp_infer16_body.inc"
-#undef IMX_ACT_BINARY
-}
-#undef IMX_INFER_NORMALIZE
-
-// imx_mlp_infer_act2n: the two-input bodies once more, normalising the rows between their load and the LDS / dense stores
-// (EmpiricalNormalization in the fused rollout: (x - mean[c]) / (std[c] + eps), k_norm_apply's expression under this library's
-// -fno-fast-math -ffp-contract=off, so everything downstream is bit-identical to an apply launch followed by k_mlp_infer2*).  Kernels of
-// their own again: the twelve above keep their instruction streams.
+// imx_mlp_infer_act2n: the rows are normalised between their load and the LDS / dense stores (EmpiricalNormalization in the fused
+// rollout: (x - mean[c]) / (std[c] + eps), k_norm_apply's expression under this library's -fno-fast-math -ffp-contract=off, so
+// everything downstream is bit-identical to an apply launch followed by imx_mlp_infer_act2).
 struct InferNorm {
     const float* mean[2];  // per network; null = that network's rows as they are
     const float* stdv[2];
     float eps[2];
 };
-#define IMX_INFER_NORMALIZE 1
-template <bool PACKED>
-__global__ void __launch_bounds__(256, 1) k_mlp_infer2n(InferArgs a, ActArgs act, InferTwo two, InferNorm nrm) {
-#define IMX_ACT_BINARY false
-#include "mlp_infer_body.inc"
-#undef IMX_ACT_BINARY
+
+// The body of all 18 inference kernels: one tile of ROWS (32, or 16 for small batches) samples of one network through its layers.
+// PACKED: the 32-row layers read the packed weight images.  BINARY: the actor head's epilogue with the binary joint term's path.
+// TWO: network 1 reads its own input (`two`) and may keep its rows as well; otherwise both read a.X and `two` is unused.  NORM (with TWO):
+// the rows are normalised with `nrm` between load and LDS store.  How the arguments are passed holds the kernels' register figures
+// (NOTES.md, "One tile body for the inference kernels"): a, act, two BY VALUE (a and act by const reference: two more SGPR spills in each
+// of the eight 32-row kernels without NORM), nrm BY REFERENCE (by value its arrays, indexed by `which`, become 48 bytes of scratch).
+template <int ROWS, bool PACKED, bool BINARY, bool TWO, bool NORM>
+__device__ __forceinline__ void infer_tile(InferArgs a, ActArgs act, InferTwo two, const InferNorm& nrm) {
+    static_assert(TWO || !NORM, "only the two-input kernels normalise");
+    extern __shared__ float smem[];  // two activation buffers of ROWS x INF_PITCH floats
+    float* buf0 = smem;
+    float* buf1 = smem + ROWS * INF_PITCH;
+    const int which = blockIdx.x / a.tiles;
+    const InferNet& net = a.net[which];
+    const int64_t m0 = (int64_t)(blockIdx.x - which * a.tiles) * ROWS;
+    const bool act_here = act.enabled && which == 0;  // the actor's workgroups finish PPO.act + ActionManager.process_action themselves
+    // where the input rows come from, and whether (and where) the tile is also stored densely on its way into LDS
+    const float* x_in = a.X;
+    int64_t ldx_in = a.ldx;
+    bool obs_on = act_here;
+    float* obs_dst = act.obs_out;  // storage.observations[t]
+    if constexpr (TWO) {
+        x_in = which ? two.X1 : a.X;
+        ldx_in = which ? two.ldx1 : a.ldx;
+        obs_dst = which ? two.obs_out1 : (act.enabled ? act.obs_out : nullptr);  // network 1: storage.privileged_observations[t]
+        obs_on = obs_dst != nullptr;
+    }
+    // input rows -> LDS (the rows are one contiguous run when ldx == dim[0]); columns up to the next multiple of 32 are zeroed
+    const int K0 = net.dim[0], K0p = (K0 + 31) & ~31;
+    {
+        // wave w takes rows w, w+4, ...; lanes run along the row.  ALL loads of the tile are issued before the first LDS store -- one HBM
+        // round trip for the whole input (a load -> store loop pays one per iteration: 16 us for 235 columns; two half tiles paid two).
+        // The 32-row tile loads only the 64-column pieces the input has (a clamped load of a piece past K0 is still a memory request);
+        // the 16-row tile loads all of them.
+        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+        const int ncc = (K0 + 63) >> 6;  // (uniform)
+        float v[ROWS / 4][INF_MAXD / 64];
+        // NORM: the lane's mean / std of its columns ride in the tile's load batch; a null pair (uniform): rows as they are
+        const float* n_mean = nullptr;
+        const float* n_std = nullptr;
+        float nmu[INF_MAXD / 64], nsd[INF_MAXD / 64];
+        if constexpr (NORM) {
+            n_mean = nrm.mean[which];
+            n_std = nrm.stdv[which];
+#pragma unroll
+            for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
+                const int c = lane + 64 * cc;
+                nmu[cc] = (n_mean && (ROWS == 16 || cc < ncc)) ? n_mean[c < K0 ? c : 0] : 0.0f;
+                nsd[cc] = (n_mean && (ROWS == 16 || cc < ncc)) ? n_std[c < K0 ? c : 0] : 1.0f;
+            }
+        }
+#pragma unroll
+        for (int rr = 0; rr < ROWS / 4; ++rr) {
+            const int row = w + 4 * rr;
+            const float* src = x_in + (m0 + row < a.M ? m0 + row : 0) * ldx_in;
+#pragma unroll
+            for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
+                if (ROWS == 16 || cc < ncc) {
+                    const int c = lane + 64 * cc;
+                    const float x = src[c < K0 ? c : 0];  // clamped, unconditional within the piece
+                    v[rr][cc] = (c < K0 && m0 + row < a.M) ? x : 0.0f;
+                } else {
+                    v[rr][cc] = 0.0f;
+                }
+            }
+        }
+        if constexpr (NORM) {
+            if (n_mean) {  // k_norm_apply's expression (a true division): LDS and the dense store get what an apply launch would have left
+                const float n_eps = nrm.eps[which];
+#pragma unroll
+                for (int rr = 0; rr < ROWS / 4; ++rr) {
+                    const int row = w + 4 * rr;
+#pragma unroll
+                    for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
+                        const int c = lane + 64 * cc;
+                        if (c < K0 && m0 + row < a.M) v[rr][cc] = (v[rr][cc] - nmu[cc]) / (nsd[cc] + n_eps);  // (padding and rows past M stay zero)
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int rr = 0; rr < ROWS / 4; ++rr) {
+            const int row = w + 4 * rr;
+#pragma unroll
+            for (int cc = 0; cc < INF_MAXD / 64; ++cc) {
+                const int c = lane + 64 * cc;
+                if (c < K0p) buf0[row * INF_PITCH + c] = v[rr][cc];
+                if (obs_on && c < K0 && m0 + row < a.M) obs_dst[(m0 + row) * (int64_t)K0 + c] = v[rr][cc];
+            }
+        }
+    }
+    __syncthreads();
+    // (the actor head of imx_mlp_infer_act keeps its means in LDS)
+    const InferBufs s = infer_layers<ROWS, PACKED>(buf0, buf1, net, PACKED ? net.Wp : net.W, act_here, [&] { return net.out; }, m0, a.M);
+    if (act_here) act_epilogue<ROWS, BINARY>(act, s.in, s.out, m0, a.M);
 }
-template <bool PACKED>
-__global__ void __launch_bounds__(256, 1) k_mlp_infer2n_binary(InferArgs a, ActArgs act, InferTwo two, InferNorm nrm) {
-#define IMX_ACT_BINARY true
-#include "mlp_infer_body.inc"
-#undef IMX_ACT_BINARY
-}
-__global__ void __launch_bounds__(256, 2) k_mlp_infer2n_16(InferArgs a, ActArgs act, InferTwo two, InferNorm nrm) {
-#define IMX_ACT_BINARY false
-#include "mlp_infer16_body.inc"
-#undef IMX_ACT_BINARY
-}
-__global__ void __launch_bounds__(256, 2) k_mlp_infer2n_16_binary(InferArgs a, ActArgs act, InferTwo two, InferNorm nrm) {
-#define IMX_ACT_BINARY true
-#include "mlp_infer16_body.inc"
-#undef IMX_ACT_BINARY
-}
-#undef IMX_INFER_NORMALIZE
-#undef IMX_INFER_TWO_INPUTS
+
+// The 18 kernels: {shared input, two inputs (2), two inputs normalised (2n)} x {affine plan, _binary: a plan with a binary joint term}
+// x {32 rows <PACKED or not>, 16 rows}.  Their names, launch bounds and argument lists are what profiles and tools/ know them by.
+template <bool PACKED> __global__ void __launch_bounds__(256, 1) k_mlp_infer(InferArgs a, ActArgs act) { infer_tile<32, PACKED, false, false, false>(a, act, {}, {}); }
+template <bool PACKED> __global__ void __launch_bounds__(256, 1) k_mlp_infer_binary(InferArgs a, ActArgs act) { infer_tile<32, PACKED, true, false, false>(a, act, {}, {}); }
+__global__ void __launch_bounds__(256, 2) k_mlp_infer16(InferArgs a, ActArgs act) { infer_tile<16, false, false, false, false>(a, act, {}, {}); }
+__global__ void __launch_bounds__(256, 2) k_mlp_infer16_binary(InferArgs a, ActArgs act) { infer_tile<16, false, true, false, false>(a, act, {}, {}); }
+template <bool PACKED> __global__ void __launch_bounds__(256, 1) k_mlp_infer2(InferArgs a, ActArgs act, InferTwo two) { infer_tile<32, PACKED, false, true, false>(a, act, two, {}); }
+template <bool PACKED> __global__ void __launch_bounds__(256, 1) k_mlp_infer2_binary(InferArgs a, ActArgs act, InferTwo two) { infer_tile<32, PACKED, true, true, false>(a, act, two, {}); }
+__global__ void __launch_bounds__(256, 2) k_mlp_infer2_16(InferArgs a, ActArgs act, InferTwo two) { infer_tile<16, false, false, true, false>(a, act, two, {}); }
+__global__ void __launch_bounds__(256, 2) k_mlp_infer2_16_binary(InferArgs a, ActArgs act, InferTwo two) { infer_tile<16, false, true, true, false>(a, act, two, {}); }
+template <bool PACKED> __global__ void __launch_bounds__(256, 1) k_mlp_infer2n(InferArgs a, ActArgs act, InferTwo two, InferNorm nrm) { infer_tile<32, PACKED, false, true, true>(a, act, two, nrm); }
+template <bool PACKED> __global__ void __launch_bounds__(256, 1) k_mlp_infer2n_binary(InferArgs a, ActArgs act, InferTwo two, InferNorm nrm) { infer_tile<32, PACKED, true, true, true>(a, act, two, nrm); }
+__global__ void __launch_bounds__(256, 2) k_mlp_infer2n_16(InferArgs a, ActArgs act, InferTwo two, InferNorm nrm) { infer_tile<16, false, false, true, true>(a, act, two, nrm); }
+__global__ void __launch_bounds__(256, 2) k_mlp_infer2n_16_binary(InferArgs a, ActArgs act, InferTwo two, InferNorm nrm) { infer_tile<16, false, true, true, true>(a, act, two, nrm); }
 
 extern "C" int imx_mlp_infer(int64_t M, const float* X_d, int64_t ldx, int nnets, const int* nlayers, const int* dims,
                              const float* const* weights_d, const int* weight_pitch, const float* const* biases_d, const float* elu_alpha,
@@ -1599,7 +1631,37 @@ extern "C" int imx_mlp_pack_weights(int out_features, int in_features, const flo
     return imx_mlp_pack_weights_batch(1, &out_features, &in_features, &W_d, &ldw, &packed_d, stream);
 }
 
-// Both entry points.  two_inputs false (imx_mlp_infer, imx_mlp_infer_act): every network reads X[0] with pitch ldx[0], and the checks and
+// The six kernels that take the same arguments after (InferArgs, ActArgs), [binary joint term in the plan][tile], and the one place
+// that raises their dynamic-LDS limit (once) and launches one of them.
+enum { INFER_16, INFER_32_PACKED, INFER_32 };
+template <class... Extra>
+struct InferKernels {
+    void (*k[2][3])(InferArgs, ActArgs, Extra...);
+    bool attr_set;
+};
+static InferKernels<> g_infer{{{k_mlp_infer16, k_mlp_infer<true>, k_mlp_infer<false>},
+                               {k_mlp_infer16_binary, k_mlp_infer_binary<true>, k_mlp_infer_binary<false>}}, false};
+static InferKernels<InferTwo> g_infer2{{{k_mlp_infer2_16, k_mlp_infer2<true>, k_mlp_infer2<false>},
+                                        {k_mlp_infer2_16_binary, k_mlp_infer2_binary<true>, k_mlp_infer2_binary<false>}}, false};
+static InferKernels<InferTwo, InferNorm> g_infer2n{{{k_mlp_infer2n_16, k_mlp_infer2n<true>, k_mlp_infer2n<false>},
+                                                    {k_mlp_infer2n_16_binary, k_mlp_infer2n_binary<true>, k_mlp_infer2n_binary<false>}}, false};
+
+template <class... Extra>
+static int infer_launch_kernel(InferKernels<Extra...>& f, bool binary, int tile, InferArgs a, const ActArgs& act, hipStream_t stream, Extra... extra) {
+    const auto lds = [](int t) { return 2ull * (t == INFER_16 ? INF16_ROWS : INF_ROWS) * INF_PITCH * sizeof(float); };
+    if (!f.attr_set) {
+        for (const auto& row : f.k)
+            for (int t = 0; t < 3; ++t)
+                IMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(row[t]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds(t)));
+        f.attr_set = true;
+    }
+    if (tile == INFER_16) a.tiles = (int)((a.M + INF16_ROWS - 1) / INF16_ROWS);
+    hipLaunchKernelGGL(f.k[binary][tile], dim3((unsigned)(a.tiles * a.nnets)), dim3(256), lds(tile), stream, a, act, extra...);
+    IMX_HIP(hipGetLastError());
+    return 0;
+}
+
+// All four entry points.  two_inputs false (imx_mlp_infer, imx_mlp_infer_act): every network reads X[0] with pitch ldx[0], and the
 // messages are the ones those always had.  true (imx_mlp_infer_act2): network k reads X[k] with pitch ldx[k]; the messages name the argument.
 static int mlp_infer_launch(bool two_inputs, int64_t M, const float* const* X, const int64_t* ldxs, int nnets, const int* nlayers, const int* dims,
                             const float* const* weights_d, const int* weight_pitch, const float* const* packed_weights_d,
@@ -1609,9 +1671,10 @@ static int mlp_infer_launch(bool two_inputs, int64_t M, const float* const* X, c
     // answer under the name of the entry point that was called (fn)
     const char* const fn = normalize ? "imx_mlp_infer_act2n" : "imx_mlp_infer_act2";
     InferNorm nrm{};
+    const bool nnets_ok = nnets >= 1 && nnets <= 2;
     if (normalize) {
         IMX_REQUIRE(norm, "imx_mlp_infer_act2n: norm is null (one imx_infer_norm_t per network; both pointers null = rows as they are)");
-        IMX_REQUIRE(nnets >= 1 && nnets <= 2, "imx_mlp_infer_act2n: nnets = %d (1 or 2 networks)", nnets);
+        IMX_REQUIRE(nnets_ok, "imx_mlp_infer_act2n: nnets = %d (1 or 2 networks)", nnets);
         for (int k = 0; k < nnets; ++k) {
             IMX_REQUIRE((norm[k].mean_d == nullptr) == (norm[k].std_d == nullptr),
                         "imx_mlp_infer_act2n: norm[%d]: null statistics (%s is null, the other is not)", k, norm[k].mean_d ? "std_d" : "mean_d");
@@ -1619,13 +1682,13 @@ static int mlp_infer_launch(bool two_inputs, int64_t M, const float* const* X, c
         }
     }
     if (two_inputs) {
-        IMX_REQUIRE(M > 0 && nnets >= 1 && nnets <= 2, "%s: M = %lld, nnets = %d (M > 0 and 1 or 2 networks)", fn, (long long)M, nnets);
+        IMX_REQUIRE(M > 0 && nnets_ok, "%s: M = %lld, nnets = %d (M > 0 and 1 or 2 networks)", fn, (long long)M, nnets);
         IMX_REQUIRE(X && ldxs && nlayers && dims && weights_d && biases_d && elu_alpha && out_d,
                     "%s: a null array among X_d, ldx, nlayers, dims, weights_d, biases_d, elu_alpha, out_d", fn);
         IMX_REQUIRE(!critic_obs_out_d || nnets == 2, "%s: critic_obs_out_d given with nnets == %d (network 1's rows: it needs 2)", fn, nnets);
         for (int k = 0; k < nnets; ++k) IMX_REQUIRE(X[k], "%s: X_d[%d] is null", fn, k);
     } else {
-        IMX_REQUIRE(M > 0 && X[0] && nnets >= 1 && nnets <= 2 && nlayers && dims && weights_d && biases_d && elu_alpha && out_d,
+        IMX_REQUIRE(M > 0 && X[0] && nnets_ok && nlayers && dims && weights_d && biases_d && elu_alpha && out_d,
                     "imx_mlp_infer: bad arguments");
     }
     const float* const X_d = X[0];
@@ -1662,10 +1725,10 @@ static int mlp_infer_launch(bool two_inputs, int64_t M, const float* const* X, c
         IMX_REQUIRE(n.nlayers >= 1 && n.nlayers <= INF_MAXL, "imx_mlp_infer: network %d has %d layers (1..%d supported)", k, n.nlayers, INF_MAXL);
         for (int l = 0; l <= n.nlayers; ++l) {
             n.dim[l] = dims[di++];
-            if (two_inputs)
-                IMX_REQUIRE(n.dim[l] >= 1 && n.dim[l] <= INF_MAXD, "%s: dims: width %d of network %d (layer %d) outside 1..%d", fn,
-                            n.dim[l], k, l, INF_MAXD);
-            IMX_REQUIRE(n.dim[l] >= 1 && n.dim[l] <= INF_MAXD, "imx_mlp_infer: layer width %d outside 1..%d", n.dim[l], INF_MAXD);
+            if (!(n.dim[l] >= 1 && n.dim[l] <= INF_MAXD)) {
+                if (two_inputs) IMX_FAIL("%s: dims: width %d of network %d (layer %d) outside 1..%d", fn, n.dim[l], k, l, INF_MAXD);
+                IMX_FAIL("imx_mlp_infer: layer width %d outside 1..%d", n.dim[l], INF_MAXD);
+            }
         }
         if (two_inputs)
             IMX_REQUIRE(ldxs[k] >= n.dim[0], "%s: ldx[%d] = %lld is less than the input width %d of network %d", fn,
@@ -1676,10 +1739,10 @@ static int mlp_infer_launch(bool two_inputs, int64_t M, const float* const* X, c
         for (int l = 0; l < n.nlayers; ++l) {
             n.W[l] = weights_d[wi];
             n.Wp[l] = packed_weights_d ? packed_weights_d[wi] : nullptr;
-            if (two_inputs)
-                IMX_REQUIRE(!packed_weights_d || (n.Wp[l] && aligned16(n.Wp[l])),
-                            "%s: packed_weights_d[%d] is null or not 16-byte aligned (network %d, layer %d)", fn, wi, k, l);
-            IMX_REQUIRE(!packed_weights_d || (n.Wp[l] && aligned16(n.Wp[l])), "imx_mlp_infer: null / unaligned packed weights (network %d, layer %d)", k, l);
+            if (packed_weights_d && !(n.Wp[l] && aligned16(n.Wp[l]))) {
+                if (two_inputs) IMX_FAIL("%s: packed_weights_d[%d] is null or not 16-byte aligned (network %d, layer %d)", fn, wi, k, l);
+                IMX_FAIL("imx_mlp_infer: null / unaligned packed weights (network %d, layer %d)", k, l);
+            }
             n.b[l] = biases_d[wi];
             n.ldw[l] = weight_pitch ? weight_pitch[wi] : n.dim[l];
             ++wi;
@@ -1697,80 +1760,13 @@ static int mlp_infer_launch(bool two_inputs, int64_t M, const float* const* X, c
     // these 16-byte-per-lane row gathers: at 4096 envs both variants sit on it, and a deeper, three-set prefetch ring changed
     // nothing), so they only pay when 32-sample tiles would leave at least half of the CUs without a workgroup
     const bool small = (int64_t)a.tiles * nnets * 2 <= g_num_cu;
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void* big[] = {reinterpret_cast<const void*>(k_mlp_infer<false>), reinterpret_cast<const void*>(k_mlp_infer<true>),
-                             reinterpret_cast<const void*>(k_mlp_infer_binary<false>), reinterpret_cast<const void*>(k_mlp_infer_binary<true>)};
-        for (const void* f : big) IMX_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2ull * INF_ROWS * INF_PITCH * sizeof(float))));
-        const void* small16[] = {reinterpret_cast<const void*>(k_mlp_infer16), reinterpret_cast<const void*>(k_mlp_infer16_binary)};
-        for (const void* f : small16) IMX_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2ull * INF16_ROWS * INF_PITCH * sizeof(float))));
-        attr_set = true;
-    }
+    const int tile = small ? INFER_16 : (packed_weights_d ? INFER_32_PACKED : INFER_32);
     const bool binary = act.has_plan == 2;  // a plan with a binary joint term: the kernels with that path in the actor head's epilogue
-    const dim3 bs(256);
-    if (two_inputs) {  // the same choice among the two-input kernels
-        static bool attr2_set = false;
-        if (!attr2_set) {
-            const void* big[] = {reinterpret_cast<const void*>(k_mlp_infer2<false>), reinterpret_cast<const void*>(k_mlp_infer2<true>),
-                                 reinterpret_cast<const void*>(k_mlp_infer2_binary<false>), reinterpret_cast<const void*>(k_mlp_infer2_binary<true>)};
-            for (const void* f : big) IMX_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2ull * INF_ROWS * INF_PITCH * sizeof(float))));
-            const void* small16[] = {reinterpret_cast<const void*>(k_mlp_infer2_16), reinterpret_cast<const void*>(k_mlp_infer2_16_binary)};
-            for (const void* f : small16) IMX_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2ull * INF16_ROWS * INF_PITCH * sizeof(float))));
-            attr2_set = true;
-        }
-        InferTwo two{};
-        if (nnets == 2) { two.X1 = X[1]; two.ldx1 = ldxs[1]; two.obs_out1 = critic_obs_out_d; }
-        if (normalize) {  // the same choice once more, among the normalising kernels
-            static bool attr2n_set = false;
-            if (!attr2n_set) {
-                const void* big[] = {reinterpret_cast<const void*>(k_mlp_infer2n<false>), reinterpret_cast<const void*>(k_mlp_infer2n<true>),
-                                     reinterpret_cast<const void*>(k_mlp_infer2n_binary<false>), reinterpret_cast<const void*>(k_mlp_infer2n_binary<true>)};
-                for (const void* f : big) IMX_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2ull * INF_ROWS * INF_PITCH * sizeof(float))));
-                const void* small16[] = {reinterpret_cast<const void*>(k_mlp_infer2n_16), reinterpret_cast<const void*>(k_mlp_infer2n_16_binary)};
-                for (const void* f : small16) IMX_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2ull * INF16_ROWS * INF_PITCH * sizeof(float))));
-                attr2n_set = true;
-            }
-            if (small) {
-                a.tiles = (int)((M + INF16_ROWS - 1) / INF16_ROWS);
-                hipLaunchKernelGGL(binary ? k_mlp_infer2n_16_binary : k_mlp_infer2n_16, dim3((unsigned)(a.tiles * nnets)), bs,
-                                   2ull * INF16_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act, two, nrm);
-            } else if (packed_weights_d) {
-                hipLaunchKernelGGL(binary ? k_mlp_infer2n_binary<true> : k_mlp_infer2n<true>, dim3((unsigned)(a.tiles * nnets)), bs,
-                                   2ull * INF_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act, two, nrm);
-            } else {
-                hipLaunchKernelGGL(binary ? k_mlp_infer2n_binary<false> : k_mlp_infer2n<false>, dim3((unsigned)(a.tiles * nnets)), bs,
-                                   2ull * INF_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act, two, nrm);
-            }
-            IMX_HIP(hipGetLastError());
-            return 0;
-        }
-        if (small) {
-            a.tiles = (int)((M + INF16_ROWS - 1) / INF16_ROWS);
-            hipLaunchKernelGGL(binary ? k_mlp_infer2_16_binary : k_mlp_infer2_16, dim3((unsigned)(a.tiles * nnets)), bs,
-                               2ull * INF16_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act, two);
-        } else if (packed_weights_d) {
-            hipLaunchKernelGGL(binary ? k_mlp_infer2_binary<true> : k_mlp_infer2<true>, dim3((unsigned)(a.tiles * nnets)), bs,
-                               2ull * INF_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act, two);
-        } else {
-            hipLaunchKernelGGL(binary ? k_mlp_infer2_binary<false> : k_mlp_infer2<false>, dim3((unsigned)(a.tiles * nnets)), bs,
-                               2ull * INF_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act, two);
-        }
-        IMX_HIP(hipGetLastError());
-        return 0;
-    }
-    if (small) {
-        a.tiles = (int)((M + INF16_ROWS - 1) / INF16_ROWS);
-        hipLaunchKernelGGL(binary ? k_mlp_infer16_binary : k_mlp_infer16, dim3((unsigned)(a.tiles * nnets)), bs,
-                           2ull * INF16_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act);
-    } else if (packed_weights_d) {
-        hipLaunchKernelGGL(binary ? k_mlp_infer_binary<true> : k_mlp_infer<true>, dim3((unsigned)(a.tiles * nnets)), bs,
-                           2ull * INF_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act);
-    } else {
-        hipLaunchKernelGGL(binary ? k_mlp_infer_binary<false> : k_mlp_infer<false>, dim3((unsigned)(a.tiles * nnets)), bs,
-                           2ull * INF_ROWS * INF_PITCH * sizeof(float), (hipStream_t)stream, a, act);
-    }
-    IMX_HIP(hipGetLastError());
-    return 0;
+    if (!two_inputs) return infer_launch_kernel(g_infer, binary, tile, a, act, (hipStream_t)stream);
+    InferTwo two{};
+    if (nnets == 2) { two.X1 = X[1]; two.ldx1 = ldxs[1]; two.obs_out1 = critic_obs_out_d; }
+    if (!normalize) return infer_launch_kernel(g_infer2, binary, tile, a, act, (hipStream_t)stream, two);
+    return infer_launch_kernel(g_infer2n, binary, tile, a, act, (hipStream_t)stream, two, nrm);
 }
 
 extern "C" int imx_mlp_infer_act(int64_t M, const float* X_d, int64_t ldx, int nnets, const int* nlayers, const int* dims,

@@ -84,34 +84,8 @@ k_pretrained_policy(PlanView P, imx_state_t S, imx_buffers_t Bf, PolicyArgs a) {
         buf0[row * INF_PITCH + x.a.x] = v;
     }
     __syncthreads();
-    // -- stage 2: the layers (the loop of mlp_infer16_body.inc / mlp_infer_body.inc; the last layer's output stays in LDS)
-    float* in = buf0;
-    float* out = buf1;
-    for (int l = 0; l < a.nlayers; ++l) {
-        const int K = a.dim[l], Nl = a.dim[l + 1];
-        const bool last = l == a.nlayers - 1;
-        if (!last) {
-            const int Np = (Nl + 31) & ~31;
-            for (int i = threadIdx.x; i < ROWS * (Np - Nl); i += blockDim.x) {
-                const int row = i / (Np - Nl), col = Nl + i - row * (Np - Nl);
-                out[row * INF_PITCH + col] = 0.0f;
-            }
-        }
-        if (ROWS == 16) {
-            const int nbw = ((Nl + 15) / 16 + 3) / 4;  // 16-column blocks per wave
-            if (nbw <= 1) infer_layer16<1>(in, K, a.W[l], a.ldw[l], a.b[l], Nl, !last, a.alpha, out, nullptr, m0, N);
-            else if (nbw == 2) infer_layer16<2>(in, K, a.W[l], a.ldw[l], a.b[l], Nl, !last, a.alpha, out, nullptr, m0, N);
-            else if (nbw <= 4) infer_layer16<4>(in, K, a.W[l], a.ldw[l], a.b[l], Nl, !last, a.alpha, out, nullptr, m0, N);
-            else infer_layer16<8>(in, K, a.W[l], a.ldw[l], a.b[l], Nl, !last, a.alpha, out, nullptr, m0, N);
-        } else {
-            const int nbw = ((Nl + 31) / 32 + 3) / 4;  // 32-column blocks per wave
-            if (nbw <= 1) infer_layer<1, PACKED>(in, K, a.W[l], a.ldw[l], a.b[l], Nl, !last, a.alpha, out, nullptr, m0, N);
-            else if (nbw == 2) infer_layer<2, PACKED>(in, K, a.W[l], a.ldw[l], a.b[l], Nl, !last, a.alpha, out, nullptr, m0, N);
-            else infer_layer<4, PACKED>(in, K, a.W[l], a.ldw[l], a.b[l], Nl, !last, a.alpha, out, nullptr, m0, N);
-        }
-        __syncthreads();
-        float* t = in; in = out; out = t;
-    }
+    // -- stage 2: the layers (the rollout inference kernels' loop; the last layer's output stays in LDS)
+    const float* in = infer_layers<ROWS, PACKED>(buf0, buf1, a, a.W, true, [] { return (float*)nullptr; }, m0, N).in;
     // -- stage 3: low_level_actions[:] = policy(obs); JointPositionAction.process_actions (joint_actions.py:130-139)
     const int A = P.A;
     for (int i = threadIdx.x; i < ROWS * A; i += blockDim.x) {

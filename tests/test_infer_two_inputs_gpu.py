@@ -8,7 +8,8 @@ three-launch step on envs with a "critic" observation group.
    storage slot of sentinels on either side of the written one;
 3. the runner on the kitchen fixture (64 envs, eager and captured; 2500 envs over a synthetic feed): ``fuse_launches`` False against
    True leaves bit-identical storages and env buffers, and the fused path is the one that ran;
-4. a binary joint term beside a critic group (Lift-Cube plus a ``critic`` group), split against fused.
+4. a binary joint term beside a critic group (Lift-Cube plus a ``critic`` group), split against fused; the Lift-Cube plan under the
+   actor head of the 32-row kernels (2081 rows, packed and row-layout weights), as part 2 compares.
 
 The single-network reference of part 1: the 16- and the 32-row kernels sum a dot product in different orders (16x16x4 against 32x32x2
 MFMAs), so a reference is only bit-comparable when it runs the tile height the launch under test ran.  The dispatch rule counts
@@ -174,26 +175,16 @@ def _env(task: str, N: int):
     return env
 
 
-@pytest.mark.parametrize("task,A,rows,clip", [("Isaac-Velocity-Flat-Anymal-C-v0", 12, 33, None), ("Isaac-Velocity-Flat-Anymal-C-v0", 12, "first32", 0.8),
-                                              ("Isaac-Velocity-Rough-G1-v0", 37, 33, 0.8), ("Isaac-Velocity-Rough-G1-v0", 37, "first32", None)])
-def test_act_variant_equals_plain_call_policy_act_action_process_and_copy(task, A, rows, clip):
-    """One launch against four.  Both row counts end in a ragged tile (33 = 2 x 16 + 1; the first 32-row count = 32 k + 1): the slot after
-    the written one is where rows beyond M would land."""
+def check_act_variant(env, pol, inf, x, cx, clip, norms=None, packed=True):
+    """One launch with ``ImxPolicyAct`` against the launches it replaces, bit for bit: the plain call, ``imx_policy_act``, the env's action
+    terms (``imx_action_process``) and a copy of the critic rows, with a storage slot of sentinels on either side of the written one.
+    ``cx`` None: a shared-input ``inf`` (no critic rows are kept).  ``norms`` (the policy's and the critic's ``EmpiricalNormalization``):
+    the one launch normalises the raw rows itself, the others start from ``apply``'s rows.  ``packed`` False: the row-layout weights."""
     from isaaclab_amd import _lib
-    from isaaclab_amd.rsl_rl.actor_critic import ActorCritic
-    from isaaclab_amd.rsl_rl.ppo import FusedInference, _mlp_layers
 
-    N, big = _rows(rows)
-    assert N % (32 if big else 16) == 1
-    env = _env(task, N)
-    D = env.plan.obs_dim
-    assert env.plan.action_dim == A
-    Dc, seed = D + 13, 12345
-    torch.manual_seed(5)
-    pol = ActorCritic(D, Dc, A, actor_hidden_dims=[128, 64], critic_hidden_dims=[96], init_noise_std=0.7).cuda()
-    two = FusedInference(_mlp_layers(pol.actor), _mlp_layers(pol.critic))
-    assert two.ok and two.two_inputs
-    x, cx = _input(N, D, False, 21), _input(N, Dc, True, 22)
+    N, D, A = x.shape[0], x.shape[1], env.plan.action_dim
+    Dc, seed = (cx.shape[1] if cx is not None else 0), 12345
+    xr, cxr = (x, cx) if norms is None else (norms[0].apply(x), norms[1].apply(cx))
     L, s = _lib.lib(), torch.cuda.current_stream().cuda_stream
     g = torch.Generator().manual_seed(4)
     env._action.copy_(torch.randn(env._action.shape, generator=g))
@@ -204,43 +195,117 @@ def test_act_variant_equals_plain_call_policy_act_action_process_and_copy(task, 
 
     def slots():  # three storage slots per output: the middle one is written
         S = lambda *sh: torch.full((3, *sh), SENTINEL, device="cuda")  # noqa: E731
-        return dict(actions=S(N, A), log_prob=S(N), mu=S(N, A), sigma=S(N, A), values=S(N, 1), observations=S(N, D), privileged_observations=S(N, Dc))
+        o = dict(actions=S(N, A), log_prob=S(N), mu=S(N, A), sigma=S(N, A), values=S(N, 1), observations=S(N, D))
+        if cx is not None:
+            o["privileged_observations"] = S(N, Dc)
+        return o
 
     def env_buffers():
         return dict(action=env._action.clone(), prev_action=env._prev_action.clone(), processed_action=env._processed_action.clone())
 
-    # the four launches
-    ref = slots()
-    mu, val = torch.empty(N, A, device="cuda"), torch.empty(N, 1, device="cuda")
-    two(x, mu, val, critic_x=cx)
-    _lib.check(L.imx_policy_act(N, A, D, mu.data_ptr(), pol.std.data_ptr(), val.data_ptr(), x.data_ptr(), seed, stp.data_ptr(),
-                                ref["actions"][1].data_ptr(), ref["log_prob"][1].data_ptr(), ref["mu"][1].data_ptr(), ref["sigma"][1].data_ptr(),
-                                ref["values"][1].data_ptr(), ref["observations"][1].data_ptr(), None, s))
-    env._process_action(ref["actions"][1])
-    ref["privileged_observations"][1].copy_(cx)
-    torch.cuda.synchronize()
-    ref.update(env_buffers())
-    # the one launch, from the same env buffers
-    for b, b0 in zip((env._action, env._prev_action, env._processed_action), start):
-        b.copy_(b0)
-    got = slots()
-    act = _lib.ImxPolicyAct(std_d=pol.std.data_ptr(), seed=seed, step_counter_d=stp.data_ptr(), actions_out_d=got["actions"][1].data_ptr(),
-                            logp_out_d=got["log_prob"][1].data_ptr(), mu_out_d=got["mu"][1].data_ptr(), sigma_out_d=got["sigma"][1].data_ptr(),
-                            obs_out_d=got["observations"][1].data_ptr(), plan=env._plan_h.value, state=ctypes.pointer(env._state()),
-                            buf=ctypes.pointer(env._bufs), pre_clip=math.inf if clip is None else float(clip))
-    two(x, None, got["values"][1], act=act, critic_x=cx, critic_obs_out=got["privileged_observations"][1])
-    torch.cuda.synchronize()
+    keep = inf._wpk
+    if not packed:
+        inf._wpk = None
+    try:
+        # the four launches
+        ref = slots()
+        mu, val = torch.empty(N, A, device="cuda"), torch.empty(N, 1, device="cuda")
+        inf(xr, mu, val, **({} if cx is None else dict(critic_x=cxr)))
+        _lib.check(L.imx_policy_act(N, A, D, mu.data_ptr(), pol.std.data_ptr(), val.data_ptr(), xr.data_ptr(), seed, stp.data_ptr(),
+                                    ref["actions"][1].data_ptr(), ref["log_prob"][1].data_ptr(), ref["mu"][1].data_ptr(), ref["sigma"][1].data_ptr(),
+                                    ref["values"][1].data_ptr(), ref["observations"][1].data_ptr(), None, s))
+        env._process_action(ref["actions"][1])
+        if cx is not None:
+            ref["privileged_observations"][1].copy_(cxr)
+        torch.cuda.synchronize()
+        ref.update(env_buffers())
+        # the one launch, from the same env buffers
+        for b, b0 in zip((env._action, env._prev_action, env._processed_action), start):
+            b.copy_(b0)
+        got = slots()
+        act = _lib.ImxPolicyAct(std_d=pol.std.data_ptr(), seed=seed, step_counter_d=stp.data_ptr(), actions_out_d=got["actions"][1].data_ptr(),
+                                logp_out_d=got["log_prob"][1].data_ptr(), mu_out_d=got["mu"][1].data_ptr(), sigma_out_d=got["sigma"][1].data_ptr(),
+                                obs_out_d=got["observations"][1].data_ptr(), plan=env._plan_h.value, state=ctypes.pointer(env._state()),
+                                buf=ctypes.pointer(env._bufs), pre_clip=math.inf if clip is None else float(clip))
+        inf(x, None, got["values"][1], act=act, norm=norms,
+            **({} if cx is None else dict(critic_x=cx, critic_obs_out=got["privileged_observations"][1])))
+        torch.cuda.synchronize()
+    finally:
+        inf._wpk = keep
     got.update(env_buffers())
     for k in ref:
         assert torch.equal(ref[k], got[k]), f"{k}: one launch differs from the four"
     for k in slots():
         assert bool((got[k][0] == SENTINEL).all()) and bool((got[k][2] == SENTINEL).all()), f"{k}: a slot beside the written one was touched"
         assert bool((got[k][1] != SENTINEL).all()) and bool(torch.isfinite(got[k][1]).all()), k
-    assert torch.equal(got["observations"][1], x) and torch.equal(got["privileged_observations"][1], cx.contiguous())
+    assert torch.equal(got["observations"][1], xr) and (cx is None or torch.equal(got["privileged_observations"][1], cxr.contiguous()))
     assert not torch.equal(got["action"], start[0]) and torch.equal(got["prev_action"], start[0])
     if clip is not None:
         assert float(got["action"].abs().max()) <= float(np.float32(clip))
+
+
+@pytest.mark.parametrize("task,A,rows,clip", [("Isaac-Velocity-Flat-Anymal-C-v0", 12, 33, None), ("Isaac-Velocity-Flat-Anymal-C-v0", 12, "first32", 0.8),
+                                              ("Isaac-Velocity-Rough-G1-v0", 37, 33, 0.8), ("Isaac-Velocity-Rough-G1-v0", 37, "first32", None)])
+def test_act_variant_equals_plain_call_policy_act_action_process_and_copy(task, A, rows, clip):
+    """One launch against four.  Both row counts end in a ragged tile (33 = 2 x 16 + 1; the first 32-row count = 32 k + 1): the slot after
+    the written one is where rows beyond M would land."""
+    from isaaclab_amd.rsl_rl.actor_critic import ActorCritic
+    from isaaclab_amd.rsl_rl.ppo import FusedInference, _mlp_layers
+
+    N, big = _rows(rows)
+    assert N % (32 if big else 16) == 1
+    env = _env(task, N)
+    D = env.plan.obs_dim
+    assert env.plan.action_dim == A
+    Dc = D + 13
+    torch.manual_seed(5)
+    pol = ActorCritic(D, Dc, A, actor_hidden_dims=[128, 64], critic_hidden_dims=[96], init_noise_std=0.7).cuda()
+    two = FusedInference(_mlp_layers(pol.actor), _mlp_layers(pol.critic))
+    assert two.ok and two.two_inputs
+    check_act_variant(env, pol, two, _input(N, D, False, 21), _input(N, Dc, True, 22), clip)
     env.close()
+
+
+def binary_head_on_32_row_tiles(family: str, packed: bool):
+    """The ``_binary`` 32-row kernels, which the Lift rollouts (257 envs: 16-row tiles) do not reach: the Lift-Cube plan (a binary joint
+    term) under the actor head at the first 32-row count + 32 (2081 rows on 256 CUs: 66 tiles, one row in the last), input widths 48 and
+    235 (one 64-column piece and four, neither a multiple of 32).  ``family``: "shared" (``imx_mlp_infer_act``), "two"
+    (``imx_mlp_infer_act2``) or "normalised" (``imx_mlp_infer_act2n``)."""
+    import _lift_cases as lc
+    from isaaclab_amd.env import ManagerBasedRLEnv
+    from isaaclab_amd.robots import FRANKA_PANDA
+    from isaaclab_amd.rsl_rl.actor_critic import ActorCritic
+    from isaaclab_amd.rsl_rl.normalizer import EmpiricalNormalization
+    from isaaclab_amd.rsl_rl.ppo import FusedInference, _mlp_layers
+    from isaaclab_amd.state_feed import StateFeed
+
+    N = _first32(2) + 32
+    Dp, Dc = (48, 235) if family != "shared" else ((48, 48) if packed else (235, 235))
+    feed = StateFeed(FRANKA_PANDA, N, "cuda:0", seed=5, num_snapshots=2)
+    lc.lift_tweak(feed, FRANKA_PANDA.body_names.index(lc.EE_BODY), torch.Generator().manual_seed(5))
+    env = ManagerBasedRLEnv(lc.load_fixture(), state_feed=feed, noise_seed=11)
+    env.reset()
+    assert env.plan.processed_action_dim != env.plan.action_dim == lc.A  # the binary joint term
+    torch.manual_seed(5)
+    pol = ActorCritic(Dp, Dc, lc.A, actor_hidden_dims=[128, 64], critic_hidden_dims=[96], init_noise_std=0.7).cuda()
+    inf = FusedInference(_mlp_layers(pol.actor), _mlp_layers(pol.critic))
+    assert inf.ok and inf._wpk is not None and inf.two_inputs == (family != "shared")
+    norms = None
+    if family == "normalised":
+        norms = [EmpiricalNormalization([D]).cuda() for D in (Dp, Dc)]
+        for n in norms:
+            n._mean.copy_(torch.randn(n._mean.shape) * 2.0)
+            n._std.copy_(torch.rand(n._std.shape) + 0.5)
+    check_act_variant(env, pol, inf, _input(N, Dp, False, 21), None if family == "shared" else _input(N, Dc, True, 22), None, norms, packed)
+    # both gripper targets were commanded: the epilogue's binary path ran on either side of zero
+    grip = env._processed_action[:, 7]
+    assert bool((grip == 0).any()) and bool((grip > 0).any())
+    env.close()
+
+
+@pytest.mark.parametrize("packed", [True, False])
+def test_binary_head_of_the_two_input_launch_on_32_row_tiles(packed):
+    binary_head_on_32_row_tiles("two", packed)
 
 
 # ------------------------------------------------------------------------------------------------ 3. the runner, kitchen fixture

@@ -265,3 +265,13 @@ def test_actuator_needs_one_target_per_joint():
     with pytest.raises(ValueError, match="1 joint targets, the robot has 2 joints"):
         env.attach_actuator(object())
     env.close()
+
+
+# ------------------------------------------------------------------------------------------------ the actor head on 32-row tiles
+@pytest.mark.parametrize("packed", [True, False])
+def test_binary_head_of_the_shared_input_launch_on_32_row_tiles(packed):
+    """The rollouts above run 257 envs (16-row tiles): ``k_mlp_infer_binary`` at 2081 rows, packed and row-layout weights, against
+    ``imx_mlp_infer`` + ``imx_policy_act`` + the action terms."""
+    from test_infer_two_inputs_gpu import binary_head_on_32_row_tiles
+
+    binary_head_on_32_row_tiles("shared", packed)

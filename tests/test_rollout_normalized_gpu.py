@@ -362,6 +362,14 @@ def test_binary_epilogues_of_the_normalising_launch(N):
     assert ib["priv"] == "critic" and int(b["obs_norm/count"]) == 4 * N * 3 == int(b["priv_norm/count"])
 
 
+def test_binary_epilogue_of_the_normalising_launch_on_row_layout_weights():
+    """The runner above reads packed weights: ``k_mlp_infer2n_binary<false>`` at 2081 rows against ``apply`` + the plain launch +
+    ``imx_policy_act`` + the action terms."""
+    from test_infer_two_inputs_gpu import binary_head_on_32_row_tiles
+
+    binary_head_on_32_row_tiles("normalised", False)
+
+
 # ------------------------------------------------------------------------------------------------ 5. the runner against fp64
 def test_runner_rows_against_the_float64_restatement():
     """The eager split path on flat Anymal-C: every step's raw rows (kept by a wrapper around ``update_rows``) through the restatement

@@ -271,7 +271,12 @@ enum imx_obs_op {
        p2 (int) = word offset of as many f32 defaults (default_joint_pos / default_joint_vel of those joints, from the asset's
        init_state), aux0 = the frame table (its first word is the row width J2 of imx_articulation_state_t.joint_pos / joint_vel) */
     IMX_O_ARTICULATION_JOINT_POS_REL,
-    IMX_O_ARTICULATION_JOINT_VEL_REL
+    IMX_O_ARTICULATION_JOINT_VEL_REL,
+    /* envs/mdp/observations.py:188-231 on an Imu sensor of the scene; aux0 = the sensor's index among those imx_plan_bind_imu bound.
+       A plan with one of the three ops below runs k_obs_imu */
+    IMX_O_IMU_ORIENTATION = 32, /* :188-201  4 columns: data.quat_w  (31 stays unknown: tests/test_cabinet_plan.py pins it) */
+    IMX_O_IMU_ANG_VEL = 33,     /* :204-216  3 columns: data.ang_vel_b */
+    IMX_O_IMU_LIN_ACC = 34      /* :219-231  3 columns: data.lin_acc_b */
 };
 
 /* action ops.  A record takes the raw columns [OUT, OUT + DIM) of the action and writes the processed columns [PCOL, PCOL + NIDS) of
@@ -609,13 +614,30 @@ typedef struct imx_ray_caster imx_ray_caster_t;
 int imx_mesh_build_ray_bounds(imx_mesh_t* mesh, imx_stream_t stream, int64_t* info4);
 int imx_ray_caster(const imx_ray_caster_t* sensor, int64_t N, imx_mesh_t* mesh, imx_stream_t stream);
 
+/* ---- Imu (sensors/imu/imu.py, sensors/sensor_base.py): imx_imu, imx_plan_bind_imu ------------------------------------------------
+ * One launch for 1..IMX_MAX_IMU sensors, lane = (sensor, env).  A sensor travels in imx_imu_t (imx_imu_struct.h, which this header
+ * includes).  Per env, in the reference's order: reset (the envs of reset_mask_d: clocks to zero, outdated, quat_w and the four
+ * body-frame vectors to zero; pos_w and the previous velocities stay), the clocks (substeps times timestamp += dt, outdated once the
+ * update period has passed), and with `refresh` _update_buffers_impl for the outdated envs only: pos_w, quat_w (offset included), the
+ * linear velocity carried from the centre of mass to the sensor, both accelerations as (v - previous v) / dt with dt the value of
+ * this call (Imu._dt: the dt of the last update, not the time since the last refresh), and the four vectors rotated into the sensor's
+ * frame; the other envs keep what they had.  The velocity inputs are never written.  No host synchronisation: capturable.
+ *   imx_plan_bind_imu: the sensors' data tensors for the IMX_O_IMU_* observation ops of `plan`, by sensor index (the record's aux0);
+ *   like imx_plan_bind_object_state the pointers are read at the time of an imx_observations call.  num_sensors = 0 unbinds.
+ * Every NULL pointer or out-of-range value is refused and named in imx_last_error before any launch. */
+#define IMX_MAX_IMU 4
+typedef struct imx_imu imx_imu_t;
+#include "imx_imu_struct.h" /* the definition of imx_imu_t */
+int imx_imu(const imx_imu_t* sensors, int32_t num_sensors, int64_t N, imx_stream_t stream);
+int imx_plan_bind_imu(imx_plan_t* plan, const imx_imu_t* sensors, int32_t num_sensors);
+
 /* ---- library ---------------------------------------------------------------------------------------------------- */
 const char* imx_version(void);
 /* sizeof of an ABI struct as this library was compiled (which: 0 imx_state_t, 1 imx_buffers_t, 2 imx_head_loss_t, 3 imx_rollout_slot_t, 4 imx_policy_act_t, 5 imx_orch_t, 6 imx_event_term_t,
  * 7 imx_diff_ik_t, 8 imx_osc_t, 10 imx_orch_manip_t, 11 imx_weight_term_t, 12 imx_pretrained_policy_t,
  * 13 imx_pose2d_command_t, 15 imx_inhand_command_t, 16 imx_object_state_t, 18 imx_articulation_state_t,
- * 20 imx_orch_articulation_t, 22 imx_norm_group_t, 23 imx_infer_norm_t, 25 imx_ray_caster_t), 0 for an unknown index
- * (9, 14, 17, 19, 21 and 24 are):
+ * 20 imx_orch_articulation_t, 22 imx_norm_group_t, 23 imx_infer_norm_t, 25 imx_ray_caster_t, 27 imx_imu_t), 0 for an unknown index
+ * (9, 14, 17, 19, 21, 24 and 26 are):
  * a binding checks its own layout against it at load time. */
 size_t imx_struct_size(int which);
 const char* imx_last_error(void);

@@ -193,5 +193,9 @@ try:
     RAY_CASTER_HEADER = os.path.join(os.path.dirname(HEADER), "imx_ray_caster_struct.h")
     with open(RAY_CASTER_HEADER) as _f:
         _, _, RAY_CASTER_STRUCTS, _ = parse(_f.read(), RAY_CASTER_HEADER, DEFINES)
+    # imx_imu_struct.h, likewise: imx_imu_t (imx_imu, imx_plan_bind_imu)
+    IMU_HEADER = os.path.join(os.path.dirname(HEADER), "imx_imu_struct.h")
+    with open(IMU_HEADER) as _f:
+        _, _, IMU_STRUCTS, _ = parse(_f.read(), IMU_HEADER, DEFINES)
 except OSError as e:
     raise AbiError(f"the ABI header {HEADER} cannot be read ({e}): the whole binding is derived from it") from e

@@ -114,6 +114,9 @@ ImxInferNorm = type("ImxInferNorm", (ctypes.Structure,), {"_fields_": [(field, _
 # (imx_ray_caster_struct.h, the same way)
 ImxRayCaster = type("ImxRayCaster", (ctypes.Structure,), {"_fields_": [(field, _abi.ctype(t, _STRUCTS))
                                                                       for field, t in _abi.RAY_CASTER_STRUCTS["imx_ray_caster_t"]]})
+# (imx_imu_struct.h, the same way)
+ImxImu = type("ImxImu", (ctypes.Structure,), {"_fields_": [(field, _abi.ctype(t, _STRUCTS)) for field, t in _abi.IMU_STRUCTS["imx_imu_t"]]})
+MAX_IMU = _abi.DEFINES["IMX_MAX_IMU"]
 FRAME_WORDS = _abi.DEFINES["IMX_FRAME_WORDS"]
 FT_HEADER_WORDS = _abi.DEFINES["IMX_FT_HEADER_WORDS"]
 if set(_STRUCTS) != set(_abi.STRUCTS):
@@ -132,7 +135,7 @@ _BY_POINTER = {**_STRUCTS, "imx_pretrained_policy_t": ImxPretrainedPolicy, "imx_
                "imx_inhand_command_t": ImxInhandCommand, "imx_object_state_t": ImxObjectState,
                "imx_articulation_state_t": ImxArticulationState,
                "imx_orch_articulation_t": ImxOrchArticulation, "imx_norm_group_t": ImxNormGroup,
-               "imx_infer_norm_t": ImxInferNorm, "imx_ray_caster_t": ImxRayCaster}  # (a struct of an included header travels as POINTER(class) too)
+               "imx_infer_norm_t": ImxInferNorm, "imx_ray_caster_t": ImxRayCaster, "imx_imu_t": ImxImu}  # (a struct of an included header travels as POINTER(class) too)
 _SIGNATURES = {name: (_abi.ctype(res, _BY_POINTER, ret=True), [_abi.ctype(t, _BY_POINTER) for t in args])
                for name, (res, args, _) in _abi.FUNCTIONS.items()}
 EXPORTS = tuple(_SIGNATURES)
@@ -162,7 +165,7 @@ def lib():
     for which, cls in (*enumerate((ImxState, ImxBuffers, ImxHeadLoss, ImxRolloutSlot, ImxPolicyAct, ImxOrch, ImxEventTerm, ImxDiffIk, ImxOsc)),
                        (10, ImxOrchManip), (11, ImxWeightTerm), (12, ImxPretrainedPolicy), (13, ImxPose2dCommand), (15, ImxInhandCommand), (16, ImxObjectState),
                        (18, ImxArticulationState), (20, ImxOrchArticulation), (22, ImxNormGroup),
-                       (23, ImxInferNorm), (25, ImxRayCaster)):  # the binding's struct layouts against the library's (indices 9, 14, 17, 19, 21 and 24 are unknown)
+                       (23, ImxInferNorm), (25, ImxRayCaster), (27, ImxImu)):  # the binding's struct layouts against the library's (indices 9, 14, 17, 19, 21, 24 and 26 are unknown)
         if int(L.imx_struct_size(which)) != ctypes.sizeof(cls):
             raise ImxError(f"{LIB_PATH}: sizeof({cls.__name__}) is {int(L.imx_struct_size(which))} in the library, {ctypes.sizeof(cls)} in the "
                            "binding -- rebuild with `python -m isaaclab_amd.build`")

@@ -44,6 +44,7 @@ extern "C" size_t imx_struct_size(int which) {
         case 22: return sizeof(imx_norm_group_t);
         case 23: return sizeof(imx_infer_norm_t);
         case 25: return sizeof(imx_ray_caster_t);
+        case 27: return sizeof(imx_imu_t);
         default: return 0;
     }
 }
@@ -233,7 +234,8 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
     for (int k = 0; k < p->nobs; ++k) {
         const int32_t* r = &w[p->obs_off + k * IMX_REC_WORDS];
         const int op = r[IMX_R_OP];
-        IMX_REQUIRE(op >= IMX_O_BASE_POS_Z && op <= IMX_O_ARTICULATION_JOINT_VEL_REL, "plan: unknown observation op %d", op);
+        IMX_REQUIRE((op >= IMX_O_BASE_POS_Z && op <= IMX_O_ARTICULATION_JOINT_VEL_REL) || (op >= IMX_O_IMU_ORIENTATION && op <= IMX_O_IMU_LIN_ACC),
+                    "plan: unknown observation op %d", op);
         const int g = r[IMX_R_WEIGHT];
         IMX_REQUIRE(g >= 0 && g < p->ngroups, "plan: observation record %d names group %d", k, g);
         {
@@ -290,6 +292,11 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
                 IMX_REQUIRE(r[IMX_R_P2] >= IMX_HEADER_WORDS && (size_t)r[IMX_R_P2] + (size_t)d <= nwords,
                             "plan: observation record %d: default table out of range", k);
             }
+        }
+        if (op >= IMX_O_IMU_ORIENTATION && op <= IMX_O_IMU_LIN_ACC) {  // an Imu sensor's data: AUX0 = the sensor's index
+            IMX_REQUIRE(d == (op == IMX_O_IMU_ORIENTATION ? 4 : 3), "plan: imu observation op %d has dim %d", op, d);
+            IMX_REQUIRE(r[IMX_R_AUX0] >= 0 && r[IMX_R_AUX0] < IMX_MAX_IMU, "plan: observation record %d: imu sensor index %d outside [0,%d)", k,
+                        r[IMX_R_AUX0], IMX_MAX_IMU);
         }
         if (op >= IMX_O_ROOT_POS_W && op <= IMX_O_ROOT_ANG_VEL_W)
             IMX_REQUIRE(r[IMX_R_AUX0] == 0 || r[IMX_R_AUX0] == 1, "plan: observation record %d: asset selector %d (0 robot, 1 object)", k, r[IMX_R_AUX0]);
@@ -413,7 +420,8 @@ static int parse_plan(const int32_t* blob, size_t nwords, imx_plan* p) {
         if (op >= IMX_O_ROOT_POS_W && op <= IMX_O_ROOT_ANG_VEL_W) x[10] = w[ro + IMX_R_AUX0];  // the asset: 0 robot, 1 object
         if (op == IMX_O_BODY_INCOMING_WRENCH) x[10] = w[(size_t)w[ro + IMX_R_IDS_OFF] + j / 6] * 6 + j % 6;  // body * 6 + component
         if (op >= IMX_O_REL_EE_DRAWER_DISTANCE && op <= IMX_O_FINGERTIPS_POS) x[10] = w[ro + IMX_R_AUX0];  // the frame table
-        if (op >= IMX_O_ARTICULATION_JOINT_POS_REL) {  // joint id in XC_AUX, its default in XC_RX, the row width J2 in XC_RY
+        if (op >= IMX_O_IMU_ORIENTATION && op <= IMX_O_IMU_LIN_ACC) x[10] = w[ro + IMX_R_AUX0];  // the sensor's index
+        if (op >= IMX_O_ARTICULATION_JOINT_POS_REL && op <= IMX_O_ARTICULATION_JOINT_VEL_REL) {  // joint id in XC_AUX, its default in XC_RX, the row width J2 in XC_RY
             x[10] = w[(size_t)w[ro + IMX_R_IDS_OFF] + j]; x[11] = w[(size_t)w[ro + IMX_R_P2] + j]; x[12] = p->J2;
         }
         if (op == IMX_O_BASE_HEADING_PROJ || op == IMX_O_BASE_ANGLE_TO_TARGET) {  // target_pos: x in XC_P0, y, z in XC_RX, XC_RY

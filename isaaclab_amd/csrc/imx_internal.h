@@ -31,6 +31,13 @@ void imx_set_error(const char* fmt, ...);
         if (!(cond)) IMX_FAIL(__VA_ARGS__); \
     } while (0)
 
+// what the imu_* observation ops read (k_obs_imu): the data tensors of the sensors imx_plan_bind_imu bound, by sensor index
+struct ImuObsView {
+    const float* quat_w[IMX_MAX_IMU];
+    const float* ang_vel_b[IMX_MAX_IMU];
+    const float* lin_acc_b[IMX_MAX_IMU];
+};
+
 // ---- plan ---------------------------------------------------------------------------------------------------------
 struct imx_plan {
     std::vector<int32_t> host;  // validated blob + appended column tables
@@ -59,6 +66,8 @@ struct imx_plan {
     // articulation's joint / body counts and the target-frame counts of the two sensors, as validated by parse_plan
     int ft_off = 0, J2 = 0, B2 = 0, ft_n_ee = 0, ft_n_cab = 0;
     imx_articulation_state_t articulation_state{};  // what imx_plan_bind_articulation_state bound (host side; all NULL = nothing bound)
+    ImuObsView imu{};  // what imx_plan_bind_imu bound (host side), n_imu sensors
+    int n_imu = 0;
 };
 
 // view passed by value to kernels

@@ -170,6 +170,17 @@ IMX_DEV float obs_inhand_value(const PlanView& P, const imx_state_t& S, const im
     return obs_plain_value<true>(P, S, Bf, es, e, x);
 }
 
+// k_obs_imu's column value: imu_orientation / imu_ang_vel / imu_lin_acc (envs/mdp/observations.py:188-231) = the sensor's data.quat_w /
+// ang_vel_b / lin_acc_b as the refresh launch (imx_imu) left them, XC_AUX = the sensor's index; every other column is obs_plain_value's
+IMX_DEV float obs_imu_value(const PlanView& P, const imx_state_t& S, const ImuObsView& X, const imx_buffers_t& Bf,
+                            const float* __restrict__ es, int64_t e, const XCol& x) {
+    const int op = x.a.y, j = x.a.z, aux = x.c.z;
+    if (op == IMX_O_IMU_ORIENTATION) return X.quat_w[aux][e * 4 + j];
+    if (op == IMX_O_IMU_ANG_VEL) return X.ang_vel_b[aux][e * 3 + j];
+    if (op == IMX_O_IMU_LIN_ACC) return X.lin_acc_b[aux][e * 3 + j];
+    return obs_plain_value<true>(P, S, Bf, es, e, x);
+}
+
 // ---- manipulation/cabinet (Isaac-Open-Drawer-Franka-v0): FrameTransformer frames out of the plan's frame table (include/imx.h IMX_FT_*)
 // The pose of the frame whose words start at P.w + fo for env e: its body's pose -- of the robot (S) or of the second articulation
 // (X, B2 bodies per env) by the frame's asset word -- combined with its offset (imx_frame_pose, imx_frame_transformer.h).

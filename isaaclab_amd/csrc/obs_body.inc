@@ -70,6 +70,8 @@
             v = obs_inhand_value(P, S, X, Bf, es, e, x);
 #elif defined(IMX_OBS_CABINET)
             v = obs_cabinet_value(P, S, X, Bf, es, e, x);
+#elif defined(IMX_OBS_IMU)
+            v = obs_imu_value(P, S, X, Bf, es, e, x);
 #else
             v = obs_plain_value<true>(P, S, Bf, es, e, x);
 #endif

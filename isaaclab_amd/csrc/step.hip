@@ -934,6 +934,19 @@ k_obs_cabinet(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, MeshView M
 #undef IMX_OBS_CABINET
 }
 
+// IMU: a plan whose observations read an Imu sensor's data (imu_orientation / imu_ang_vel / imu_lin_acc, envs/mdp/observations.py:188-231;
+// X = the tensors imx_plan_bind_imu bound) runs the same body in a kernel of its own, like the in-hand and cabinet plans.
+template <bool LEAN>
+__global__ void __launch_bounds__(256)
+k_obs_imu(PlanView P, int64_t N, imx_state_t S, imx_buffers_t Bf, MeshView M, const float* __restrict__ frame,
+          const float* __restrict__ noise_u, uint64_t seed, int corrupt, float* __restrict__ ray_hits_out, StepScratch sc, int tail_G,
+          int tail_parts, ImuObsView X) {
+    constexpr bool GENERAL_RAYS = true;
+#define IMX_OBS_IMU
+#include "obs_body.inc"
+#undef IMX_OBS_IMU
+}
+
 // ------------------------------------------------------------------------------------------------- root frame
 __global__ void k_root_frame(int64_t N, const float* __restrict__ q, const float* __restrict__ lv,
                              const float* __restrict__ av, float gx, float gy, float gz, float* __restrict__ olv,
@@ -1249,6 +1262,7 @@ struct ObsKernelChoice {
     bool single_wave;  // k_obs_lean: one single-wave workgroup per 64 rays + one for the env's other columns
     bool inhand;       // k_obs_inhand: a root observation on the rigid object (asset word 1) or goal_quat_diff
     bool cabinet;      // k_obs_cabinet: a FrameTransformer frame observation or a joint observation on the second articulation
+    bool imu;          // k_obs_imu: an observation of an Imu sensor's data
     int scan_rec;
 };
 static ObsKernelChoice choose_obs_kernel(const imx_plan_t* plan) {
@@ -1261,6 +1275,7 @@ static ObsKernelChoice choose_obs_kernel(const imx_plan_t* plan) {
     c.scan_rec = -1;
     c.inhand = false;
     c.cabinet = false;
+    c.imu = false;
     bool object_op = false;  // (k_obs_lean is compiled without it)
     for (int k = 0; k < plan->nobs; ++k) {
         if (w[plan->obs_off + k * IMX_REC_WORDS + IMX_R_OP] == IMX_O_HEIGHT_SCAN) c.scan_rec = k;
@@ -1268,9 +1283,10 @@ static ObsKernelChoice choose_obs_kernel(const imx_plan_t* plan) {
         object_op = object_op || op == IMX_O_OBJECT_POSITION_IN_ROBOT_ROOT_FRAME;
         c.inhand = c.inhand || op == IMX_O_GOAL_QUAT_DIFF ||
                    (op >= IMX_O_ROOT_POS_W && op <= IMX_O_ROOT_ANG_VEL_W && w[plan->obs_off + k * IMX_REC_WORDS + IMX_R_AUX0]);
-        c.cabinet = c.cabinet || op >= IMX_O_REL_EE_DRAWER_DISTANCE;
+        c.cabinet = c.cabinet || (op >= IMX_O_REL_EE_DRAWER_DISTANCE && op <= IMX_O_ARTICULATION_JOINT_VEL_REL);
+        c.imu = c.imu || (op >= IMX_O_IMU_ORIENTATION && op <= IMX_O_IMU_LIN_ACC);
     }
-    c.single_wave = c.lean && c.scan_rec >= 0 && pv.R > 0 && pv.R <= 64 * 15 && !object_op && !c.inhand && !c.cabinet;
+    c.single_wave = c.lean && c.scan_rec >= 0 && pv.R > 0 && pv.R <= 64 * 15 && !object_op && !c.inhand && !c.cabinet && !c.imu;
     return c;
 }
 
@@ -1279,6 +1295,7 @@ extern "C" const char* imx_observations_kernel_name(const imx_plan_t* plan) {
     const ObsKernelChoice c = choose_obs_kernel(plan);
     if (c.single_wave) return c.vertical ? "k_obs_lean<false>" : "k_obs_lean<true>";
     if (c.cabinet) return c.lean ? "k_obs_cabinet<true>" : "k_obs_cabinet<false>";
+    if (c.imu) return c.lean ? "k_obs_imu<true>" : "k_obs_imu<false>";
     if (c.inhand) return c.lean ? "k_obs_inhand<true>" : "k_obs_inhand<false>";
     if (c.vertical) return c.lean ? "k_obs<false,true>" : "k_obs<false,false>";
     return c.lean ? "k_obs<true,true>" : "k_obs<true,false>";
@@ -1336,6 +1353,11 @@ extern "C" int imx_observations(const imx_plan_t* plan, int64_t N, const imx_sta
             case IMX_O_ARTICULATION_JOINT_POS_REL: p = plan->articulation_state.joint_pos; name = "articulation_state.joint_pos"; break;
             case IMX_O_ARTICULATION_JOINT_VEL_REL: p = plan->articulation_state.joint_vel; name = "articulation_state.joint_vel"; break;
             case IMX_O_EE_POS: case IMX_O_FINGERTIPS_POS: p = st->env_origins; name = "env_origins"; break;
+            case IMX_O_IMU_ORIENTATION: case IMX_O_IMU_ANG_VEL: case IMX_O_IMU_LIN_ACC: {  // (AUX0 < IMX_MAX_IMU: parse_plan)
+                const int si = w[plan->obs_off + k * IMX_REC_WORDS + IMX_R_AUX0];
+                p = si < plan->n_imu ? (const void*)1 : nullptr; name = "imu data (imx_plan_bind_imu)";
+                break;
+            }
             default: break;
         }
         IMX_REQUIRE(p, "state tensor '%s' is required by an observation term but missing", name);
@@ -1400,7 +1422,16 @@ extern "C" int imx_observations(const imx_plan_t* plan, int64_t N, const imx_sta
         const unsigned grid = (unsigned)N + (unsigned)tail_parts;
         IMX_REQUIRE(!(ch.cabinet && ch.inhand), "imx_observations: a plan with cabinet (manipulation/cabinet) observations beside observations on the "
                                                 "scene's rigid object (manipulation/inhand) is not supported");
-        if (ch.cabinet) {
+        IMX_REQUIRE(!(ch.imu && (ch.cabinet || ch.inhand)), "imx_observations: a plan with Imu observations beside cabinet or rigid-object "
+                                                            "observations is not supported");
+        if (ch.imu) {
+            if (lean)
+                hipLaunchKernelGGL(k_obs_imu<true>, dim3(grid), dim3(bs), lds, (hipStream_t)stream, pv, N, *st, *bf, mv, frame, noise_u_d, seed,
+                                   enable_corruption, ray_hits_out_d, sc, tail_G, tail_parts, plan->imu);
+            else
+                hipLaunchKernelGGL(k_obs_imu<false>, dim3(grid), dim3(bs), lds, (hipStream_t)stream, pv, N, *st, *bf, mv, frame, noise_u_d, seed,
+                                   enable_corruption, ray_hits_out_d, sc, tail_G, tail_parts, plan->imu);
+        } else if (ch.cabinet) {
             if (lean)
                 hipLaunchKernelGGL(k_obs_cabinet<true>, dim3(grid), dim3(bs), lds, (hipStream_t)stream, pv, N, *st, *bf, mv, frame, noise_u_d, seed,
                                    enable_corruption, ray_hits_out_d, sc, tail_G, tail_parts, plan->articulation_state);

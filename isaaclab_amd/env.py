@@ -679,6 +679,45 @@ class _RaySensor:
         return self._sensor.ranges(range_clip)
 
 
+class _ImuSensor:
+    """``env.scene[<Imu>]``: a ``producers.Imu`` on the robot body its ``prim_path`` ends in, fed that body's link pose and
+    centre-of-mass velocities from the state feed (``body_pos_w`` / ``body_quat_w`` / ``body_lin_vel_w`` / ``body_ang_vel_w``; for the
+    synthetic feed ``body_lin_vel_w`` IS the COM velocity PhysX's ``get_velocities`` returns).  The env advances its clocks
+    ``decimation`` times ``physics_dt`` per step and resets it with its own reset mask, all sensors in one launch.  A sensor an imu_*
+    observation term of the plan reads (``in_plan``) is refreshed by the env before the observation kernel -- inside a captured
+    rollout too; any other is built on first access and refreshes lazily in ``data``, on the eager path."""
+
+    def __init__(self, env, entity, in_plan: bool):
+        from .producers import Imu
+
+        body, com = env._entities.imu(entity)
+        self._env, self.cfg, self.in_plan, self.body_index = env, env._entities.imus[entity], in_plan, body
+        try:
+            env.feed.ensure_dynamics()  # (body_ang_vel_w; a recorded feed has it only when its snapshots carried it)
+        except KeyError:
+            pass
+        self._sensor = Imu(self.cfg, env.num_envs, env.device, body_index=body, com_pos_b=com, name=entity)
+        # ManagerBasedEnv.__init__ -> scene.update(dt=physics_dt) after sim.reset (manager_based_env.py): one update before the first read
+        self._sensor.update(env.physics_dt, *self._inputs())
+
+    def _inputs(self):
+        f = self._env.feed
+        try:
+            return f["body_pos_w"], f["body_quat_w"], f["body_lin_vel_w"], f["body_ang_vel_w"]
+        except KeyError as e:
+            raise KeyError(f"Imu '{self._sensor.name}': the state feed carries no {e}") from None
+
+    def _struct(self, substeps: int, refresh: bool, reset_mask):
+        s = self._sensor
+        s._inputs, s._dt = self._inputs(), self._env.physics_dt  # (shapes were checked when the sensor was built: same feed)
+        return s.struct(substeps=substeps, refresh=refresh, reset_mask=reset_mask)
+
+    @property
+    def data(self):
+        self._sensor._inputs = self._inputs()
+        return self._sensor.data
+
+
 class _Scene:
     def __init__(self, env):
         r = env.plan.robot
@@ -690,6 +729,10 @@ class _Scene:
         self._frame_names = list(env._entities.frames)  # FrameTransformer sensors: built on first access (a scene that is never asked launches nothing)
         # RayCaster sensors that no height_scan term reads (the plan's scanner is fused into the observation kernel): likewise on first access
         self._ray_names = [k for k in env._entities.ray_casters if not (k == "height_scanner" and env.plan.num_rays > 0)]
+        # Imu sensors: those the plan's imu_* terms read exist already (the env owns them), any other likewise on first access
+        self._imu_names = list(env._entities.imus)
+        for s, name in zip(env._imu_sensors, env.plan.imu_sensors):
+            self._e[name] = self.sensors[name] = s
         self._env = env
         self.num_envs = env.num_envs
 
@@ -698,7 +741,7 @@ class _Scene:
         return self._env.feed["env_origins"]
 
     def keys(self):
-        return list(self._e) + [k for k in self._frame_names + self._ray_names if k not in self._e]
+        return list(self._e) + [k for k in self._frame_names + self._ray_names + self._imu_names if k not in self._e]
 
     def __getitem__(self, k):
         if k not in self._e and k in self._frame_names:
@@ -706,6 +749,9 @@ class _Scene:
         elif k not in self._e and k in self._ray_names:
             self._e[k] = self.sensors[k] = _RaySensor(self._env, k)
             self._env._ray_sensors.append(self._e[k])
+        elif k not in self._e and k in self._imu_names:
+            self._e[k] = self.sensors[k] = _ImuSensor(self._env, k, in_plan=False)
+            self._env._imu_sensors.append(self._e[k])
         return self._e[k]
 
 
@@ -826,6 +872,7 @@ class ManagerBasedRLEnv:
         self.terrain: TerrainMesh | None = None
         self._terrain_arg, self._terrain_cell = terrain, terrain_cell  # (a RayCaster of the scene other than the height scanner builds its mesh on first access)
         self._ray_sensors: list = []  # the scene's _RaySensor objects built so far (scene[...]): stepped and reset with the env
+        self._imu_sensors: list = []  # the scene's _ImuSensor objects, the plan's first (built below, once the feed exists)
         if plan.num_rays > 0:
             if terrain is None:
                 raise ValueError("this config has a height scanner: pass terrain=(vertices, triangles)")
@@ -1138,6 +1185,11 @@ class ManagerBasedRLEnv:
             self._ev_part = torch.zeros(int(self._lib.imx_orch_part_floats(N)), device=self.device)
             self._orch_draws = {}  # parity runs: "command" -> (2,N,7) uniforms, "rand_levels" -> (N) int64
             self.defer_step_tail = True
+        # the Imu sensors the plan's imu_* observation terms read, in the order of their index in the records (plan.imu_sensors); sensors
+        # of the scene no term reads join the list when env.scene[...] builds them.  All are stepped and reset in ONE imx_imu launch
+        self._imu_sensors = [_ImuSensor(self, name, in_plan=True) for name in plan.imu_sensors]
+        self._imu_all = torch.ones(N, dtype=torch.bool, device=self.device)
+        self._bind_imu()
         self.scene = _Scene(self)
         self._class_terms: list = []  # instances of class-based Python-evaluated terms, in construction order
         self._ext_funcs = {
@@ -1369,11 +1421,30 @@ class ManagerBasedRLEnv:
             # ... and the second articulation's (imx_articulation_state_t): feed name "articulation_<field>"
             self._articulation_state_cache[idx] = _lib.ImxArticulationState(**{n: snap["articulation_" + n].data_ptr() for n in _lib.ARTICULATION_STATE_FIELDS
                                                                                if "articulation_" + n in snap})
+        if self.plan.imu_sensors:  # (imx_plan_update replaces the plan's host side: bound again like the two below)
+            self._bind_imu()
         if self._reads_object:  # bound to the plan for the launches made with this state
             check(self._lib.imx_plan_bind_object_state(self._plan_h, ctypes.byref(self._object_state_cache[idx])))
         if self._reads_articulation:
             check(self._lib.imx_plan_bind_articulation_state(self._plan_h, ctypes.byref(self._articulation_state_cache[idx])))
         return st
+
+    def _bind_imu(self):
+        """imx_plan_bind_imu: the data tensors of the plan's Imu sensors, by sensor index (fixed addresses: bound once per plan state)."""
+        n = len(self.plan.imu_sensors)
+        if n and len(self._imu_sensors) >= n:
+            arr = (_lib.ImxImu * n)(*[s._sensor._c for s in self._imu_sensors[:n]])
+            check(self._lib.imx_plan_bind_imu(self._plan_h, arr, n))
+
+    def _imu_launch(self, substeps: int, refresh: bool, reset_mask=None):
+        """One ``imx_imu`` launch over every Imu of the scene built so far (``_lib.MAX_IMU`` per launch): ``substeps`` clock advances at
+        ``physics_dt``, the reset of ``reset_mask`` (N,) first, and with ``refresh`` the recompute of the outdated envs -- for the
+        sensors the plan reads only; the others refresh lazily in ``data``.  No host decision: capturable."""
+        sensors = self._imu_sensors
+        for k in range(0, len(sensors), _lib.MAX_IMU):
+            part = sensors[k:k + _lib.MAX_IMU]
+            arr = (_lib.ImxImu * len(part))(*[s._struct(substeps, refresh and s.in_plan, reset_mask) for s in part])
+            check(self._lib.imx_imu(arr, len(part), self.num_envs, _lib.current_stream(self.device)))
 
     def _root_frame(self) -> dict:
         N, f = self.num_envs, self.feed
@@ -1745,6 +1816,12 @@ class ManagerBasedRLEnv:
             self.actuator_net.reset(None if env_ids is None else env_ids)
         for rs in self._ray_sensors:
             rs._reset(None if env_ids is None else env_ids)
+        if self._imu_sensors:  # scene.reset(env_ids), then ObservationManager.compute -> Imu.data: reset and refresh in one launch
+            mask = self._imu_all
+            if env_ids is not None:
+                mask = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)
+                mask[ids] = True
+            self._imu_launch(0, True, mask)
         if self._has_orchestration:
             # _reset_idx(env_ids) (manager_based_rl_env.py:347-392): curriculum, scene.reset, reset events, manager resets with their
             # log entries -- no command compute, no interval events (those belong to step()).  Host-side reductions are fine here
@@ -1812,6 +1889,8 @@ class ManagerBasedRLEnv:
             self.contact_sensor.update(self.feed["net_forces_w_history"][:, 0], self.step_dt)
         for rs in self._ray_sensors:  # scene.update -> RayCaster.update: the clocks only, the cast waits for `data`
             rs._step()
+        if self._imu_sensors:  # scene.update -> Imu.update, decimation times: the clocks only, the refresh waits for the observations
+            self._imu_launch(int(self.cfg_decimation), False)
         self.common_step_counter += 1
         # -- post-physics: counters, terminations, rewards, reset bookkeeping (one kernel)
         if self._ext_funcs["rew"] or self._ext_funcs["term"]:
@@ -1831,6 +1910,10 @@ class ManagerBasedRLEnv:
         self.extras["log"] = self._log_views if not self._pose2d_command or "error_pos_2d" in self.command_term.metrics else self._log_views_before_compute
         for rs in self._ray_sensors:  # _reset_idx -> scene.reset(env_ids): on the device, by the reset mask
             rs._reset(self.reset_buf)
+        if self._imu_sensors:
+            # _reset_idx -> scene.reset(env_ids), then observation_manager.compute -> Imu.data (manager_based_rl_env.py:215-223): ONE launch
+            # resets by the step's mask and refreshes the outdated envs of the sensors the observation kernel reads below
+            self._imu_launch(0, True, self.reset_buf)
         if self._class_terms:
             # _reset_idx reaches the class terms between the reward and the observation pass (manager_based_rl_env.py:215-218 ->
             # RewardManager.reset / ObservationManager.reset).  This route is Python-evaluated anyway: the ids are read like the

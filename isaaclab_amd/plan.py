@@ -413,6 +413,7 @@ class Plan:
     # read, resolved (robots.FrameTable by entity name; None for a sensor the scene lacks), as written to the blob at frame_table_off
     frame_tables: dict = dataclasses.field(default_factory=dict)
     frame_table_off: int = 0
+    imu_sensors: tuple = ()  # the scene's Imu sensors the imu_* observation terms read; a term's sensor index (AUX0) indexes this
 
 
 @dataclasses.dataclass
@@ -910,6 +911,28 @@ def _root_asset(op, c, name, p, rec):
         _quat_unique(c, name, p, rec)
 
 
+_IMU_READS = ("body_pos_w", "body_quat_w", "body_lin_vel_w", "body_ang_vel_w")
+MAX_IMU = _abi.DEFINES["IMX_MAX_IMU"]
+
+
+def _imu_obs(c, name, p, rec):
+    """``imu_orientation`` / ``imu_ang_vel`` / ``imu_lin_acc`` (observations.py:188-231): only ``asset_cfg.name`` is read.  AUX0 = the
+    sensor's index among the Imu sensors this plan reads (``Plan.imu_sensors``, first use first); the sensor is fed the four body
+    tensors of the robot."""
+    ent = _entity_name(p.get("asset_cfg"), "imu")
+    if ent not in c.entities.imus:
+        raise ValueError(f"observation term '{name}': asset_cfg names the scene entity '{ent}', which is not an Imu of the scene "
+                         f"(it has {list(c.entities.imus)})")
+    c.entities.imu(ent)  # refuses debug_vis and a prim_path that ends in no robot body, with the reason
+    if ent not in c.imu_sensors:
+        if len(c.imu_sensors) >= MAX_IMU:
+            raise NotImplementedError(f"observation term '{name}': the plan already reads {MAX_IMU} Imu sensors {c.imu_sensors}; one refresh "
+                                      f"launch carries at most {MAX_IMU}")
+        c.imu_sensors.append(ent)
+    rec["aux0"] = c.imu_sensors.index(ent)
+    _reads(c, *_IMU_READS)
+
+
 _T = f"{_MDP}.terminations:"
 TERMINATION_TERMS = {
     _T + "time_out": _Fused("TIME_OUT"),
@@ -1150,6 +1173,7 @@ OBSERVATION_TERMS = {
     _O + "last_action": _Fused("LAST_ACTION", hook=_last_action, applies=lambda p: p.get("action_name") is None),
     _O + "generated_commands": _Fused("GENERATED_COMMANDS", hook=_generated_commands),
     _O + "body_incoming_wrench": _Fused("BODY_INCOMING_WRENCH", _BODIES, hook=_incoming_wrench),
+    **{_O + f: _Fused(f.upper(), width=w, hook=_imu_obs) for f, w in (("imu_orientation", 4), ("imu_ang_vel", 3), ("imu_lin_acc", 3))},  # :188-231
     _OC + "base_yaw_roll": _Fused("BASE_YAW_ROLL", width=2),  # :19-30
     _OC + "base_up_proj": _Fused("BASE_UP_PROJ", width=1),  # :33-40
     _OC + "base_heading_proj": _Fused("BASE_HEADING_PROJ", width=1, hook=_target_obs),  # :43-58
@@ -1188,6 +1212,7 @@ class PlanCompiler:
         self.state_reads: set[str] = set()
         self.ft_off: int | None = None  # the frame table (_frame_table): written by the first term that reads a FrameTransformer frame
         self.frame_tables: dict = {}
+        self.imu_sensors: list[str] = []  # the Imu sensors the imu_* observation terms read, in index order (_imu_obs)
 
     def compile(self) -> Plan:
         self._scalars()
@@ -1426,6 +1451,10 @@ class PlanCompiler:
             if t.op == O_OPS["HEIGHT_SCAN"]:
                 raise NotImplementedError(f"action term '{name}': low-level observation term '{t.name}' is a height scan (a rough-terrain "
                                           "low-level policy); not on the fused path")
+            if t.op in (O_OPS["IMU_ORIENTATION"], O_OPS["IMU_ANG_VEL"], O_OPS["IMU_LIN_ACC"]):
+                raise NotImplementedError(f"action term '{name}': low-level observation term '{t.name}' ({t.func}) reads an Imu sensor: the "
+                                          "sensor is refreshed once per env step, before the policy observations, not between the low-level "
+                                          "steps; not on the fused path")
         blob = self.blob
         dim = 3
         rec = dict(op=A_JOINT_AFFINE, ids_off=blob.ints([0] * dim), nids=dim, out=self.action_dim, dim=dim, p0=1.0, p1=0.0, flags=0)
@@ -1682,7 +1711,7 @@ class PlanCompiler:
                     n_ext_obs=self.n_ext_obs, gravity_dir=tuple(float(x) for x in gdir), mod_state_dim=self.mod_state,
                     term_slots=len(self.term_slots), processed_action_dim=self.processed_dim, ik_terms=self.ik_terms, osc_terms=self.osc_terms,
                     policy_terms=self.policy_terms, state_reads=tuple(sorted(self.state_reads)), frame_tables=dict(self.frame_tables),
-                    frame_table_off=int(self.ft_off or 0))
+                    frame_table_off=int(self.ft_off or 0), imu_sensors=tuple(self.imu_sensors))
 
 
 def compile_plan(env_cfg: Any, robot: RobotSpec) -> Plan:

@@ -880,3 +880,134 @@ class RayCaster:
         """(N, R) ``min(||ray_hits_w - pos_w||, range_clip)``, a miss = ``range_clip``, after the refresh of ``data`` (same launch)."""
         self._launch(refresh=True, range_clip=range_clip)
         return self._ranges
+
+
+class Imu:
+    """``Imu`` (isaaclab/sensors/imu/imu.py under ``SensorBase``, sensors/sensor_base.py:182-205,287-296) in one launch (``imx_imu``):
+    reset, clocks, and for the outdated envs the sensor pose, the velocity carried from the body's centre of mass to the sensor, both
+    accelerations by numerical differentiation and the four vectors in the sensor's frame.
+
+    ``cfg``: the ``ImuCfg`` as object or dict -- ``offset.pos`` / ``.rot``, ``gravity_bias``, ``update_period``, ``history_length``
+    (> 0 only makes every ``update`` recompute, as in ``SensorBase.update``).  ``body_index``: the sensor sits on column ``b`` of
+    (N, B, .) inputs; None = (N, .) inputs.  ``com_pos_b``: the body's centre of mass in its link frame, (3,) or (N, 3); default zeros.
+
+    ``update(dt, pos_w, quat_w, lin_vel_w, ang_vel_w)`` is ``Imu.update``: the link pose (quaternion w, x, y, z) and the velocities of
+    the centre of mass, kept by reference for ``data`` and never written.  Without ``force_recompute`` only the clocks and flags advance;
+    ``data`` refreshes the outdated envs lazily and has ``pos_w``, ``quat_w``, ``lin_vel_b``, ``ang_vel_b``, ``lin_acc_b``, ``ang_acc_b``.
+    The reference's quirks are kept: the accelerations divide by the ``dt`` of the LAST ``update`` call whatever time has passed since
+    the last refresh, and a reset zeroes ``quat_w`` and the four body-frame vectors but neither ``pos_w`` nor the previous velocities."""
+
+    DATA_FIELDS = ("pos_w", "quat_w", "lin_vel_b", "ang_vel_b", "lin_acc_b", "ang_acc_b")
+
+    def __init__(self, cfg, num_envs: int, device, body_index: int | None = None, com_pos_b=None, name: str = "imu"):
+        N, dev = int(num_envs), torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.name = str(name)
+        if bool(_cfg_field(cfg, "debug_vis", False)):
+            raise NotImplementedError(f"Imu '{self.name}': debug_vis=True: the acceleration markers are not drawn (no visualisation here)")
+        off = _cfg_field(cfg, "offset") or {}
+        pos = tuple(float(x) for x in _cfg_field(off, "pos", (0.0, 0.0, 0.0)))
+        rot = tuple(float(x) for x in _cfg_field(off, "rot", (1.0, 0.0, 0.0, 0.0)))
+        bias = tuple(float(x) for x in _cfg_field(cfg, "gravity_bias", (0.0, 0.0, 9.81)))
+        if len(pos) != 3 or len(rot) != 4 or len(bias) != 3:
+            raise ValueError(f"Imu '{self.name}': offset.pos / offset.rot / gravity_bias must have 3 / 4 / 3 components")
+        period = float(_cfg_field(cfg, "update_period", 0.0))
+        if period < 0.0:
+            raise ValueError(f"Imu '{self.name}': update_period {period} is negative")
+        if body_index is not None and int(body_index) < 0:
+            raise ValueError(f"Imu '{self.name}': body_index {body_index} is negative")
+        self.num_envs, self.device = N, dev
+        self.body_index = None if body_index is None else int(body_index)
+        self.cfg = types.SimpleNamespace(offset=types.SimpleNamespace(pos=pos, rot=rot), gravity_bias=bias, update_period=period,
+                                         history_length=int(_cfg_field(cfg, "history_length", 0) or 0))
+        self.com_pos_b = None
+        if com_pos_b is not None:
+            com = torch.as_tensor(com_pos_b, dtype=torch.float32)
+            if tuple(com.shape) not in ((3,), (N, 3)):
+                raise ValueError(f"Imu '{self.name}': com_pos_b must be (3,) or ({N}, 3), got {tuple(com.shape)}")
+            self.com_pos_b = com.to(dev).contiguous()
+        z = lambda *sh, dtype=torch.float32: torch.zeros(*sh, dtype=dtype, device=dev)  # noqa: E731
+        self._timestamp, self._timestamp_last_update = z(N), z(N)
+        self._is_outdated = torch.ones(N, dtype=torch.bool, device=dev)  # sensor_base.py:_initialize_impl
+        self._all = torch.ones(N, dtype=torch.bool, device=dev)
+        self._data = types.SimpleNamespace(pos_w=z(N, 3), quat_w=z(N, 4), lin_vel_b=z(N, 3), ang_vel_b=z(N, 3), lin_acc_b=z(N, 3), ang_acc_b=z(N, 3))
+        self._data.quat_w[:, 0] = 1.0
+        self._prev_lin_vel_w, self._prev_ang_vel_w = z(N, 3), z(N, 3)
+        self._inputs = None
+        self._dt = None  # Imu._dt: set by update()
+        p = _lib.ptr
+        d = self._data
+        self._c = _lib.ImxImu(body_index=self.body_index or 0, num_bodies=1, com_per_env=int(self.com_pos_b is not None and self.com_pos_b.dim() == 2),
+                              update_period=period, offset_pos=(ctypes.c_float * 3)(*pos), offset_quat=(ctypes.c_float * 4)(*rot),
+                              gravity_bias=(ctypes.c_float * 3)(*bias), com_pos_b_d=p(self.com_pos_b), timestamp_d=p(self._timestamp),
+                              timestamp_last_update_d=p(self._timestamp_last_update), is_outdated_d=p(self._is_outdated), pos_w_d=p(d.pos_w),
+                              quat_w_d=p(d.quat_w), lin_vel_b_d=p(d.lin_vel_b), ang_vel_b_d=p(d.ang_vel_b), lin_acc_b_d=p(d.lin_acc_b),
+                              ang_acc_b_d=p(d.ang_acc_b), prev_lin_vel_w_d=p(self._prev_lin_vel_w), prev_ang_vel_w_d=p(self._prev_ang_vel_w))
+
+    def _check_inputs(self, pos_w, quat_w, lin_vel_w, ang_vel_w):
+        N, b = self.num_envs, self.body_index
+        B = 1
+        if b is not None:
+            if pos_w.dim() != 3 or pos_w.shape[1] <= b:
+                raise ValueError(f"Imu '{self.name}': body_index {b} needs ({N}, B, 3) inputs with B > {b}, got pos_w {tuple(pos_w.shape)}")
+            B = int(pos_w.shape[1])
+        lead = (N,) if b is None else (N, B)
+        for nm, t, w in (("pos_w", pos_w, 3), ("quat_w", quat_w, 4), ("lin_vel_w", lin_vel_w, 3), ("ang_vel_w", ang_vel_w, 3)):
+            if tuple(t.shape) != lead + (w,):
+                raise ValueError(f"Imu '{self.name}': {nm} must be {lead + (w,)}, got {tuple(t.shape)}")
+            if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"Imu '{self.name}': {nm} must be a contiguous float32 tensor on {self.device}")
+        return B
+
+    def struct(self, dt=None, substeps=0, refresh=False, reset_mask=None) -> "_lib.ImxImu":
+        """The sensor's ``imx_imu_t`` for one launch (the env packs several into one ``imx_imu`` call)."""
+        c = self._c
+        c.dt = float(self._dt or 0.0) if dt is None else float(dt)
+        c.substeps, c.refresh = int(substeps), int(bool(refresh))
+        ins = self._inputs or (None, None, None, None)
+        c.body_pos_w_d, c.body_quat_w_d, c.body_lin_vel_w_d, c.body_ang_vel_w_d = (_lib.ptr(t) for t in ins)
+        c.reset_mask_d = _lib.ptr(reset_mask)
+        return c
+
+    def set_inputs(self, pos_w, quat_w, lin_vel_w, ang_vel_w):
+        self._c.num_bodies = self._check_inputs(pos_w, quat_w, lin_vel_w, ang_vel_w)
+        self._inputs = (pos_w, quat_w, lin_vel_w, ang_vel_w)
+
+    def _launch(self, **kw):
+        c = self.struct(**kw)
+        check(lib().imx_imu(ctypes.byref(c), 1, self.num_envs, _lib.current_stream(self.device)))
+
+    def _mask(self, env_ids):
+        N = self.num_envs
+        if env_ids is None or isinstance(env_ids, slice) and env_ids == slice(None):
+            return self._all
+        ids = torch.as_tensor(env_ids, device=self.device)
+        if ids.dtype in (torch.bool, torch.uint8) and tuple(ids.shape) == (N,):
+            return ids.contiguous()
+        m = torch.zeros(N, dtype=torch.bool, device=self.device)
+        m[ids.long()] = True
+        return m
+
+    def reset(self, env_ids=None):
+        """``SensorBase.reset`` + ``Imu.reset`` for ``env_ids`` (None = all; indices or an (N,) mask): clocks to zero, outdated,
+        ``quat_w`` and the four body-frame vectors to zero.  No refresh, so no input is read."""
+        self._launch(reset_mask=self._mask(env_ids))
+
+    def update(self, dt: float, pos_w: torch.Tensor, quat_w: torch.Tensor, lin_vel_w: torch.Tensor, ang_vel_w: torch.Tensor,
+               force_recompute: bool = False, substeps: int = 1, reset_mask=None):
+        """``Imu.update(dt)``, ``substeps`` times, on the link pose and centre-of-mass velocities of the body the sensor sits on (kept
+        by reference for ``data``); ``reset_mask``: those envs are reset first, in the same launch.  With ``force_recompute`` (or a
+        ``history_length`` > 0) the outdated envs are refreshed."""
+        self.set_inputs(pos_w, quat_w, lin_vel_w, ang_vel_w)
+        self._dt = float(dt)
+        self._launch(substeps=substeps, refresh=force_recompute or self.cfg.history_length > 0,
+                     reset_mask=None if reset_mask is None else self._mask(reset_mask))
+
+    @property
+    def data(self):
+        """``SensorBase.data``: ``_update_outdated_buffers`` first (one launch; an env that is not outdated leaves it at once)."""
+        if self._dt is None or self._inputs is None:
+            raise RuntimeError("The update function must be called before the data buffers are accessed the first time.")  # imu.py:144-147
+        self._launch(refresh=True)
+        return self._data

@@ -227,7 +227,10 @@ class SceneEntityResolver:
     resolved to its first target frame by :meth:`frame` and to its source and all its targets by :meth:`frame_table` (``self.frames``
     holds the cfg entries); an ``Articulation`` other than ``robot`` is the scene's second articulation (``self.articulations``,
     :class:`SecondArticulation`): its name tables come with the scene entry (``joint_names`` / ``body_names``: PhysX provides them in
-    the reference, a cfg fixture's side file here), its defaults from the entry's ``init_state``.  More than one is refused."""
+    the reference, a cfg fixture's side file here), its defaults from the entry's ``init_state``.  More than one is refused.  An
+    ``Imu`` (``self.imus`` holds the cfg entries) is resolved by :meth:`imu` to the robot body its ``prim_path`` ends in; the entry may
+    carry ``body_com_pos_b``, the centre of mass of that body in its link frame ((3,), or (B, 3) for every body of the robot: PhysX
+    provides it in the reference), default zeros."""
 
     def __init__(self, robot: RobotSpec, scene: dict | None = None):
         self.joint_names = list(robot.joint_names)
@@ -235,6 +238,7 @@ class SceneEntityResolver:
         self.rigid_objects: dict[str, str] = {}  # entity -> its one body's name
         self.frames: dict[str, dict] = {}
         self.ray_casters: dict[str, dict] = {}  # RayCaster entries (the env serves those no height_scan term reads through producers.RayCaster)
+        self.imus: dict[str, dict] = {}  # Imu entries (producers.Imu; the imu_* observation terms read them inside the fused step)
         self.articulations: dict[str, SecondArticulation] = {}
         for name, ent in (scene or {}).items():
             cls = ent.get("class_type") if isinstance(ent, dict) else None
@@ -245,11 +249,15 @@ class SceneEntityResolver:
                 self.frames[name] = ent
             elif cls and cls.endswith(":RayCaster"):
                 self.ray_casters[name] = ent
+            elif cls and cls.endswith(":Imu"):
+                self.imus[name] = ent
             elif cls and cls.endswith(":Articulation") and name != "robot":
                 self.articulations[name] = SecondArticulation.from_scene_entry(name, ent)
         if len(self.articulations) > 1:
             raise NotImplementedError(f"the scene has {len(self.articulations)} articulations beside the robot {list(self.articulations)}; the "
                                       "fused path carries the state of one second articulation")
+        for name in self.imus:  # an Imu the resolver cannot serve is refused here, with the reason, whether a term reads it or not
+            self.imu(name)
 
     @property
     def second(self) -> "SecondArticulation | None":
@@ -264,7 +272,38 @@ class SceneEntityResolver:
         if entity in self.articulations:
             return self.articulations[entity].joint_names if kind == "joint" else self.articulations[entity].body_names
         raise ValueError(f"The scene entity '{entity}' does not exist. Available entities: "
-                         f"{['robot', 'contact_forces', 'height_scanner'] + list(self.rigid_objects) + list(self.frames) + list(self.articulations)}.")
+                         f"{['robot', 'contact_forces', 'height_scanner'] + list(self.rigid_objects) + list(self.frames) + list(self.articulations) + list(self.imus)}.")
+
+    def imu(self, entity: str) -> tuple[int, list | None]:
+        """Imu ``entity`` resolved: (index of the robot body its ``prim_path`` ends in -- 0 for the articulation root --, the body's
+        ``com_pos_b`` from the entry's ``body_com_pos_b`` table or None).  Refused with the reason: ``debug_vis=True``, a body of the
+        second articulation or the rigid object, a last segment that is no body at all."""
+        if entity not in self.imus:
+            raise ValueError(f"The scene entity '{entity}' is not an Imu of the scene (it has {list(self.imus)}).")
+        cfg = self.imus[entity]
+        if cfg.get("debug_vis"):
+            raise NotImplementedError(f"Imu '{entity}': debug_vis=True: the acceleration markers are not drawn (no visualisation here)")
+        body = str(cfg.get("prim_path", "")).rstrip("/").rsplit("/", 1)[-1]
+        names = self.body_names
+        if body in ("Robot", "robot") or (names and body == names[0]):
+            idx = 0  # the articulation root
+        elif body in names:
+            idx = names.index(body)
+        elif any(body in a.body_names for a in self.articulations.values()) or body in self.rigid_objects.values():
+            raise NotImplementedError(f"Imu '{entity}': its prim_path ends in '{body}', a body of a second articulation or of the rigid object; "
+                                      "the sensor is fed the body states of the robot only")
+        else:
+            raise ValueError(f"Imu '{entity}': its prim_path ends in '{body}', which is neither a body of the robot ({names}) nor its root")
+        com = cfg.get("body_com_pos_b")
+        if com is not None:
+            com = [list(map(float, r)) for r in com] if isinstance(com[0], (list, tuple)) else [float(x) for x in com]
+            if isinstance(com[0], list):
+                if len(com) != len(names) or any(len(r) != 3 for r in com):
+                    raise ValueError(f"Imu '{entity}': body_com_pos_b must be (3,) or ({len(names)}, 3)")
+                com = com[idx]
+            elif len(com) != 3:
+                raise ValueError(f"Imu '{entity}': body_com_pos_b must be (3,) or ({len(names)}, 3)")
+        return idx, com
 
     def frame_table(self, entity: str) -> "FrameTable":
         """FrameTransformer ``entity`` resolved: its source frame and every target frame in cfg order, each on the body its ``prim_path``

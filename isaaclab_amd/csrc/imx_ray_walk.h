@@ -17,7 +17,8 @@
 // P.z lies in the triangle's z-range.  The walk is in the cell c with t_enter <= t(P) <= t_exit at that moment; the existing walk finds
 // the triangle in c's 3x3 block (its own premise), so the dilated range of c contains the triangle's, and the ray's z over
 // [t_enter, t_exit] contains P.z: the two intervals meet and c is not skipped.  The ray's interval is widened by `slack` (1 mm + 1e-5
-// relative) for the rounding of t, of the ray's z and of a grazing ray's hit parameter, which is a convex combination of the corners'.
+// relative in z + 1e-6 of the origin's xy distance to the far side of the grid) for the rounding of t, of the ray's z and of a grazing
+// ray's hit parameter, which is a convex combination of the corners'.
 #pragma once
 
 #include "imx_raycast.h"
@@ -39,7 +40,8 @@ IMX_DEV bool cast_ray_pruned(const MeshView& m, const RayBoundsView& zb, float o
     const WoopRay r = woop_setup(ox, oy, oz, dx, dy, dz);
     float best = max_dist;
     face = -1;
-    const float gx_lo = m.x0, gy_lo = m.y0, gx_hi = m.x0 + m.nx * m.cell, gy_hi = m.y0 + m.ny * m.cell;
+    const float gm = grid_margin(m, ox, oy);  // (the clip of cast_ray, see there)
+    const float gx_lo = m.x0 - gm, gy_lo = m.y0 - gm, gx_hi = m.x0 + m.nx * m.cell + gm, gy_hi = m.y0 + m.ny * m.cell + gm;
     float t0 = 0.0f, t1 = max_dist;
     if (dx != 0.0f) {
         const float ta = (gx_lo - ox) / dx, tb = (gx_hi - ox) / dx;
@@ -56,7 +58,13 @@ IMX_DEV bool cast_ray_pruned(const MeshView& m, const RayBoundsView& zb, float o
         return false;
     }
     // the slab of the mesh in z, widened by the slack of the cell test (a ray is never clipped tighter than its cells are tested)
-    const float slack0 = 1.0e-3f + 1.0e-5f * (fabsf(oz) + fmaxf(fabsf(zb.zmin), fabsf(zb.zmax)));
+    // The hit parameter is t = sum w_i t_i over the corners' own parameters t_i = (corner - origin)[kz] / d[kz] with the computed weights
+    // w_i; its rounding, times dz, is a height error of a few ulps of the largest |corner - origin| in x or y -- nothing on a terrain a
+    // few tens of metres wide, 0.1 m on the 2e6 m ground plane, where a ray that starts a few centimetres past the plane and points
+    // away is still a hit (t = 0) of the exhaustive search.  1e-6 (16 ulps) of the origin's distance to the far side of the grid
+    const float far_xy = fmaxf(fmaxf(fabsf(ox - gx_lo), fabsf(ox - gx_hi)), fmaxf(fabsf(oy - gy_lo), fabsf(oy - gy_hi)));
+    const float slack_xy = 1.0e-3f + 1.0e-6f * far_xy;
+    const float slack0 = slack_xy + 1.0e-5f * (fabsf(oz) + fmaxf(fabsf(zb.zmin), fabsf(zb.zmax)));
     const float z_lo = zb.zmin - 2.0f * slack0, z_hi = zb.zmax + 2.0f * slack0;
     if (dz != 0.0f) {
         const float ta = (z_lo - oz) / dz, tb = (z_hi - oz) / dz;
@@ -104,12 +112,12 @@ IMX_DEV bool cast_ray_pruned(const MeshView& m, const RayBoundsView& zb, float o
             // cell of this tile may therefore end up to one cell's crossing time after tt
             tt = fmaxf(tt + fminf(tdx, tdy), t_exit);
             const float za = oz + t_enter * dz, zc = oz + tt * dz;
-            const float slack = 1.0e-3f + 1.0e-5f * (fabsf(oz) + fabsf(za) + fabsf(zc));
+            const float slack = slack_xy + 1.0e-5f * (fabsf(oz) + fabsf(za) + fabsf(zc));
             tile_out = z_miss(za, zc, 2.0f * slack, zb.tile_z[tl]);
         }
         if (!tile_out) {
             const float za = oz + t_enter * dz, zc = oz + fminf(t_exit, t1) * dz;
-            const float slack = 1.0e-3f + 1.0e-5f * (fabsf(oz) + fabsf(za) + fabsf(zc));
+            const float slack = slack_xy + 1.0e-5f * (fabsf(oz) + fabsf(za) + fabsf(zc));
             if (!z_miss(za, zc, slack, zb.cell_z[imx_cell_index(ix, iy, m.ntx)])) {
                 for (int jy = -1; jy <= 1; ++jy)
                     for (int jx = -1; jx <= 1; ++jx) test_cell(m, r, ix + jx, iy + jy, best, face);

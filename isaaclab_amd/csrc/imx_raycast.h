@@ -381,6 +381,16 @@ IMX_DEV bool cast_ray_vertical_wave(const MeshView& m, bool active, float ox, fl
     return true;
 }
 
+// The general walk clips a ray to the grid's extent grown by this much.  The Woop test accepts a hit up to its own rounding OUTSIDE a
+// triangle's edge, so a ray that passes the mesh's outermost edge or corner at a rounding's distance -- aimed at a corner vertex, or with
+// a zero component and its origin a denormal beside the first line -- is a hit of the exhaustive search; clipped to the bare extent, the
+// rounding of the two divisions decides between t0 <= t1 and a miss without a walk.  The snap band of the grid (tau cells) plus 1e-6
+// of the largest coordinate involved (16 fp32 ulps) covers it; the start cell is clamped into the grid as before.
+IMX_DEV float grid_margin(const MeshView& m, float ox, float oy) {
+    const float big = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fmaxf(fmaxf(fabsf(m.x0), fabsf(m.y0)), fmaxf(fabsf(m.x0 + m.nx * m.cell), fabsf(m.y0 + m.ny * m.cell))));
+    return IMX_GRID_TAU * m.cell + 1.0e-6f * big;
+}
+
 // Closest hit with t in [0, max_dist]; returns false on a miss.
 IMX_DEV bool cast_ray(const MeshView& m, float ox, float oy, float oz, float dx, float dy, float dz, float max_dist,
                       float& t_hit, int32_t& face) {
@@ -398,7 +408,8 @@ IMX_DEV bool cast_ray(const MeshView& m, float ox, float oy, float oz, float dx,
         if (nbx && nby) test_cell(m, r, ix + nbx, iy + nby, best, face);
     } else {
         // general ray: 2-D DDA over the grid; every visited cell tests its 3x3 block (covers the tau-shrunk lists)
-        const float gx_lo = m.x0, gy_lo = m.y0, gx_hi = m.x0 + m.nx * m.cell, gy_hi = m.y0 + m.ny * m.cell;
+        const float gm = grid_margin(m, ox, oy);
+        const float gx_lo = m.x0 - gm, gy_lo = m.y0 - gm, gx_hi = m.x0 + m.nx * m.cell + gm, gy_hi = m.y0 + m.ny * m.cell + gm;
         float t0 = 0.0f, t1 = max_dist;
         if (dx != 0.0f) {
             const float ta = (gx_lo - ox) / dx, tb = (gx_hi - ox) / dx;

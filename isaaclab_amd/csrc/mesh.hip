@@ -57,8 +57,10 @@ static inline void cell_range(float lo, float hi, float origin, float inv_cell, 
         const int c = (int)std::floor(0.5f * (g_lo + g_hi));
         a = b = c;
     }
-    a = std::max(a, 0);
-    b = std::min(b, n - 1);
+    // both ends into the grid: a wall ON the grid's last line has g == n in fp32 where the double floor(extent / cell) + 1 counted n cells
+    // (5 / 0.2f, 200 / 0.1f), and a range of [n, n - 1] would list it nowhere; the last cell owns it, rays on that line snap to it
+    a = std::min(std::max(a, 0), n - 1);
+    b = std::max(std::min(b, n - 1), 0);
 }
 
 extern "C" int imx_mesh_create(const float* verts, int64_t V, const uint32_t* tris, int64_t F, float cell_size,
